@@ -2,6 +2,7 @@
 frames (BASELINE.json metric), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload neo360|vanilla|mip360|mip360_128|pixelnerf]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 (the first form with N > 1 starts its N ranks itself, one process per GPU; both forms run the same code)
@@ -9,8 +10,14 @@ frames (BASELINE.json metric), one process per GPU.
 Default workload = the north-star path, BASELINE.json configs[2] (and [3] when N > 1): the NeO-360
 tri-planar decoder, 3 source views, 640x480, 128 coarse + 256 fine samples per ray, inside + outside
 sphere, reference chunk 1024.  `--workload vanilla` = configs[1], `mip360` / `mip360_128` = configs[4]
-(reference default 64/64/32 and BASELINE's wording 64 + 128).  At N = 1 the JSON line also carries
-one-step numbers of the vanilla and mip360 configurations (`other_workloads`).
+(reference default 64/64/32 and BASELINE's wording 64 + 128).
+
+A plain run sets up, warms up, times the K steps and prints the line (headline + the roofline of the timed
+steps).  `--full` adds everything that needs runs of its own: the CPU baseline and parity against it, the
+once-per-scene set-up time, the reference-style chunk loop, and at N = 1 the exact fp32 kernels, one-step
+numbers of the vanilla and mip360 configurations (`other_workloads`) and the training step.  The single
+--cpu-rays / --others / --exact-f32 / --setup-timing / --chunk-loop / --train-step switches override either.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 A step = ray generation for this rank's range of the frame + coarse and fine render of its
 contiguous range of whole 1024-ray chunks (+ ONE RCCL all-gather of the packed (rgb,depth,acc)
@@ -66,6 +73,34 @@ def physical_cores():
     except OSError:
         pass
     return os.cpu_count() or 1
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays a caller of the timed path received from its last step, one DIR/<name>.npy each, float32
+    (float64 stays float64).  Above DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of its rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        for name, a in out.items():
+            if a.ndim and a.shape[0] > 1:
+                keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+                rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+                out[name] = a[rows]
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def frame_outputs(frame):
+    """The (R, 5) frame of render_frame_sharded as its caller reads it: rgb, depth, acc."""
+    return {"rgb": frame[:, :3], "depth": frame[:, 3], "acc": frame[:, 4]}
 
 
 # the translation unit of each workload's dominant kernel (split arithmetic) + the headers it is built from
@@ -575,36 +610,45 @@ def run_train(args, dev, emit=True):
         loss = loss + 0.01 * (training.eff_distloss(lv[1][1], lv[1][3], interval) + training.eff_distloss(lv[1][2], lv[1][4], interval))
         loss.backward()
         opt.step()
-        return loss
+        return loss, lv
 
     for i in range(args.warmup + 1):
         step(i)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = step(100 + i)
+        loss, lv = step(100 + i)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
-    # phases of one step (events): forward, loss + backward, optimizer
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    opt.zero_grad(set_to_none=True)
-    ev[0].record()
-    lv = net(batch, True, False, 0.0, 0.0, out_depth=False, seed=7)
-    ev[1].record()
-    l2 = sum(((l[0] - target) ** 2).mean() for l in lv) + 0.01 * (training.eff_distloss(lv[1][1], lv[1][3], interval) + training.eff_distloss(lv[1][2], lv[1][4], interval))
-    l2.backward()
-    ev[2].record()
-    opt.step()
-    ev[3].record()
-    torch.cuda.synchronize()
+    if emit and args.dump_outputs:
+        # the last timed step's loss and per-level rgb, and the four MLPs as its optimizer step left them
+        arrays = {"loss": loss.detach(), "rgb_coarse": lv[0][0], "rgb_fine": lv[1][0]}
+        arrays.update({"param." + k: v for k, v in net.named_parameters()})
+        dump_outputs(args.dump_outputs, arrays)
+    phases = None
+    if args.full:
+        # phases of one step (events): forward, loss + backward, optimizer
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        opt.zero_grad(set_to_none=True)
+        ev[0].record()
+        lv = net(batch, True, False, 0.0, 0.0, out_depth=False, seed=7)
+        ev[1].record()
+        l2 = sum(((l[0] - target) ** 2).mean() for l in lv) + 0.01 * (training.eff_distloss(lv[1][1], lv[1][3], interval) + training.eff_distloss(lv[1][2], lv[1][4], interval))
+        l2.backward()
+        ev[2].record()
+        opt.step()
+        ev[3].record()
+        torch.cuda.synchronize()
+        phases = {"forward": ev[0].elapsed_time(ev[1]), "loss_and_backward": ev[1].elapsed_time(ev[2]), "optimizer": ev[2].elapsed_time(ev[3])}
     out = {"metric": "NeO-360 training step: rays/s through forward + loss + backward + optimizer step", "value": B / dt, "unit": "rays/s",
            "steps_per_s": 1.0 / dt, "ms_per_step": dt * 1e3, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True,
            "dtype": "f32 (exact fp32 MFMA GEMMs of the training operators)", "data": "synthetic",
            "config": {"workload": "neo360 training step, %d rays, 3 source views, 128 + 256 samples inside + outside the sphere, randomized "
                                   "sampling, full-size feature maps (3x128x120x160 planes, 3x512x240x320 latent) receiving gradients, Adam on the four MLPs" % B,
                       "rays_per_step": B},
-           "phases_ms": {"forward": ev[0].elapsed_time(ev[1]), "loss_and_backward": ev[1].elapsed_time(ev[2]), "optimizer": ev[2].elapsed_time(ev[3])},
            "loss": float(loss.detach())}
+    if phases is not None:
+        out["phases_ms"] = phases
     # roofline of the step (round 6; VERDICT r5 task 6): the matrix work the training operators EXECUTE per step on the fp32 MFMA
     # pipe (the fused per-row chain kernels, k_sgemm forward / dX, k_dw weight gradients - the library's own GEMMs, texel-space projection included), counted from
     # the operator shapes: per point-view the NeRFPPMLP chain without the 512 latent columns (they are applied once per texel:
@@ -809,18 +853,32 @@ def main():
     ap.add_argument("--precision", choices=("auto", "f32", "f16x3"), default="auto",
                     help="MLP arithmetic: exact fp32 MFMA, or fp16 MFMA with hi/lo-split operands (fp32-equivalent, "
                          "the default of every renderer)")
-    ap.add_argument("--cpu-rays", type=int, default=-1, help="rays in the CPU-baseline sample (0 = skip, -1 = default)")
-    ap.add_argument("--others", type=int, default=-1, help="1/0: also time one step of the other BASELINE configs (default: N == 1)")
-    ap.add_argument("--setup-timing", type=int, default=1, dest="setup_timing",
-                    help="0: skip the scene_setup_ms measurement (two extra one-chunk renders; counter passes want only the frame's launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baseline, scene set-up, chunk loop and (N == 1) the exact fp32 "
+                         "kernels, the other configurations and the training step")
+    ap.add_argument("--dump-outputs", default=None, dest="dump_outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--cpu-rays", type=int, default=-1, help="rays in the CPU-baseline sample (0 = skip, -1 = default: with --full)")
+    ap.add_argument("--others", type=int, default=-1, help="1/0: also time one step of the other BASELINE configs (default: --full and N == 1)")
+    ap.add_argument("--setup-timing", type=int, default=-1, dest="setup_timing",
+                    help="1/0: the scene_setup_ms measurement (two extra one-chunk renders; counter passes want only the frame's launches; "
+                         "default: with --full)")
     ap.add_argument("--exact-f32", type=int, default=-1, dest="exact_f32",
                     help="1/0: also time 2 frames of the same workload on the exact fp32-MFMA kernels (default: as --others)")
     ap.add_argument("--train-step", type=int, default=1, dest="train_step",
                     help="1/0: with the other workloads (N == 1), also time five steps of the NeO-360 training step (`training_step` record)")
-    ap.add_argument("--chunk-loop", type=int, default=1, dest="chunk_loop",
-                    help="1/0: also time the frame as the reference's own chunk loop drives the module (300 forward calls; neo360, N = 1)")
+    ap.add_argument("--chunk-loop", type=int, default=-1, dest="chunk_loop",
+                    help="1/0: also time the frame as the reference's own chunk loop drives the module (300 forward calls; neo360, N = 1; "
+                         "default: with --full)")
     ap.add_argument("--fake", action="store_true", help=argparse.SUPPRESS)     # CPU plumbing test: gloo + FakeRunner (tests/test_bench_cpu.py)
     args = ap.parse_args()
+    # what only --full runs by default; an explicit 1 / count still turns a single part on
+    if args.cpu_rays < 0 and not args.full:
+        args.cpu_rays = 0
+    if args.setup_timing < 0:
+        args.setup_timing = int(args.full)
+    if args.chunk_loop < 0:
+        args.chunk_loop = int(args.full)
 
     # one process per GPU.  Under torch.distributed.run the ranks exist already (RANK set); a plain `python bench.py --gpus N`
     # with N > 1 starts them itself - the driver's N = 1 command line with another N must not die on an assertion
@@ -845,10 +903,12 @@ def main():
         run = FakeRunner(world, rank, dist)
         dt, _, frame = run.timed(args.steps, args.warmup)
         ranks = rank_records(dist, world, rank, local_rank, None, run.local_dt / args.steps * 1e3, numa)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame_outputs(frame))
         if rank == 0:
             ok = bool(torch.equal(frame[:, 0], torch.arange(run.R, dtype=torch.float32))) if dist is not None else True
             print(json.dumps({"metric": "plumbing test (no measurement)", "fake": True, "n_gpus": world, "steps": args.steps,
-                              "warmup": args.warmup, "frame_rows": int(frame.shape[0]), "frame_in_order": ok,
+                              "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "frame_rows": int(frame.shape[0]), "frame_in_order": ok,
                               "rank_column": sorted(set(frame[:, 4].tolist())) if dist is not None else [0.0],
                               "self_spawned": bool(os.environ.get("NEO360_BENCH_SELF_SPAWNED")), "value": run.R * args.steps / dt,
                               "ranks": ranks}))
@@ -877,6 +937,8 @@ def main():
     run = Runner(args.workload, args.precision, dev, world, rank, dist, setup_timing=bool(args.setup_timing))
     dt, kern, frame = run.timed(args.steps, args.warmup)
     R = run.R
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame_outputs(frame))
     ranks = rank_records(dist, world, rank, local_rank, dev, run.local_dt / args.steps * 1e3, numa)
 
     if rank == 0:
@@ -934,7 +996,7 @@ def main():
                                     "max_abs_depth": float((depth_g - depth_c).abs().max()),
                                     "psnr_db": render.psnr(rgb_g, rgb_c), "rays": n}
             out["speedup_vs_cpu"] = out["value"] / base["value"]
-        others = (world == 1) if args.others < 0 else bool(args.others)
+        others = (world == 1 and args.full) if args.others < 0 else bool(args.others)
         exact = others if args.exact_f32 < 0 else bool(args.exact_f32)
         if exact and world == 1 and run.split:
             # the same workload on the EXACT fp32-MFMA kernels (module.precision = "f32"), 1 warm-up + 2 timed frames:
@@ -996,7 +1058,7 @@ def main():
                 try:
                     tr = run_train(ta, dev, emit=False)
                     out["training_step"] = {"ms_per_step": tr["ms_per_step"], "value": tr["value"], "unit": tr["unit"], "steps": 5,
-                                            "rays_per_step": tr["config"]["rays_per_step"], "phases_ms": tr["phases_ms"],
+                                            "rays_per_step": tr["config"]["rays_per_step"], "phases_ms": tr.get("phases_ms"),
                                             "matrix_pipe_frac_of_157.3": tr["roofline"]["frac"], "dtype": tr["dtype"],
                                             "workload": tr["config"]["workload"]}
                 finally:

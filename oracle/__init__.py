@@ -21,6 +21,7 @@ under import stubs (`tests/golden/_ref_loader.py`) and committed as fixtures by
 integer-hash generator `neo360_amd.synth`, fixtures hold expected outputs).
 `tests/test_oracle_golden.py` checks every oracle stage and the end-to-end
 renders against those fixtures on every CPU run; `tests/test_oracle_vs_reference.py`
-re-derives them live when /root/reference is present.
+checks whole forwards and mip360 gradients against the reference's outputs in
+`tests/golden/g10_live.npz`.
 """
 from . import rays, sampling, encoding, compositing, gather, mlp, vanilla, neo360, pixelnerf, pillar, training  # noqa: F401

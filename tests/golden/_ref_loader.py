@@ -2,8 +2,7 @@
 
 TEST INFRASTRUCTURE, build-container only.  The GPU box has no /root/reference;
 nothing under tests/ that runs there imports this module.  It is used by
-`make_golden.py` (to produce the committed fixtures) and by the
-`-m "not gpu"` oracle-pinning tests, which skip when the reference is absent.
+`make_golden.py` only, to produce the committed fixtures.
 
 The reference's Python needs third-party modules that are not installed here
 (numba, kornia, cv2, torchvision, pytorch_lightning, wandb, ...).  We inject

@@ -206,3 +206,35 @@ def mip_rays(n, radius_px=0.0012):
     spread = synth.uniform(61, "mip_radii", (n, 1), 0.8, 1.2)
     rays["radii"] = spread * radius_px
     return rays
+
+
+def mip_mlp_param_grads(state, prefix, x0, dy_density, dir_enc=None, dy_rgb=None, skip=4):
+    """Gradients of the linear layers of one Mip-NeRF 360 MLP (state keys under `prefix`) from what crossed its boundary in a
+    forward / backward of the reference: its input features x0 (points x 504), the gradient arriving at the density head and -
+    for a NeRF MLP - the view-direction encoding beside the bottleneck and the gradient arriving at the rgb head.  The trunk is
+    Linear + ReLU with the input concatenated back after every `skip`-th layer; torch fp32 ops as the reference runs them."""
+    F = torch.nn.functional
+    with torch.enable_grad():
+        p = {k[len(prefix):]: v.clone().requires_grad_(True) for k, v in state.items()
+             if k.startswith(prefix) and (k.endswith(".weight") or k.endswith(".bias"))}
+        layer = lambda name, x: F.linear(x, p[name + ".weight"], p[name + ".bias"])
+        x = x0
+        i = 0
+        while "pts_linear.%d.weight" % i in p:
+            x = F.relu(layer("pts_linear.%d" % i, x))
+            if i % skip == 0 and i > 0:
+                x = torch.cat([x, x0], dim=-1)
+            i += 1
+        outs, grads = [layer("density_layer", x)], [dy_density]
+        if dir_enc is not None:
+            h = torch.cat([layer("bottleneck_layer", x), dir_enc], dim=-1)
+            h0, i = h, 0
+            while "views_linear.%d.weight" % i in p:
+                h = F.relu(layer("views_linear.%d" % i, h))
+                if i % skip == 0 and i > 0:
+                    h = torch.cat([h, h0], dim=-1)
+                i += 1
+            outs.append(layer("rgb_layer", h))
+            grads.append(dy_rgb)
+        torch.autograd.backward(outs, grads)
+    return {prefix + k: v.grad for k, v in p.items()}

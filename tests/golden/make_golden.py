@@ -692,6 +692,96 @@ def g9_pillar():
     save("g9_pillar", **out)
 
 
+# ---------------------------------------------------------------------------------
+# G10 the reference's outputs for the calls of tests/test_oracle_vs_reference.py (same inputs, same seeds)
+# ---------------------------------------------------------------------------------
+
+def _quiet(fn, *a, **k):
+    import contextlib
+    import io
+    with contextlib.redirect_stdout(io.StringIO()):
+        return fn(*a, **k)
+
+
+def g10_live():
+    out = {}
+    # vanilla NeRF, 64 rays
+    net = _quiet(ref.load("models.vanilla_nerf.model").NeRF)
+    net.load_state_dict(synth.vanilla_state(0))
+    want = net.eval()(cases.strided_rays(64), False, False, 0.2, 3.0)
+    out.update(van_rgb0=want[0][0], van_rgb1=want[1][0], van_depth1=want[1][2])
+    # PixelNeRF late-fusion MLP stage on synthetic encodings / latents
+    M = ref.load("models.vanilla_nerf.model_pixel")
+    for nv in (1, 3):
+        mlp = _quiet(M.NeRFMLP, 0, 10, 4)
+        mlp.load_state_dict(synth.pixelnerf_mlp_state(61 + nv, ""))
+        P = 40
+        x = synth.uniform(63, "pix_x%d" % nv, (nv, P, 63), -1, 1)
+        cond = synth.uniform(63, "pix_c%d" % nv, (nv * P, 27), -1, 1)
+        latent = synth.normal(63, "pix_l%d" % nv, (nv * P, 512), 0.3)
+        r, s = mlp.eval()(x, cond, latent, combine_inner_dims=(nv, P))
+        out["pixmlp_rgb_nv%d" % nv], out["pixmlp_sigma_nv%d" % nv] = r.reshape(-1, 3), s.reshape(-1, 1)
+    # PixelNeRF and NeO-360 decoders on the small scene
+    scene = cases.small_scene()
+    net = ref_pixelnerf(synth.pixelnerf_state(0), scene)
+    want = net(cases.neo_batch(cases.strided_rays(48)), False, False, 0.2, 2.5)
+    out.update(pix_rgb0=want[0][0], pix_rgb1=want[1][0], pix_depth1=want[1][2])
+    net = ref_nerf_tp(synth.nerf_tp_state(0), scene)
+    net.num_coarse_samples, net.num_fine_samples = 24, 40
+    want = net(cases.neo_batch(cases.strided_rays(40)), False, False, 0.0, 0.0, out_depth=True)
+    out.update(neo_rgb0=want[0][0], neo_rgb1=want[1][0], neo_out4_1=want[1][4], neo_out5_1=want[1][5])
+    # Mip-NeRF 360, deterministic forward
+    M = ref.load("models.mipnerf360.model")
+    net = M.MipNeRF360(num_prop_samples=32, num_nerf_samples=16)
+    net.load_state_dict(synth.mip360_state(0, weight_gain=0.5), strict=True)
+    with torch.enable_grad():
+        rend, hist = net(cases.mip_rays(24), 1.0, False, False, 0.2, 3.0)
+    out.update(mip_rgb=rend[-1]["rgb"].detach(), mip_sdist=hist[-1]["sdist"].detach())
+    # Mip-NeRF 360, randomized forward + autograd gradients of every parameter.  All 9.3 M gradient entries follow from what crossed
+    # each MLP's boundary - its input features and the gradients arriving at its heads (cases.mip_mlp_param_grads) - so that is what
+    # is stored; the gradients rebuilt from it are checked here against the reference's own autograd result
+    n_prop, n_nerf, B = 16, 8, 12
+    state = synth.mip360_state(0, weight_gain=0.25)
+    net = M.MipNeRF360(num_prop_samples=n_prop, num_nerf_samples=n_nerf)
+    net.load_state_dict(state, strict=True)
+    seen = {}
+    for mname, mod in net.named_modules():
+        if isinstance(mod, torch.nn.Linear):
+            def fwd(m, inp, res, mname=mname):
+                e = seen.setdefault(mname, {"x": [], "dy": []})
+                e["x"].append(inp[0].detach().reshape(-1, m.in_features))
+                call = len(e["x"]) - 1
+                res.register_hook(lambda g, call=call: e["dy"].append((call, g.detach().reshape(-1, m.out_features))))
+            mod.register_forward_hook(fwd)
+    torch.manual_seed(5)
+    with torch.enable_grad():
+        rend, hist = net(cases.mip_rays(B), 0.5, True, True, 0.2, 3.0)
+        loss_ref = (rend[-1]["rgb"] ** 2).mean() + sum((h["weights"] ** 2).sum(-1).mean() for h in hist)
+        names = [k for k, p in net.named_parameters()]
+        g_ref = torch.autograd.grad(loss_ref, [p for _, p in net.named_parameters()], allow_unused=True)
+    for lvl in range(3):
+        out["rnd_sdist%d" % lvl] = hist[lvl]["sdist"].detach()
+        out["rnd_w%d" % lvl] = hist[lvl]["weights"].detach()
+    out["rnd_rgb"] = rend[-1]["rgb"].detach()
+    out["rnd_names"] = np.frombuffer("\n".join(names).encode(), dtype=np.uint8)       # parameter order, as bytes (fixtures load as tensors)
+    out["rnd_unused"] = np.array([g is None for g in g_ref])
+    xs = lambda name: torch.cat(seen[name]["x"])
+    dys = lambda name: torch.cat([g for _, g in sorted(seen[name]["dy"], key=lambda c: c[0])])
+    rebuilt = {}
+    for m in sorted({k.split(".pts_linear")[0] for k in names if ".pts_linear" in k}):
+        tag = m.replace(".", "")
+        out["rnd_x0_" + tag], out["rnd_dyd_" + tag] = xs(m + ".pts_linear.0"), dys(m + ".density_layer")
+        if m + ".rgb_layer" in seen:
+            width = net.get_submodule(m + ".bottleneck_layer").out_features
+            out["rnd_dir_" + tag], out["rnd_dyrgb_" + tag] = xs(m + ".views_linear.0")[:, width:], dys(m + ".rgb_layer")
+        rebuilt.update(cases.mip_mlp_param_grads(state, m + ".", out["rnd_x0_" + tag], out["rnd_dyd_" + tag],
+                                                 out.get("rnd_dir_" + tag), out.get("rnd_dyrgb_" + tag)))
+    for k, g in zip(names, g_ref):
+        if g is not None:
+            assert float((rebuilt[k] - g).norm()) <= 1e-5 * float(g.norm()) + 1e-12, (k, float((rebuilt[k] - g).norm() / g.norm()))
+    save("g10_live", **out)
+
+
 def main(which):
     jobs = {
         "g1": g1_raygen, "g2": g2_aabb, "g3": g3_stages, "g3n": g3_pdf_noise, "g4v": g4_vanilla,
@@ -735,6 +825,7 @@ def main(which):
         "g7": g7_pixelnerf,
         "g8": g8_training,
         "g9": g9_pillar,
+        "g10": g10_live,
     }
     for name, fn in jobs.items():
         if not which or name in which:

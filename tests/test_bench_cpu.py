@@ -8,6 +8,8 @@ import socket
 import subprocess
 import sys
 
+import torch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -84,3 +86,31 @@ def test_single_process_default():
     assert r.returncode == 0, r.stderr[-2000:]
     out = _line(r.stdout)
     assert out["n_gpus"] == 1 and out["frame_rows"] == 640 * 480
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs DIR: the frame of the last timed step as DIR/{rgb,depth,acc}.npy in float32; the line keeps ms_per_step."""
+    r = subprocess.run([sys.executable, BENCH, "--fake", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], env=_env(),
+                       cwd="/tmp", capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = _line(r.stdout)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    import numpy as np
+    rgb, depth, acc = (np.load(str(tmp_path / (n + ".npy"))) for n in ("rgb", "depth", "acc"))
+    assert rgb.dtype == depth.dtype == acc.dtype == np.float32
+    assert rgb.shape == (640 * 480, 3) and depth.shape == acc.shape == (640 * 480,)
+    assert np.array_equal(rgb[:, 0], np.arange(640 * 480, dtype=np.float32))        # the fake renderer writes each ray's index
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """Above the 64 MB cap every array keeps the same seeded sample of rows, the same from run to run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    big = {"a": torch.arange(12 << 20, dtype=torch.float32).reshape(-1, 3), "b": torch.arange(3 << 20, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "1"), big)
+    bench.dump_outputs(str(tmp_path / "2"), big)
+    a1, b1 = np.load(str(tmp_path / "1" / "a.npy")), np.load(str(tmp_path / "1" / "b.npy"))
+    assert len(a1) < (4 << 20) and a1.nbytes + b1.nbytes <= bench.DUMP_LIMIT_BYTES and b1.dtype == np.float64 and a1.dtype == np.float32
+    assert np.array_equal(a1, np.load(str(tmp_path / "2" / "a.npy"))) and np.array_equal(b1, np.load(str(tmp_path / "2" / "b.npy")))
+    assert np.array_equal(a1[:, 0] % 3, np.zeros(len(a1))) and np.all(np.diff(a1[:, 0]) > 0)     # whole rows, in order

@@ -16,6 +16,7 @@ import subprocess
 import sys
 import warnings
 
+import numpy as np
 import pytest
 import torch
 
@@ -381,11 +382,11 @@ def test_static_operand_trip_latches_until_weights_or_scene_change():
 
 # ---- bench.py: both launch forms, scene set-up from events ----------------------------------------------------------------
 
-def _bench(cmd_prefix, extra_env=None):
+def _bench(cmd_prefix, extra_env=None, args=("--full", "--steps", "1", "--warmup", "0", "--cpu-rays", "0", "--others", "0", "--exact-f32", "0")):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env or {})
-    r = subprocess.run(cmd_prefix + [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--cpu-rays", "0",
-                                    "--others", "0", "--exact-f32", "0"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    r = subprocess.run(cmd_prefix + [os.path.join(ROOT, "bench.py"), "--gpus", "1"] + list(args), env=env, cwd=ROOT, capture_output=True,
+                       text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     rows = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(rows) == 1
@@ -406,6 +407,20 @@ def test_bench_plain_form_scene_setup_from_events():
     # gave 7.2-7.7 ms on most, 93 / 95 / 7.6 / 7.7 / 15 / 174 ms within one call on a loaded one, and a steady 94-100 ms on another
     # (GPU work in the window: ~5 ms in rocprofv3).  A test that asserted either would fail the whole suite on such a box.
     assert ss["total_ms"] == sorted(runs)[1] and 0.5 < ss["total_ms"] < 5000.0, ss
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain run times exactly --steps steps, reports ms_per_step and runs nothing of --full; --dump-outputs writes the last
+    timed step's frame as its caller reads it."""
+    out = _bench([sys.executable], args=("--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)))
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "rays/s"
+    for key in ("cpu_baseline", "scene_setup", "chunk_loop", "exact_f32", "other_workloads", "training_step"):
+        assert key not in out, key
+    assert out["roofline"]["all_evaluator_launches"]["launches"] == 2 * 4       # two timed frames: inside / outside x coarse / fine
+    rgb, depth, acc = (np.load(str(tmp_path / (n + ".npy"))) for n in ("rgb", "depth", "acc"))
+    assert rgb.shape == (480 * 640, 3) and depth.shape == acc.shape == (480 * 640,)
+    assert rgb.dtype == depth.dtype == acc.dtype == np.float32
+    assert np.isfinite(rgb).all() and np.isfinite(depth).all() and float(rgb.std()) > 0
 
 
 # ---- the training call's fused point / activation operators (round 5) ------------------------------------------------------

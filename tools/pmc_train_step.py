@@ -1,5 +1,5 @@
 """HBM traffic of one NeO-360 training step: sums FETCH_SIZE / WRITE_SIZE (two counter-only rocprofv3 passes over
-`bench.py --workload neo360_train --steps S --warmup 0 --cpu-rays 0`) over every kernel of the run and divides by the steps the run
+`bench.py --workload neo360_train --full --steps S --warmup 0 --cpu-rays 0`) over every kernel of the run and divides by the steps the run
 executed (warm-up + timed + the phase-timing step), per kernel family as well.  usage: pmc_train_step.py <dir with pass1 / pass2> <steps>"""
 import csv, glob, json, os, sys
 root, steps = sys.argv[1], float(sys.argv[2])
