@@ -377,10 +377,11 @@ int neo_tp_gather_map_slice_backward(neo_ctx* ctx, long texels, long pitch, int 
                                      float focal, float cx, float cy, const float* g_out, float* g_map, void* stream);
 int neo_tp_mlp_train_forward_pre(neo_ctx* ctx, int input_ch, const float* const* w, const float* const* b, const float* x_enc,
                                  const float* pre, const float* world_feat, const float* cond, int NV, long P, float* tape,
-                                 float* raw_rgb, float* raw_sigma, void* stream);
+                                 float* raw_rgb, float* raw_sigma, int* chain_mode, void* stream);
 int neo_tp_mlp_train_backward_pre(neo_ctx* ctx, int input_ch, const float* const* w, const float* x_enc, const float* world_feat,
                                   const float* cond, int NV, long P, const float* tape, const float* g_rgb, const float* g_sigma,
-                                  float* const* gw, float* const* gb, float* g_x_enc, float* g_pre, float* g_world, void* stream);
+                                  float* const* gw, float* const* gb, float* g_x_enc, float* g_pre, float* g_world, int chain_mode,
+                                  void* stream);
 
 /* One linear layer of a training chain the caller composes (models whose MLP has no fused training kernel: PixelNeRF's decoder,
  * vanilla_nerf/model_pixel.py:96-131): y (rows, out_f) = x (rows, in_f) W^T + bias [then ReLU] (accumulate != 0: added onto y
@@ -391,10 +392,13 @@ int neo_linear_forward(neo_ctx* ctx, long rows, int out_f, int in_f, const float
                        const float* bias, int relu, int accumulate, float* y, long ldy, void* stream);
 int neo_linear_input_grad(neo_ctx* ctx, long rows, int in_f, int out_f, const float* gy, long ldy, const float* w, long ldw,
                           int accumulate, float* gx, long ldx, void* stream);
-/* Schedule of the projected-space NeRFPPMLP training chain (neo_tp_mlp_train_forward_pre / _backward_pre), process-wide: 1 (default) =
+/* Schedule of the projected-space training chains (neo_tp_mlp_train_forward_pre, neo_pix_mlp_train_forward_pre), process-wide: 1 (default) =
  * everything per row - layers 0..3, bottleneck, view layer 0; backward: the input-gradient chain g_y0 -> g_z0 and g_world - as ONE
  * kernel each way with the activation tile in LDS and every layer written to HBM once (csrc/train_chain.h); 0 = one GEMM launch per
- * layer (rounds 3-5).  Same exact-fp32 products in both; mode < 0 only queries.  Returns the previous mode. */
+ * layer (rounds 3-5).  Same exact-fp32 products in both; mode < 0 only queries.  Returns the previous mode.
+ * The mode applies to the NEXT forward: the two modes write different tape layouts, so each *_forward_pre reports the mode it used
+ * through `chain_mode` (may be null) and the matching *_backward_pre must be passed that value - the backward never reads this
+ * setting, and changing it between a forward and its backward is harmless. */
 int neo_train_chain_mode(int mode);
 /* PixelNeRF's late-fusion MLP under autograd as ONE chain each way (round 6; vanilla_nerf/model_pixel.py:96-131 inside the training
  * step :255-300): rows R = NV * P view-major; x_enc (R, 63) camera-frame encodings, pre (R, 128) = the gathered PROJECTED latent
@@ -404,10 +408,11 @@ int neo_train_chain_mode(int mode);
  * untouched: their gradient is the texel-space GEMM's), g_pre (R, 128) = dL/dz0 and, when g_x_enc is not null, dL/dx_enc. */
 long neo_pix_mlp_train_tape_floats(int NV, long P);
 int neo_pix_mlp_train_forward_pre(neo_ctx* ctx, const float* const* w, const float* const* b, const float* x_enc, const float* pre,
-                                  const float* cond, int NV, long P, float* tape, float* raw_rgb, float* raw_sigma, void* stream);
+                                  const float* cond, int NV, long P, float* tape, float* raw_rgb, float* raw_sigma, int* chain_mode,
+                                  void* stream);
 int neo_pix_mlp_train_backward_pre(neo_ctx* ctx, const float* const* w, const float* x_enc, const float* cond, int NV, long P,
                                    const float* tape, const float* g_rgb, const float* g_sigma, float* const* gw, float* const* gb,
-                                   float* g_x_enc, float* g_pre, void* stream);
+                                   float* g_x_enc, float* g_pre, int chain_mode, void* stream);
 /* Mip-NeRF 360's MLPs under autograd as ONE chain each way (round 6; mipnerf360/model.py:107-176 inside the training step :236-365):
  * rows = R rays x n intervals, x0 (rows, 504) integrated encodings (neo_mip_encode; data, no gradient), d_enc (R, 27) one direction
  * encoding per ray.  width / depth = netwidth / netdepth (256 x 4 proposal, 1024 x 8 NeRF; the layer after index 4 reads [h | x0]),

@@ -81,14 +81,15 @@ SIGNATURES = {
     "neo_pix_gather_map": (_i, [_vp, _vp, ctypes.c_long, _i, _vp, ctypes.c_long, c_float_p, _i, _f, _f, _f, _vp, _vp]),
     "neo_pix_gather_map_backward": (_i, [_vp, ctypes.c_long, _i, _vp, ctypes.c_long, c_float_p, _i, _f, _f, _f, _vp, _vp, _vp]),
     "neo_tp_mlp_train_forward_pre": (_i, [_vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _i, ctypes.c_long, _vp, _vp,
-                                          _vp, _vp]),
+                                          _vp, ctypes.POINTER(_i), _vp]),
     "neo_tp_mlp_train_backward_pre": (_i, [_vp, _i, ctypes.POINTER(_vp), _vp, _vp, _vp, _i, ctypes.c_long, _vp, _vp, _vp,
-                                           ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _vp]),
+                                           ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _i, _vp]),
     "neo_train_chain_mode": (_i, [_i]),
     "neo_pix_mlp_train_tape_floats": (ctypes.c_long, [_i, ctypes.c_long]),
-    "neo_pix_mlp_train_forward_pre": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _i, ctypes.c_long, _vp, _vp, _vp, _vp]),
+    "neo_pix_mlp_train_forward_pre": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _i, ctypes.c_long, _vp, _vp, _vp,
+                                           ctypes.POINTER(_i), _vp]),
     "neo_pix_mlp_train_backward_pre": (_i, [_vp, ctypes.POINTER(_vp), _vp, _vp, _i, ctypes.c_long, _vp, _vp, _vp,
-                                            ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp]),
+                                            ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _i, _vp]),
     "neo_mip_mlp_train_tape_floats": (ctypes.c_long, [_i, _i, _i, ctypes.c_long, _i]),
     "neo_mip_mlp_train_forward": (_i, [_vp, _i, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, ctypes.c_long, _i, _vp, _vp, _vp]),
     "neo_mip_mlp_train_backward": (_i, [_vp, _i, _i, _i, ctypes.POINTER(_vp), _vp, _vp, ctypes.c_long, _i, _vp, _vp, _vp,

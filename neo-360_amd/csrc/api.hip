@@ -161,8 +161,8 @@ int neo_ctx_create(int device, neo_ctx** out) {
     if (!g.ok) return fail(NEO_ERR_HIP, "hipSetDevice(%d) failed", device);
     neo_ctx* c = new neo_ctx();
     c->device = device;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->flags), sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(c->flags, 0, sizeof(uint32_t));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->flags), neo_ctx::FLAG_WORDS * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->flags, 0, neo_ctx::FLAG_WORDS * sizeof(uint32_t));
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->flag_host), neo_ctx::FLAG_RING * sizeof(uint32_t), hipHostMallocDefault);
     for (int i = 0; e == hipSuccess && i < neo_ctx::FLAG_RING; ++i) e = hipEventCreateWithFlags(&c->flag_ev[i], hipEventDisableTiming);
     if (e != hipSuccess) {
@@ -211,12 +211,32 @@ int neo_ctx_destroy(neo_ctx* ctx) {
     return NEO_OK;
 }
 
+namespace {
+// Read-and-clear of the assertion word as ONE device atomic (a vector global atomic swap, its old value stored to this reader's own
+// device slot).  The three readers below used to copy the word and then clear it with a second operation: with overlapped calls
+// (two side streams, models.CallOverlap) a kernel of the other lane could atomicOr a bit between one reader's copy and its clear,
+// and that bit was wiped unseen.  An atomic swap has no such window: every atomicOr lands either before it (and is returned) or
+// after it (and stays in the word for the next read).
+__global__ void k_take_flags(uint32_t* __restrict__ word, uint32_t* __restrict__ out) {
+    if (threadIdx.x == 0) out[0] = atomicExch(word, 0u);
+}
+
+// word -> device slot (atomic swap) -> host (copy behind it on the same stream).  slot: 0 .. FLAG_RING - 1 the deferred ring's,
+// FLAG_RING the synchronous readers' (they wait before returning, so they never share it with a read in flight).
+hipError_t take_flags_async(neo_ctx* ctx, int slot, uint32_t* host, hipStream_t s) {
+    uint32_t* dev = ctx->flags + 1 + slot;
+    hipLaunchKernelGGL(k_take_flags, dim3(1), dim3(64), 0, s, ctx->flags, dev);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(host, dev, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+}
+}  // namespace
+
 int neo_ctx_poll_flags(neo_ctx* ctx, uint32_t* flags, void* stream) {
     ENTER(ctx);
     REQUIRE(flags != nullptr, "null flags");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(flags, ctx->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemsetAsync(ctx->flags, 0, sizeof(uint32_t), s));
+    HIP_TRY(take_flags_async(ctx, neo_ctx::FLAG_RING, flags, s));
     HIP_TRY(hipStreamSynchronize(s));
     ctx->blocking_waits += 1;
     return NEO_OK;
@@ -240,8 +260,7 @@ int neo_ctx_post_flags(neo_ctx* ctx, void* stream) {
     }
     ctx->flag_unposted = false;
     const int slot = static_cast<int>(ctx->flag_posted % neo_ctx::FLAG_RING);
-    HIP_TRY(hipMemcpyAsync(ctx->flag_host + slot, ctx->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemsetAsync(ctx->flags, 0, sizeof(uint32_t), s));
+    HIP_TRY(take_flags_async(ctx, slot, ctx->flag_host + slot, s));
     HIP_TRY(hipEventRecord(ctx->flag_ev[slot], s));
     ctx->flag_posted += 1;
     return NEO_OK;
@@ -269,8 +288,7 @@ int neo_ctx_take_flags(neo_ctx* ctx, int wait, void* stream, uint32_t* flags, in
         // calls after the last posted read (their post found the ring full): one synchronous read covers them
         uint32_t now = 0;
         hipStream_t s = static_cast<hipStream_t>(stream);
-        HIP_TRY(hipMemcpyAsync(&now, ctx->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemsetAsync(ctx->flags, 0, sizeof(uint32_t), s));
+        HIP_TRY(take_flags_async(ctx, neo_ctx::FLAG_RING, &now, s));
         HIP_TRY(hipStreamSynchronize(s));
         ctx->blocking_waits += 1;
         ctx->flag_unposted = false;

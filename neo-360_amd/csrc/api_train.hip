@@ -417,8 +417,10 @@ int neo_tp_mlp_train_backward(neo_ctx* ctx, int input_ch, const float* const* w,
 
 int neo_tp_mlp_train_forward_pre(neo_ctx* ctx, int input_ch, const float* const* w, const float* const* b, const float* x_enc,
                                  const float* pre, const float* world_feat, const float* cond, int NV, long P, float* tape,
-                                 float* raw_rgb, float* raw_sigma, void* stream) {
+                                 float* raw_rgb, float* raw_sigma, int* chain_mode, void* stream) {
     ENTER(ctx);
+    const int chain = neo::train_chain_mode(-1);          // read ONCE: the tape layout this forward writes (returned for the backward)
+    if (chain_mode) *chain_mode = chain;
     REQUIRE(input_ch == 3 || input_ch == 4, "input_ch must be 3 (inside the sphere) or 4 (outside)");
     REQUIRE(NV >= 1 && P >= 0, "bad shape");
     if (P == 0) return NEO_OK;
@@ -426,14 +428,16 @@ int neo_tp_mlp_train_forward_pre(neo_ctx* ctx, int input_ch, const float* const*
     REQUIRE(w && b && x_enc && pre && world_feat && cond && tape && raw_rgb && raw_sigma, "null pointer");
     for (int i = 0; i < 9; ++i) REQUIRE(w[i] && b[i], "null weight / bias pointer");
     neo::launch_tp_train_forward(input_ch * 21, w, b, x_enc, nullptr, world_feat, cond, NV, P, tape, raw_rgb, raw_sigma,
-                                 static_cast<hipStream_t>(stream), pre);
+                                 static_cast<hipStream_t>(stream), pre, chain);
     return check_launch();
 }
 
 int neo_tp_mlp_train_backward_pre(neo_ctx* ctx, int input_ch, const float* const* w, const float* x_enc, const float* world_feat,
                                   const float* cond, int NV, long P, const float* tape, const float* g_rgb, const float* g_sigma,
-                                  float* const* gw, float* const* gb, float* g_x_enc, float* g_pre, float* g_world, void* stream) {
+                                  float* const* gw, float* const* gb, float* g_x_enc, float* g_pre, float* g_world, int chain_mode,
+                                  void* stream) {
     ENTER(ctx);
+    REQUIRE(chain_mode == 0 || chain_mode == 1, "chain_mode must be the 0 / 1 the forward returned");
     REQUIRE(NV >= 1 && P >= 0, "bad shape");
     if (P == 0) return NEO_OK;
     REQUIRE(input_ch == 3 || input_ch == 4, "input_ch must be 3 (inside the sphere) or 4 (outside)");
@@ -443,7 +447,7 @@ int neo_tp_mlp_train_backward_pre(neo_ctx* ctx, int input_ch, const float* const
     ORDERED(ctx, static_cast<hipStream_t>(stream));
     if (ctx->train_scratch.reserve(neo::tp_train_scratch_floats(NV, P) * sizeof(float))) return NEO_ERR_NOMEM;
     neo::launch_tp_train_backward(input_ch * 21, w, x_enc, nullptr, world_feat, cond, NV, P, tape, ctx->train_scratch.as<float>(),
-                                  g_rgb, g_sigma, gw, gb, g_x_enc, nullptr, g_world, static_cast<hipStream_t>(stream), g_pre);
+                                  g_rgb, g_sigma, gw, gb, g_x_enc, nullptr, g_world, static_cast<hipStream_t>(stream), g_pre, chain_mode);
     return check_launch();
 }
 
@@ -452,21 +456,25 @@ int neo_train_chain_mode(int mode) { return neo::train_chain_mode(mode); }
 long neo_pix_mlp_train_tape_floats(int NV, long P) { return (NV >= 1 && P >= 0) ? (long)neo::pix_train_tape_floats(NV, P) : 0; }
 
 int neo_pix_mlp_train_forward_pre(neo_ctx* ctx, const float* const* w, const float* const* b, const float* x_enc, const float* pre,
-                                  const float* cond, int NV, long P, float* tape, float* raw_rgb, float* raw_sigma, void* stream) {
+                                  const float* cond, int NV, long P, float* tape, float* raw_rgb, float* raw_sigma, int* chain_mode,
+                                  void* stream) {
     ENTER(ctx);
+    const int chain = neo::train_chain_mode(-1);          // read ONCE: the tape layout this forward writes (returned for the backward)
+    if (chain_mode) *chain_mode = chain;
     REQUIRE(NV >= 1 && P >= 0, "bad shape");
     if (P == 0) return NEO_OK;
     REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
     REQUIRE(w && b && x_enc && pre && cond && tape && raw_rgb && raw_sigma, "null pointer");
     for (int i = 0; i < 9; ++i) REQUIRE(w[i] && b[i], "null weight / bias pointer");
-    neo::launch_pix_train_forward(w, b, x_enc, pre, cond, NV, P, tape, raw_rgb, raw_sigma, static_cast<hipStream_t>(stream));
+    neo::launch_pix_train_forward(w, b, x_enc, pre, cond, NV, P, tape, raw_rgb, raw_sigma, static_cast<hipStream_t>(stream), chain);
     return check_launch();
 }
 
 int neo_pix_mlp_train_backward_pre(neo_ctx* ctx, const float* const* w, const float* x_enc, const float* cond, int NV, long P,
                                    const float* tape, const float* g_rgb, const float* g_sigma, float* const* gw, float* const* gb,
-                                   float* g_x_enc, float* g_pre, void* stream) {
+                                   float* g_x_enc, float* g_pre, int chain_mode, void* stream) {
     ENTER(ctx);
+    REQUIRE(chain_mode == 0 || chain_mode == 1, "chain_mode must be the 0 / 1 the forward returned");
     REQUIRE(NV >= 1 && P >= 0, "bad shape");
     if (P == 0) return NEO_OK;
     REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
@@ -475,7 +483,7 @@ int neo_pix_mlp_train_backward_pre(neo_ctx* ctx, const float* const* w, const fl
     ORDERED(ctx, static_cast<hipStream_t>(stream));
     if (ctx->train_scratch.reserve(neo::pix_train_scratch_floats(NV, P) * sizeof(float))) return NEO_ERR_NOMEM;
     neo::launch_pix_train_backward(w, x_enc, cond, NV, P, tape, ctx->train_scratch.as<float>(), g_rgb, g_sigma, gw, gb, g_x_enc, g_pre,
-                                   static_cast<hipStream_t>(stream));
+                                   static_cast<hipStream_t>(stream), chain_mode);
     return check_launch();
 }
 

@@ -131,7 +131,7 @@ extern "C" void neo_linspace_host(float start, float end, int steps, float* out)
 
 struct neo_ctx {
     int device = 0;
-    uint32_t* flags = nullptr;  // device word, bit0 = ray missed the unit sphere
+    uint32_t* flags = nullptr;  // device word, bit0 = ray missed the unit sphere; followed by FLAG_RING + 1 read slots (api.hip take_flags_async)
     neo_host::MlpSlot vanilla[2];
     neo_host::MlpSlot tp[4];
     neo_host::MlpSlot mip[3];
@@ -182,6 +182,7 @@ struct neo_ctx {
     int precision = 1;   // 1 (default): fp16 MFMA with hi/lo-split operands (fp32-equivalent); 0: exact fp32 MFMA
     // deferred reads of the flag word (neo_ctx_post_flags / neo_ctx_take_flags): pinned host words + one event each
     static constexpr int FLAG_RING = 64;
+    static constexpr int FLAG_WORDS = 2 + FLAG_RING;   // the word, one device slot per ring entry, one for the synchronous reads
     uint32_t* flag_host = nullptr;
     hipEvent_t flag_ev[FLAG_RING] = {};
     uint64_t flag_posted = 0, flag_taken = 0;    // monotone; slot = index % FLAG_RING

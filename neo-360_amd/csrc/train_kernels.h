@@ -14,14 +14,15 @@ size_t tp_train_tape_floats(int NV, long P);
 size_t tp_train_scratch_floats(int NV, long P);
 void launch_tp_train_forward(int pe, const float* const* w, const float* const* b, const float* x_enc, const float* local,
                              const float* world, const float* cond, int NV, long P, float* tape, float* raw_rgb,
-                             float* raw_sigma, hipStream_t s, const float* pre = nullptr);
+                             float* raw_sigma, hipStream_t s, const float* pre = nullptr, int chain = 0);
 void launch_tp_train_backward(int pe, const float* const* w, const float* x_enc, const float* local, const float* world,
                               const float* cond, int NV, long P, const float* tape, float* scratch, const float* g_rgb,
                               const float* g_sigma, float* const* gw, float* const* gb, float* g_x_enc, float* g_local,
-                              float* g_world, hipStream_t s, float* g_pre = nullptr);
+                              float* g_world, hipStream_t s, float* g_pre = nullptr, int chain = 0);
 
-// 1 (default): the per-row part of the projected-space NeRFPPMLP chain runs as one kernel each way (train_chain.h); 0: layer by layer.
-// mode < 0 only queries.  Returns the previous mode.
+// 1 (default): the per-row part of the projected-space NeRFPPMLP / PixelNeRF chains runs as one kernel each way (train_chain.h);
+// 0: layer by layer.  mode < 0 only queries.  Returns the previous mode.  The launchers take the mode as `chain` (pre-projected paths
+// only): a forward's mode fixes its tape layout and the matching backward must be given the same value.
 int train_chain_mode(int mode);
 
 // PixelNeRF's MLP (vanilla_nerf/model_pixel.py:96-131) on the projected latent: pre (R, 128), x_enc (R, 63), cond (R, 27).
@@ -29,10 +30,10 @@ int train_chain_mode(int mode);
 size_t pix_train_tape_floats(int NV, long P);
 size_t pix_train_scratch_floats(int NV, long P);
 void launch_pix_train_forward(const float* const* w, const float* const* b, const float* x_enc, const float* pre, const float* cond,
-                              int NV, long P, float* tape, float* raw_rgb, float* raw_sigma, hipStream_t s);
+                              int NV, long P, float* tape, float* raw_rgb, float* raw_sigma, hipStream_t s, int chain);
 void launch_pix_train_backward(const float* const* w, const float* x_enc, const float* cond, int NV, long P, const float* tape,
                                float* scratch, const float* g_rgb, const float* g_sigma, float* const* gw, float* const* gb,
-                               float* g_x_enc, float* g_pre, hipStream_t s);
+                               float* g_x_enc, float* g_pre, hipStream_t s, int chain);
 
 // Mip-NeRF 360 MLP (mipnerf360/model.py:107-176): rows = R x n intervals, x0 (rows, 504), d_enc (R, 27); W / D = netwidth / netdepth, rgb = 1 with
 // the colour branch.  w / b order as neo_mip_upload_mlp.  Outputs activated: rgbdens (rows, 4) = [rgb | density].

@@ -637,7 +637,11 @@ void dw_gemm(int M, int N, int K, const float* Z, long ldz, const float* X, long
 #include "train_chain.h"
 
 const int g_heads_fused = [] { const char* e = getenv("NEO360_TRAIN_HEADS"); return e ? atoi(e) : 1; }();    // 0: the P-sized forward tail as separate launches (A/B)
-int g_chain_fused = 1;      // 1: the per-row part of the projected-space NeRFPPMLP chain as one kernel each way (train_chain.h); 0: layer by layer
+// 1: the per-row part of the projected-space NeRFPPMLP / PixelNeRF chains as one kernel each way (train_chain.h); 0: layer by layer.
+// Read by the FORWARD entry points only, which hand the mode they used back to the caller: the two modes lay the activation tape out
+// differently (fused: no per-view bottleneck / view-layer rows, the view means in their first P rows), so the backward takes the
+// forward's mode as an argument and a toggle between a forward and its backward cannot make it read the tape in the wrong layout.
+int g_chain_fused = 1;
 
 }  // namespace
 
@@ -683,12 +687,12 @@ int train_chain_mode(int mode) {
 // half of `pre` and reduce over [x_enc | world] only - the 512-wide segments of both GEMMs (and of their dX / dW) are gone.
 void launch_tp_train_forward(int pe, const float* const* w, const float* const* b, const float* x_enc, const float* local,
                              const float* world, const float* cond, int NV, long P, float* tape, float* raw_rgb,
-                             float* raw_sigma, hipStream_t s, const float* pre) {
+                             float* raw_sigma, hipStream_t s, const float* pre, int chain) {
     const long R = (long)NV * P;
     const int K0 = pe + 640;
     float* h0 = tape; float* h1 = h0 + R * 128; float* h2 = h1 + R * 128; float* h3 = h2 + R * 128;
     float* bott = h3 + R * 128; float* y0 = bott + R * 128; float* hm = y0 + R * 64; float* ym = hm + P * 128; float* y1 = ym + P * 64;
-    if (pre && g_chain_fused && (pe == 63 || pe == 84)) {
+    if (pre && chain && (pe == 63 || pe == 84)) {
         // one kernel for everything per row: layers 0..3 (train_chain.h).  Behind relu(L3_v) the network is linear up to the view means
         // (no activation on the bottleneck; view layer 0 is averaged over the views before its ReLU), so the bottleneck and view
         // layer 0 run on the MEANS, P rows instead of NV P: W4a mean_v(W6 h3_v + b6) + W4c mean_v(cond_v) + b4 = W4a (W6 hm + b6) + W4c cm + b4.
@@ -762,12 +766,12 @@ size_t pix_train_scratch_floats(int NV, long P) {
 }
 
 void launch_pix_train_forward(const float* const* w, const float* const* b, const float* x_enc, const float* pre, const float* cond,
-                              int NV, long P, float* tape, float* raw_rgb, float* raw_sigma, hipStream_t s) {
+                              int NV, long P, float* tape, float* raw_rgb, float* raw_sigma, hipStream_t s, int chain) {
     const long R = (long)NV * P;
     const int pe = 63, K0 = pe + 512, VC = 128;                     // VC: netwidth_condition (model_pixel.py:44)
     float* h0 = tape; float* h1 = h0 + R * 128; float* h2 = h1 + R * 128; float* h3 = h2 + R * 128;
     float* bott = h3 + R * 128; float* y0 = bott + R * 128; float* hm = y0 + R * VC; float* ym = hm + P * 128; float* y1 = ym + P * VC;
-    if (g_chain_fused) {
+    if (chain) {
         // the four per-row layers as ONE kernel (train_chain.h, PIX form)
         ChainFwdArgs a{w[0], w[1], w[2], w[3], b[0], b[1], b[2], b[3], x_enc, nullptr, pre, h0, h1, h2, h3, R, pe};
         hipLaunchKernelGGL((k_tp_chain_fwd<8, true>), dim3((unsigned)((R + CH_ROWS - 1) / CH_ROWS)), dim3(256), 0, s, a);
@@ -778,7 +782,7 @@ void launch_pix_train_forward(const float* const* w, const float* const* b, cons
     gemm<false, false>((int)R, 128, 128, h1, 128, w[2], 128, h2, 128, epi(b[2], 1), 1, s);
     gemm<false, false>((int)R, 128, 128, h2, 128, w[3], 128, h3, 128, epi(b[3], 1), 1, s);
     }
-    if (g_chain_fused) {
+    if (chain) {
         // the bottleneck has no activation and view layer 0 is averaged over the views before its ReLU (:113-126): both run on the view
         // MEANS - P rows instead of NV P - as in the NeRFPPMLP chain; bm / cm live in the first P rows of the tape's per-view regions
         float* bm = bott;
@@ -807,7 +811,7 @@ void launch_pix_train_forward(const float* const* w, const float* const* b, cons
 // W0's latent columns is formed in texel space); g_x_enc (R, 63) may be null.  scratch: pix_train_scratch_floats(NV, P).
 void launch_pix_train_backward(const float* const* w, const float* x_enc, const float* cond, int NV, long P, const float* tape,
                                float* scratch, const float* g_rgb, const float* g_sigma, float* const* gw, float* const* gb,
-                               float* g_x_enc, float* g_pre, hipStream_t s) {
+                               float* g_x_enc, float* g_pre, hipStream_t s, int chain) {
     const long R = (long)NV * P;
     const int pe = 63, K0 = pe + 512, VC = 128;                     // VC: netwidth_condition (model_pixel.py:44)
     const float* h0 = tape; const float* h1 = h0 + R * 128; const float* h2 = h1 + R * 128; const float* h3 = h2 + R * 128;
@@ -821,7 +825,7 @@ void launch_pix_train_backward(const float* const* w, const float* x_enc, const 
     gemm<false, true>((int)P, VC, 3, g_rgb, 3, w[8], VC, g_y1, VC, epi(nullptr, 0, 0, y1, VC), 1, s);            // x relu'(y1)
     dw_gemm(VC, VC, (int)P, g_y1, VC, ym, VC, gw[5], VC, gb[5], part, s);                                        // view layer 1
     gemm<false, true>((int)P, VC, VC, g_y1, VC, w[5], VC, g_ym, VC, epi(nullptr, 0, 0, ym, VC), 1, s);           // x relu'(mean)
-    if (g_chain_fused) {
+    if (chain) {
         // backward of the view branch on the means (see the forward): P-sized; g_h3[v, p] = g_hm[p] / NV
         const float* bm = bott;
         const float* cm = bott + P * 128;
@@ -870,7 +874,7 @@ void launch_pix_train_backward(const float* const* w, const float* x_enc, const 
 void launch_tp_train_backward(int pe, const float* const* w, const float* x_enc, const float* local, const float* world,
                               const float* cond, int NV, long P, const float* tape, float* scratch, const float* g_rgb,
                               const float* g_sigma, float* const* gw, float* const* gb, float* g_x_enc, float* g_local,
-                              float* g_world, hipStream_t s, float* g_pre) {
+                              float* g_world, hipStream_t s, float* g_pre, int chain) {
     // g_pre != null: the forward ran on `pre` (projected-space path): the local segment has no dW / dX here; instead the two
     // first-layer gradients are returned as g_pre (R, 256) = [g_z0 | g_z3] for the lookup's backward into the projected map
     const long R = (long)NV * P;
@@ -885,7 +889,7 @@ void launch_tp_train_backward(int pe, const float* const* w, const float* x_enc,
     const float* in[3] = {x_enc, local, world};
     float* g_in[3] = {g_x_enc, g_local, g_world};
     const int kin[3] = {pe, 512, 128}, off[3] = {0, pe, pe + 512};
-    const bool fused = g_pre && g_chain_fused && (pe == 63 || pe == 84);
+    const bool fused = g_pre && chain && (pe == 63 || pe == 84);
     if (fused && g_heads_fused) {
         // the input-gradient part of everything P-sized as one kernel: g_y1, g_ym, g_bm, g_hm (train_chain.h)
         HeadsBwdArgs hb{g_rgb, g_sigma, y1, ym, w[4], w[5], w[6], w[7], w[8], g_y1, g_ym, part + DW_PART_FLOATS, g_hm, P};

@@ -196,17 +196,60 @@ def eff_distloss(w, m, interval, ctx=None):
     return _DistLoss.apply(w, m, interval, ctx)
 
 
+class _SharedGradSink(torch.autograd.Function):
+    """Identity between a group of tensors and the lookups that scatter their gradients into ONE set of buffers (shared_grad_group /
+    shared_grad_buffers).  The lookups take the sink's outputs as inputs, so autograd runs this backward once per pass, after every
+    lookup of that pass has scattered - however many of them the loss reached - and here the complete buffers are handed on and the
+    holder is cleared for the next pass.  Whatever else feeds the original tensors (a regulariser, a second call with its own group)
+    is summed by autograd as for any other function: the lookups return no gradient for the group themselves.  `box` holds only the
+    buffers, never the sink's outputs (that would be a reference cycle through this node)."""
+
+    @staticmethod
+    def forward(ctx_, box, *xs):
+        ctx_.box = box
+        ctx_.set_materialize_grads(False)
+        return tuple(x.view_as(x) for x in xs)
+
+    @staticmethod
+    def backward(ctx_, *gs):
+        bufs = ctx_.box.get("bufs")
+        ctx_.box["bufs"] = None
+        return (None,) + (tuple(bufs) if bufs is not None else tuple(gs))
+
+
+def shared_grad_group(shared, xs):
+    """The sink's outputs for the tensors `xs`, made on the first use of the dict `shared` (one sink per dict): the lookups that
+    share `shared` take these as their differentiable inputs.  A dict belongs to one set of tensor objects."""
+    held = shared.get("src")
+    if held is None:
+        shared["src"] = tuple(xs)
+        shared["box"] = {"bufs": None}
+        shared["sunk"] = _SharedGradSink.apply(shared["box"], *xs)
+    elif len(held) != len(xs) or any(a is not b for a, b in zip(held, xs)):
+        raise ValueError("a shared-gradient dict serves one set of tensors; use a new dict for other tensors")
+    return shared["sunk"]
+
+
+def shared_grad_buffers(shared, make):
+    """The gradient buffers a lookup's backward scatters into: this pass's buffers of the group (`make()` for the first lookup of
+    the pass to run).  The group's sink hands them to autograd; the lookup itself returns None for the group's tensors."""
+    box = shared["box"]
+    if box["bufs"] is None:
+        box["bufs"] = make()
+    return box["bufs"]
+
+
 class _Gather(torch.autograd.Function):
     @staticmethod
-    def forward(ctx_, module, pts, plane_xz, plane_xy, plane_yz, latent, rays, planes_only=False, shared=None):
+    def forward(ctx_, module, pts, plane_xz, plane_xy, plane_yz, latent, rays, planes_only=False, shared=None, src=None):
         # the module's context holds channels-last copies of the scene: they must be copies of THESE tensors at THIS
         # version (an optimizer step or a fresh encoder output would otherwise leave the forward values stale while
-        # gradients still flow to the arguments) - re-upload when the fingerprint differs
+        # gradients still flow to the arguments) - re-upload when the fingerprint differs.  src: the caller's tensor objects
+        # when the planes arrive through a shared-gradient sink (its outputs are new views of the same tensors)
         pts = f32(pts, "pts").reshape(-1, 3)
-        maps = (plane_xz, plane_xy, plane_yz, latent)
+        maps = tuple(src) if src is not None else (plane_xz, plane_xy, plane_yz, latent)
         if not module.scene_matches(maps):
-            module.set_scene(plane_xz.detach(), plane_xy.detach(), plane_yz.detach(), latent.detach(),
-                             module.scene_image_wh(rays), _source=maps)
+            module.set_scene(*(m.detach() for m in maps), module.scene_image_wh(rays), _source=maps)
         c = module._context(pts.device)
         host_poses, NV, focal, cx, cy = module._camera_args(rays)
         P = pts.shape[0]
@@ -215,8 +258,6 @@ class _Gather(torch.autograd.Function):
         _lib.check(c.lib.neo_tp_gather(c.handle, ptr(pts), P, host_poses, NV, focal, cx, cy, ptr(world), ptr(local), c.stream()))
         ctx_.save_for_backward(pts)
         ctx_.meta = (c, host_poses, NV, focal, cx, cy, plane_xz.shape, latent.shape, bool(planes_only), shared)
-        if shared is not None:
-            shared["uses"] = shared.get("uses", 0) + 1
         if planes_only:
             return world, torch.empty(0, device=pts.device)
         return world, local
@@ -228,30 +269,23 @@ class _Gather(torch.autograd.Function):
         dev = pts.device
         _, Cw, Hp, Wp = pshape
         _, Cl, Hf, Wf = lshape
-        # `shared` (round 6): the lookups of one training call scatter into ONE set of channels-last plane-gradient buffers - the first
-        # backward to run allocates them and hands them to autograd, the others add into them and return nothing: one zero fill, one
-        # NHWC -> NCHW conversion and no full-size sums per plane and call instead of one of each per lookup (4 per call)
-        first = True
+        new_planes = lambda: [torch.zeros(NV, Hp, Wp, Cw, device=dev) for _ in range(3)]
+        nchw = lambda x: x.permute(0, 3, 1, 2)
+        # `shared` (gather_planes): the lookups of one training call scatter into ONE set of channels-last plane-gradient buffers -
+        # one zero fill, one NHWC -> NCHW conversion and no full-size sums per plane and call instead of one of each per lookup.  The
+        # call's _SharedGradSink hands them to autograd once every lookup of the pass has scattered (shared_grad_group)
         if shared is not None and planes_only:
-            first = shared.get("planes") is None
-            if first:
-                shared["planes"] = [torch.zeros(NV, Hp, Wp, Cw, device=dev) for _ in range(3)]
-                shared["left"] = shared.get("uses", 1)
-            gp = shared["planes"]
-            shared["left"] -= 1
-            if shared["left"] <= 0:                                      # every lookup of the call has reported: a later pass starts afresh
-                shared["planes"] = None
+            gp = [t.permute(0, 2, 3, 1) for t in shared_grad_buffers(shared, lambda: [nchw(t) for t in new_planes()])]
         else:
-            gp = [torch.zeros(NV, Hp, Wp, Cw, device=dev) for _ in range(3)]
+            gp = new_planes()
         gl = None if planes_only else torch.zeros(NV, Hf, Wf, Cl, device=dev)
         gw = f32(g_world.contiguous(), "g_world")
         gloc = None if planes_only else f32(g_local.contiguous(), "g_local")
         _lib.check(c.lib.neo_tp_gather_backward(c.handle, ptr(pts), pts.shape[0], host_poses, NV, focal, cx, cy, ptr(gw),
                                                 ptr(gloc), ptr(gp[0]), ptr(gp[1]), ptr(gp[2]), ptr(gl), c.stream()))
-        nchw = lambda x: x.permute(0, 3, 1, 2)
-        if not first:
-            return None, None, None, None, None, None, None, None, None
-        return None, None, nchw(gp[0]), nchw(gp[1]), nchw(gp[2]), (nchw(gl) if gl is not None else None), None, None, None
+        if shared is not None and planes_only:
+            return None, None, None, None, None, None, None, None, None, None
+        return None, None, nchw(gp[0]), nchw(gp[1]), nchw(gp[2]), (nchw(gl) if gl is not None else None), None, None, None, None
 
 
 def gather_features(module, pts, plane_xz, plane_xy, plane_yz, latent, rays):
@@ -261,14 +295,20 @@ def gather_features(module, pts, plane_xz, plane_xy, plane_yz, latent, rays):
     recorded by `module.set_scene`), the four maps are uploaded again first (image size from the previous `set_scene` or
     `rays["src_imgs"]`), so forward values and gradients always refer to the same data.  Gradients flow to the four
     feature maps (NCHW, like the inputs)."""
-    return _Gather.apply(module, pts, plane_xz, plane_xy, plane_yz, latent, rays)
+    return _Gather.apply(module, pts, plane_xz, plane_xy, plane_yz, latent, rays, False, None, None)
 
 
 def gather_planes(module, pts, plane_xz, plane_xy, plane_yz, latent, rays, shared=None):
     """The tri-plane half of gather_features alone: world (NV*P,128).  The latent is not looked up (the projected-space
     training path gathers it through `gather_map`); it is still passed so that the device-side scene - geometry included -
-    follows these tensors."""
-    return _Gather.apply(module, pts, plane_xz, plane_xy, plane_yz, latent, rays, True, shared)[0]
+    follows these tensors.  shared: a dict (start with {}) common to several lookups in the SAME three planes - one training
+    call's: their backward passes scatter into one set of gradient buffers, released through a sink node (_SharedGradSink) once
+    per backward pass, so partial losses, retained graphs, other gradient terms on the planes and several dicts in one loss all
+    give the plain sum of the contributions."""
+    if shared is None:
+        return _Gather.apply(module, pts, plane_xz, plane_xy, plane_yz, latent, rays, True, None, None)[0]
+    sxz, sxy, syz = shared_grad_group(shared, (plane_xz, plane_xy, plane_yz))
+    return _Gather.apply(module, pts, sxz, sxy, syz, latent, rays, True, shared, (plane_xz, plane_xy, plane_yz, latent))[0]
 
 
 class _ChannelsLast(torch.autograd.Function):
@@ -429,17 +469,18 @@ class _TrainMLPPre(torch.autograd.Function):
         raw_rgb = torch.empty(npts, 3, device=xe.device)
         raw_sigma = torch.empty(npts, 1, device=xe.device)
         tape = torch.empty(c.lib.neo_tp_mlp_train_tape_floats(nv, npts), device=xe.device)
+        chain = ctypes.c_int(-1)        # the tape layout this forward wrote (neo_train_chain_mode at THIS call), for the backward
         _lib.check(c.lib.neo_tp_mlp_train_forward_pre(c.handle, input_ch, tab(wd), tab(bd), ptr(xe), ptr(pf), ptr(wf), ptr(cond), nv,
-                                                      npts, ptr(tape), ptr(raw_rgb), ptr(raw_sigma), c.stream()))
+                                                      npts, ptr(tape), ptr(raw_rgb), ptr(raw_sigma), ctypes.byref(chain), c.stream()))
         ctx_.save_for_backward(xe, wf, cond, tape, *wd)
-        ctx_.meta = (c, input_ch, nv, npts, x_enc.shape, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs])
+        ctx_.meta = (c, input_ch, nv, npts, x_enc.shape, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs], chain.value)
         return raw_rgb, raw_sigma
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx_, g_rgb, g_sigma):
         xe, wf, cond, tape, *wd = ctx_.saved_tensors
-        c, input_ch, nv, npts, xshape, wshapes, bshapes = ctx_.meta
+        c, input_ch, nv, npts, xshape, wshapes, bshapes, chain = ctx_.meta
         if ctx_.needs_input_grad[4]:
             raise NotImplementedError("nerfpp_mlp: no gradient for cond_rows (the reference's view directions are data)")
         dev = xe.device
@@ -452,7 +493,7 @@ class _TrainMLPPre(torch.autograd.Function):
         tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         _lib.check(c.lib.neo_tp_mlp_train_backward_pre(c.handle, input_ch, tab(wd), ptr(xe), ptr(wf), ptr(cond), nv, npts, ptr(tape),
                                                        ptr(g_rgb), ptr(g_sigma), tab(gw), tab(gb), ptr(gx), ptr(gpre), ptr(gworld),
-                                                       c.stream()))
+                                                       chain, c.stream()))
         return (None, None, None, gx.reshape(xshape) if gx is not None else None, None, gworld, gpre, *gw, *gb)
 
 
@@ -897,17 +938,18 @@ class _PixTrainMLPPre(torch.autograd.Function):
         raw_rgb = torch.empty(npts, 3, device=xe.device)
         raw_sigma = torch.empty(npts, 1, device=xe.device)
         tape = torch.empty(c.lib.neo_pix_mlp_train_tape_floats(nv, npts), device=xe.device)
+        chain = ctypes.c_int(-1)        # the tape layout this forward wrote: handed to the backward (see _TrainMLPPre)
         _lib.check(c.lib.neo_pix_mlp_train_forward_pre(c.handle, tab(wd), tab(bd), ptr(xe), ptr(pf), ptr(cond), nv, npts, ptr(tape),
-                                                       ptr(raw_rgb), ptr(raw_sigma), c.stream()))
+                                                       ptr(raw_rgb), ptr(raw_sigma), ctypes.byref(chain), c.stream()))
         ctx_.save_for_backward(xe, cond, tape, *wd)
-        ctx_.meta = (c, nv, npts, x_enc.shape, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs])
+        ctx_.meta = (c, nv, npts, x_enc.shape, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs], chain.value)
         return raw_rgb, raw_sigma
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx_, g_rgb, g_sigma):
         xe, cond, tape, *wd = ctx_.saved_tensors
-        c, nv, npts, xshape, wshapes, bshapes = ctx_.meta
+        c, nv, npts, xshape, wshapes, bshapes, chain = ctx_.meta
         if ctx_.needs_input_grad[3]:
             raise NotImplementedError("pixel_mlp: no gradient for cond_rows (the reference's view directions are data)")
         dev = xe.device
@@ -919,7 +961,7 @@ class _PixTrainMLPPre(torch.autograd.Function):
         gpre = torch.empty(nv * npts, 128, device=dev)
         tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         _lib.check(c.lib.neo_pix_mlp_train_backward_pre(c.handle, tab(wd), ptr(xe), ptr(cond), nv, npts, ptr(tape), ptr(g_rgb), ptr(g_sigma),
-                                                        tab(gw), tab(gb), ptr(gx), ptr(gpre), c.stream()))
+                                                        tab(gw), tab(gb), ptr(gx), ptr(gpre), chain, c.stream()))
         return (None, None, gx.reshape(xshape) if gx is not None else None, None, gpre, *gw, *gb)
 
 
