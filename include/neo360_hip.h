@@ -268,6 +268,27 @@ int neo_enc_floorplans(neo_ctx* ctx, const float* latent, int NV, int Hf, int Wf
                        const float* src_poses, float focal, float cx, float cy, int G0, int G1, int G2,
                        float* fp_yz, float* fp_xz, float* fp_xy, void* stream);
 
+/* The pillar stage under autograd (GridEncoder trained as the reference trains it, models/neo360/model.py:697-820).
+ * neo_enc_floorplans_train: neo_enc_floorplans with the activations the backward needs written to `tape`, a CALLER-owned
+ * device buffer of neo_enc_train_tape_floats(NV, G0, G1, G2) floats = h1, h2, L (M x 512 each, M = NV G0 G1 G2 cell-views)
+ * and the three score vectors (xz, yz, xy); same kernels, same split-fp16 arithmetic, same range guard and flags: the
+ * floor-plans are bitwise those of neo_enc_floorplans.  At most 8,388,480 cell-views per call.
+ * neo_enc_floorplans_backward: exact fp32 MFMA.  w / b: the nine layers as fp32 device tensors in neo_enc_upload's order;
+ * latent / geometry: the forward's arguments; tape: the forward's, only read (a second backward of the same tape gives the
+ * same gradients); g_yz / g_xz / g_xy: gradients of the floor-plans, channels-last like the outputs; gw / gb [host arrays of
+ * 9 device pointers]: accumulated into (zeroed by the caller; the parameter gradients are reduced in a fixed order and
+ * repeat bitwise); g_latent (NV,512,Hf,Wf) NCHW: accumulated (atomically: repeats to rounding), may be NULL.  No gradient
+ * reaches src_poses, focal or the principal point.  The first layer's input is re-gathered from the latent, not taped; the
+ * scratch (about 3 M x 512 floats + the channels-last latent gradient) is context-owned. */
+long neo_enc_train_tape_floats(int NV, int G0, int G1, int G2);
+int neo_enc_floorplans_train(neo_ctx* ctx, const float* latent, int NV, int Hf, int Wf, float image_w, float image_h,
+                             const float* src_poses, float focal, float cx, float cy, int G0, int G1, int G2, float* tape,
+                             float* fp_yz, float* fp_xz, float* fp_xy, void* stream);
+int neo_enc_floorplans_backward(neo_ctx* ctx, const float* const* w, const float* const* b, const float* latent, int NV, int Hf,
+                                int Wf, float image_w, float image_h, const float* src_poses, float focal, float cx, float cy,
+                                int G0, int G1, int G2, const float* tape, const float* g_yz, const float* g_xz, const float* g_xy,
+                                float* const* gw, float* const* gb, float* g_latent, void* stream);
+
 /* ---- training-side operators ----------------------------------------------------------- */
 /* Counter-based uniforms in [0,1): out[r][c] = (Philox4x32-10(key = seed, counter = (r, c, stream_id, 0))[0] >> 8) 2^-24
  * - the generator behind every randomized=True sampler here (the reference draws torch.rand: helper.py:49, :196). */

@@ -11,6 +11,13 @@ focal, c)` -> (scene_grid_xz, scene_grid_xy, scene_grid_yz), same state_dict key
   floorplan_convnet_*    the reference's 2-D conv stacks on 64 x 64 floor-plans: PyTorch (MIOpen), once per scene
 
 Attach it to `models.NeRF_TP(encoder=GridEncoder(spatial_encoder=...))`: the module runs it once per distinct src_imgs.
+
+Training: with autograd on and a pillar parameter or the latent requiring grad, `forward` runs the pillar stage as a
+`torch.autograd.Function` (`_PillarStage`): the same split-fp16 forward kernels (bitwise the floor-plans of `floorplans`)
+writing their activations to a tape, and a native backward on exact fp32 MFMA (csrc/pillar_train.hip) that returns the
+gradients of all nine depth_fc / pillar_aggregator layers (weights and biases) and of the latent.  `differentiable`
+(None = automatic, True / False = always / never) overrides the choice, as on the renderers.  No gradient reaches the poses,
+focal length or principal point (the reference's cameras are data).
 """
 import ctypes
 
@@ -120,11 +127,95 @@ class GridEncoder(_HipModule):
             self._raise_flags(ctx.poll_flags())
         return yz, xz, xy
 
+    def _pillar_params(self):
+        """The pillar stage's parameters in the library's order: the nine weights, then the nine biases."""
+        layers = self.ordered_layers()
+        return [l.weight for l in layers] + [l.bias for l in layers]
+
+    def _pillar_grad(self, latent):
+        """Whether `forward` takes the differentiable pillar stage (`differentiable` overrides the automatic rule)."""
+        if self.differentiable is not None:
+            return bool(self.differentiable)
+        return torch.is_grad_enabled() and (latent.requires_grad or any(p.requires_grad for p in self._pillar_params()))
+
+    def floorplans_train(self, latent, poses, focal, c, image_wh):
+        """`floorplans` under autograd: same arguments, same (bitwise) floor-plans, differentiable with respect to the latent
+        and the nine depth_fc / pillar_aggregator layers.  Keeps a tape of 3 x 512 + 3 floats per cell-view (4.7 GB at 64^3 x 3
+        views) until the backward."""
+        return _PillarStage.apply(self, (poses, focal, c, image_wh), latent, *self._pillar_params())
+
     def forward(self, images, poses, focal, c):
         """GridEncoder.forward (encoder_tp_fusion_conv.py:472-597): images (NV,3,H,W) -> three (NV,128,120,160) planes
         in the reference's return order (xz, xy, yz).  Leaves the pixel-aligned latent in `spatial_encoder.latent`."""
         NV, _, H, W = images.shape
         self.spatial_encoder(images)
-        yz, xz, xy = self.floorplans(self.spatial_encoder.latent, poses, focal, c, (W, H))
+        latent = self.spatial_encoder.latent
+        if self._pillar_grad(latent):
+            yz, xz, xy = self.floorplans_train(latent, poses, focal, c, (W, H))
+        else:
+            yz, xz, xy = self.floorplans(latent, poses, focal, c, (W, H))
         nchw = lambda t: t.permute(0, 3, 1, 2)
         return self.floorplan_convnet_xz(nchw(xz)), self.floorplan_convnet_xy(nchw(xy)), self.floorplan_convnet_yz(nchw(yz))
+
+
+def _camera_args(poses, focal, c):
+    nv = poses.shape[0]
+    host = poses.detach().float().cpu().contiguous()
+    host_poses = (ctypes.c_float * (16 * nv))(*host.reshape(-1).tolist())
+    cx, cy = (float(x) for x in c[0])
+    return host_poses, float(focal[0]), cx, cy
+
+
+class _PillarStage(torch.autograd.Function):
+    """The pillar stage under autograd.  Inputs: the encoder, the camera tuple (poses, focal, c, image_wh: no gradient), the
+    latent (NV,512,Hf,Wf) and the 18 tensors of `GridEncoder._pillar_params`; outputs the channels-last floor-plans
+    (yz, xz, xy).  The tape (h1, h2, L, scores) lives in the autograd context; the backward only reads it, so a retained
+    graph differentiates again to the same gradients."""
+
+    @staticmethod
+    def forward(ctx_, enc, cams, latent, *params):
+        poses, focal, c, image_wh = cams
+        latent32 = f32(latent.detach(), "latent")
+        dev = latent32.device
+        ctx = enc._context(dev)
+        enc._sync_weights(ctx)
+        NV, C, Hf, Wf = latent32.shape
+        if C != enc.LATENT:
+            raise _lib.NeoError("the pillar stage is specialised for the reference's 512-channel latent")
+        G0, G1, G2 = enc.grid_size
+        host_poses, f0, cx, cy = _camera_args(poses, focal, c)
+        tape = torch.empty(int(ctx.lib.neo_enc_train_tape_floats(NV, G0, G1, G2)), device=dev)
+        yz = torch.empty(NV, G1, G2, 512, device=dev)
+        xz = torch.empty(NV, G0, G2, 512, device=dev)
+        xy = torch.empty(NV, G0, G1, 512, device=dev)
+        geo = (NV, Hf, Wf, float(image_wh[0]), float(image_wh[1]))
+        _lib.check(ctx.lib.neo_enc_floorplans_train(ctx.handle, ptr(latent32), *geo, host_poses, f0, cx, cy, G0, G1, G2,
+                                                    ptr(tape), ptr(yz), ptr(xz), ptr(xy), ctx.stream()))
+        if enc.poll_flags:
+            enc._raise_flags(ctx.poll_flags())
+        ctx_.enc, ctx_.tape = enc, tape
+        ctx_.args = (geo, host_poses, f0, cx, cy, (G0, G1, G2))
+        ctx_.save_for_backward(latent, *params)
+        return yz, xz, xy
+
+    @staticmethod
+    def backward(ctx_, g_yz, g_xz, g_xy):
+        latent, *params = ctx_.saved_tensors
+        geo, host_poses, f0, cx, cy, (G0, G1, G2) = ctx_.args
+        latent = f32(latent.detach(), "latent")
+        dev = latent.device
+        ctx = ctx_.enc._context(dev)
+        NV = geo[0]
+        grads = []
+        for g, shape in ((g_yz, (NV, G1, G2, 512)), (g_xz, (NV, G0, G2, 512)), (g_xy, (NV, G0, G1, 512))):
+            grads.append(torch.zeros(shape, device=dev) if g is None else f32(g, "floor-plan gradient"))
+        ws = [f32(p.detach(), "weight") for p in params[:9]]
+        bs = [f32(p.detach(), "bias") for p in params[9:]]
+        gw = [torch.zeros_like(w) for w in ws]
+        gb = [torch.zeros_like(b) for b in bs]
+        g_lat = torch.zeros_like(latent) if ctx_.needs_input_grad[2] else None
+        _lib.check(ctx.lib.neo_enc_floorplans_backward(ctx.handle, _ptr_table(ws), _ptr_table(bs), ptr(latent), *geo, host_poses,
+                                                       f0, cx, cy, G0, G1, G2, ptr(ctx_.tape), ptr(grads[0]), ptr(grads[1]),
+                                                       ptr(grads[2]), _ptr_table(gw), _ptr_table(gb), ptr(g_lat), ctx.stream()))
+        out = [g if need else None for g, need in zip(gw + gb, ctx_.needs_input_grad[3:])]
+        return (None, None, g_lat, *out)
