@@ -7,8 +7,9 @@ There is no CPU or eager-PyTorch fallback: calls fail loudly if the library is
 missing or the tensors are not on a ROCm device.
 
 The differentiable training calls (`training.py`) are chains of the library's operators - samplers, encodings, lookups,
-MLP / linear-layer GEMMs and compositing, each with a native backward - held together by torch autograd.  NeRF_TP and NeRF run
-their MLPs as fused native chains; PixelNeRF and MipNeRF360 compose theirs per layer (`training.linear`) with torch elementwise
-ops (ReLU masks, view means, activations) between the GEMMs, and the texel-space projection of the latent uses a library GEMM.
+MLP / linear-layer GEMMs and compositing, each with a native backward - held together by torch autograd.  All four renderers run
+their MLPs as one fused native chain each way (`nerfpp_mlp*`, `nerf_mlp`, `pixel_mlp_fused`, `mip_mlp_fused`); the per-layer
+composition on `training.linear` remains as `module.train_fused = False` and for Mip-NeRF 360 shapes outside the chain's range.
+The texel-space projections of the latent run on the library's own GEMM kernels (`neo_linear_*`), not on a BLAS library.
 """
 __version__ = "0.1.0"

@@ -9,21 +9,6 @@ namespace {
 // 158,976; per point density 128 + 128*128 + rgb 384 = 16,896
 double pix_flop_per_point(int nv) { return 2.0 * (nv * 158976.0 + 16896.0); }
 
-// rot = c2w[:3,:3]^T ; trans = -rot @ c2w[:3,3]   (vanilla_nerf/util.py:20-34), fp32
-void fill_views(const float* poses, int nv, neo::TpViews& v) {
-    for (int i = 0; i < nv; ++i) {
-        const float* m = poses + i * 16;
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) v.rot[i][r * 3 + c] = m[c * 4 + r];
-        for (int r = 0; r < 3; ++r) {
-            float acc = v.rot[i][r * 3 + 0] * m[0 * 4 + 3];
-            acc = acc + v.rot[i][r * 3 + 1] * m[1 * 4 + 3];
-            acc = acc + v.rot[i][r * 3 + 2] * m[2 * 4 + 3];
-            v.trans[i][r] = -acc;
-        }
-    }
-}
-
 int pix_launch(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
                const float* rays_d, const float* viewdirs, const float* tvals, int t_shared, int R, int N, int chunk,
                float* out, hipStream_t s) {
@@ -142,10 +127,7 @@ int neo_pix_mlp(neo_ctx* ctx, int slot, const float* rays_o, const float* rays_d
     if (!ctx->pix_scene_ready) return fail(NEO_ERR_STATE, "scene latent not set (neo_pix_set_scene)");
     REQUIRE(NV == ctx->pix_scene.nv, "NV differs from the uploaded scene");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->pix_scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
+    auto [sc, views] = call_scene(ctx->pix_scene, src_poses, NV, focal, cx, cy);
     const int rc = pix_launch(ctx, slot, sc, views, rays_o, rays_d, viewdirs, tvals, 0, R, N, chunk, out, s);
     if (rc) return rc;
     return check_launch();
@@ -163,10 +145,7 @@ int neo_pix_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const
     if (!ctx->pix_scene_ready) return fail(NEO_ERR_STATE, "scene latent not set (neo_pix_set_scene)");
     REQUIRE(NV == ctx->pix_scene.nv, "NV differs from the uploaded scene");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->pix_scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
+    auto [sc, views] = call_scene(ctx->pix_scene, src_poses, NV, focal, cx, cy);
     const int N0 = n_coarse + 1, N1 = N0 + n_fine;
     const float* t0 = ctx->get_edges(n_coarse, near, far, s);
     const float* u = ctx->get_quantiles(n_fine, s);

@@ -13,21 +13,6 @@ double tp_flop_per_point(int input_ch, int nv) {
     return 2.0 * (nv * per_view + 4416.0);
 }
 
-// rot = c2w[:3,:3]^T ; trans = -rot @ c2w[:3,3]   (neo360/util.py:64-66), fp32
-void fill_views(const float* poses, int nv, neo::TpViews& v) {
-    for (int i = 0; i < nv; ++i) {
-        const float* m = poses + i * 16;
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) v.rot[i][r * 3 + c] = m[c * 4 + r];
-        for (int r = 0; r < 3; ++r) {
-            float acc = v.rot[i][r * 3 + 0] * m[0 * 4 + 3];
-            acc = acc + v.rot[i][r * 3 + 1] * m[1 * 4 + 3];
-            acc = acc + v.rot[i][r * 3 + 2] * m[2 * 4 + 3];
-            v.trans[i][r] = -acc;
-        }
-    }
-}
-
 // The maps a slot gathers in pre-projection modes, recomputed (exact fp32 MFMA, k_tp_preproject: ~1 ms per map) only when the
 // scene or the slot's weights changed since they were made: the latent through [W0_loc | W3_loc], and - planes = true - the three
 // tri-planes through [W0_world | W3_world] (chunks 64..79 of the fp32 fragment stream).  Shared by both arithmetic modes.
@@ -259,10 +244,7 @@ int neo_tp_mlp(neo_ctx* ctx, int slot, const float* rays_o, const float* rays_d,
     REQUIRE(sl.input_ch == (slot < 2 ? 3 : 4), "slots 0,1 must hold fg weights, 2,3 bg weights");
     REQUIRE(slot < 2 || far, "far required for the outside-sphere slots");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
+    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
     if (int rc = tp_launch(ctx, sl, sc, views, rays_o, rays_d, viewdirs, tvals, far, R, N, chunk, out, s)) return rc;
     return check_launch();
 }
@@ -283,10 +265,7 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const 
             "slots 0,1 must be fg (input_ch 3), slots 2,3 bg (input_ch 4)");
     (void)white_bkgd;  // out_depth=True semantics: the reference composites with white_bkgd=False (model.py:477-501)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
+    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
     sc.grid_w = ctx->ray_grid_w;              // pixel-grid hint of the frame API: the evaluators walk the rays in 8 x 8 patches
     sc.grid_first = ctx->ray_grid_first;
 

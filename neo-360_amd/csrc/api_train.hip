@@ -8,18 +8,65 @@ using namespace neo_host;
 
 namespace {
 
-void fill_views(const float* poses, int nv, neo::TpViews& v) {       // as api_tp.hip (neo360/util.py:64-66)
-    for (int i = 0; i < nv; ++i) {
-        const float* m = poses + i * 16;
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) v.rot[i][r * 3 + c] = m[c * 4 + r];
-        for (int r = 0; r < 3; ++r) {
-            float acc = v.rot[i][r * 3 + 0] * m[0 * 4 + 3];
-            acc = acc + v.rot[i][r * 3 + 1] * m[1 * 4 + 3];
-            acc = acc + v.rot[i][r * 3 + 2] * m[2 * 4 + 3];
-            v.trans[i][r] = -acc;
-        }
+// The bilinear lookup in a caller-owned channels-last map and its scatter backward, behind the six neo_*_gather_map* entry points.
+// pix: the geometry of neo_pix_set_scene instead of neo_tp_set_scene.  slice: `map` / `g_map` point at a C-column slice of rows
+// `pitch` floats apart (the forward reads it in 16-byte pieces, hence its alignment rules); dense maps pass pitch 0.
+int map_gather_checks(neo_ctx* ctx, bool pix, bool ptrs, bool aligned, long texels, int NV) {
+    REQUIRE(ptrs, "null pointer");
+    REQUIRE(aligned, "the slice must start at a 16-byte boundary");
+    if (!(pix ? ctx->pix_scene_ready : ctx->scene_ready))
+        return fail(NEO_ERR_STATE, pix ? "scene geometry not set (neo_pix_set_scene)" : "scene geometry not set (neo_tp_set_scene)");
+    const neo::TpScene& scene = pix ? ctx->pix_scene : ctx->scene;
+    REQUIRE(NV == scene.nv, "NV differs from the uploaded scene");
+    REQUIRE(texels == static_cast<long>(scene.nv) * scene.Hf * scene.Wf,
+            "map rows differ from NV*Hf*Wf of the uploaded scene geometry (stale scene, or a map of another resolution)");
+    return NEO_OK;
+}
+
+bool map_width_ok(int C) { return C >= 64 && C <= 1024 && C % 64 == 0; }
+
+int map_gather(neo_ctx* ctx, bool pix, bool slice, const float* map, long texels, long pitch, int C, const float* pts, long P,
+               const float* src_poses, int NV, float focal, float cx, float cy, float* out, void* stream) {
+    ENTER(ctx);
+    if (slice) REQUIRE(P >= 0 && map_width_ok(C) && pitch >= C && pitch % 4 == 0, "bad shape (C a multiple of 64, <= 1024; pitch >= C, a multiple of 4)");
+    else REQUIRE(P >= 0 && map_width_ok(C), "bad shape (C a multiple of 64, <= 1024)");
+    if (P == 0) return NEO_OK;
+    if (int rc = map_gather_checks(ctx, pix, map && pts && src_poses && out, !slice || (reinterpret_cast<uintptr_t>(map) & 15) == 0, texels, NV))
+        return rc;
+    auto [sc, views] = call_scene(pix ? ctx->pix_scene : ctx->scene, src_poses, NV, focal, cx, cy);
+    neo::launch_map_gather(sc, views, pts, P, map, C, out, static_cast<hipStream_t>(stream), pitch);
+    return check_launch();
+}
+
+int map_gather_backward(neo_ctx* ctx, bool pix, bool slice, long texels, long pitch, int C, const float* pts, long P,
+                        const float* src_poses, int NV, float focal, float cx, float cy, const float* g_out, float* g_map, void* stream) {
+    ENTER(ctx);
+    if (slice) REQUIRE(P >= 0 && map_width_ok(C) && pitch >= C, "bad shape (C a multiple of 64, <= 1024; pitch >= C)");
+    else REQUIRE(P >= 0 && map_width_ok(C), "bad shape (C a multiple of 64, <= 1024)");
+    if (P == 0) return NEO_OK;
+    if (int rc = map_gather_checks(ctx, pix, pts && src_poses && g_out && g_map, true, texels, NV)) return rc;
+    auto [sc, views] = call_scene(pix ? ctx->pix_scene : ctx->scene, src_poses, NV, focal, cx, cy);
+    neo::launch_map_gather_bwd(sc, views, pts, P, g_out, C, g_map, static_cast<hipStream_t>(stream), pitch);
+    return check_launch();
+}
+
+// Argument checks of the fused training chains that take (NV, P) rows and nine layers - NeRFPPMLP and the PixelNeRF MLP, forward and
+// backward - in the order each entry point has always made them: a forward judges input_ch first, a backward only after the P == 0
+// early-out, which the caller takes as soon as this returns NEO_OK.  input_ch_ok: true for the PixelNeRF chain, which has no such
+// argument.  ptrs: the call's own tensor and table pointers.  t1 / t2: the bias table (forward) or the two gradient tables (backward).
+int chain_train_checks(bool forward, bool input_ch_ok, int NV, long P, bool ptrs, const float* const* w, const float* const* t1,
+                       const float* const* t2) {
+    if (forward) REQUIRE(input_ch_ok, "input_ch must be 3 (inside the sphere) or 4 (outside)");
+    REQUIRE(NV >= 1 && P >= 0, "bad shape");
+    if (P == 0) return NEO_OK;
+    if (!forward) REQUIRE(input_ch_ok, "input_ch must be 3 (inside the sphere) or 4 (outside)");
+    REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
+    REQUIRE(ptrs, "null pointer");
+    for (int i = 0; i < 9; ++i) {
+        if (forward) REQUIRE(w[i] && t1[i], "null weight / bias pointer");
+        else REQUIRE(w[i] && t1[i] && t2[i], "null weight / gradient pointer");
     }
+    return NEO_OK;
 }
 
 }  // namespace
@@ -148,10 +195,7 @@ int neo_tp_gather(neo_ctx* ctx, const float* pts, long P, const float* src_poses
     REQUIRE(pts && src_poses && world, "null pointer");            // local may be NULL: tri-planes only
     if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
     REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
+    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
     neo::launch_gather(sc, views, pts, P, world, local, static_cast<hipStream_t>(stream));
     return check_launch();
 }
@@ -167,10 +211,7 @@ int neo_tp_gather_backward(neo_ctx* ctx, const float* pts, long P, const float* 
     REQUIRE((g_local == nullptr) == (g_latent == nullptr), "g_local and g_latent go together (both NULL: tri-planes only)");
     if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
     REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
+    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
     neo::launch_gather_bwd(sc, views, pts, P, g_world, g_local, g_plane_xz, g_plane_xy, g_plane_yz, g_latent,
                            static_cast<hipStream_t>(stream));
     return check_launch();
@@ -178,114 +219,35 @@ int neo_tp_gather_backward(neo_ctx* ctx, const float* pts, long P, const float* 
 
 int neo_tp_gather_map(neo_ctx* ctx, const float* map, long texels, int C, const float* pts, long P, const float* src_poses, int NV, float focal,
                       float cx, float cy, float* out, void* stream) {
-    ENTER(ctx);
-    REQUIRE(P >= 0 && C >= 64 && C <= 1024 && C % 64 == 0, "bad shape (C a multiple of 64, <= 1024)");
-    if (P == 0) return NEO_OK;
-    REQUIRE(map && pts && src_poses && out, "null pointer");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene geometry not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    REQUIRE(texels == static_cast<long>(ctx->scene.nv) * ctx->scene.Hf * ctx->scene.Wf,
-            "map rows differ from NV*Hf*Wf of the uploaded scene geometry (stale scene, or a map of another resolution)");
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
-    neo::launch_map_gather(sc, views, pts, P, map, C, out, static_cast<hipStream_t>(stream));
-    return check_launch();
+    return map_gather(ctx, false, false, map, texels, 0, C, pts, P, src_poses, NV, focal, cx, cy, out, stream);
 }
 
 int neo_tp_gather_map_backward(neo_ctx* ctx, long texels, int C, const float* pts, long P, const float* src_poses, int NV, float focal, float cx,
                                float cy, const float* g_out, float* g_map, void* stream) {
-    ENTER(ctx);
-    REQUIRE(P >= 0 && C >= 64 && C <= 1024 && C % 64 == 0, "bad shape (C a multiple of 64, <= 1024)");
-    if (P == 0) return NEO_OK;
-    REQUIRE(pts && src_poses && g_out && g_map, "null pointer");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene geometry not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    REQUIRE(texels == static_cast<long>(ctx->scene.nv) * ctx->scene.Hf * ctx->scene.Wf,
-            "map rows differ from NV*Hf*Wf of the uploaded scene geometry (stale scene, or a map of another resolution)");
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
-    neo::launch_map_gather_bwd(sc, views, pts, P, g_out, C, g_map, static_cast<hipStream_t>(stream));
-    return check_launch();
+    return map_gather_backward(ctx, false, false, texels, 0, C, pts, P, src_poses, NV, focal, cx, cy, g_out, g_map, stream);
 }
 
 // a C-column slice of a wider map (row pitch `pitch` floats; `map` / `g_map` point at the slice's first column): one merged texel-space
 // projection serves the four MLPs of NeRF_TP (round 6)
 int neo_tp_gather_map_slice(neo_ctx* ctx, const float* map, long texels, long pitch, int C, const float* pts, long P, const float* src_poses,
                             int NV, float focal, float cx, float cy, float* out, void* stream) {
-    ENTER(ctx);
-    REQUIRE(P >= 0 && C >= 64 && C <= 1024 && C % 64 == 0 && pitch >= C && pitch % 4 == 0, "bad shape (C a multiple of 64, <= 1024; pitch >= C, a multiple of 4)");
-    if (P == 0) return NEO_OK;
-    REQUIRE(map && pts && src_poses && out, "null pointer");
-    REQUIRE((reinterpret_cast<uintptr_t>(map) & 15) == 0, "the slice must start at a 16-byte boundary");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene geometry not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    REQUIRE(texels == static_cast<long>(ctx->scene.nv) * ctx->scene.Hf * ctx->scene.Wf,
-            "map rows differ from NV*Hf*Wf of the uploaded scene geometry (stale scene, or a map of another resolution)");
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
-    neo::launch_map_gather(sc, views, pts, P, map, C, out, static_cast<hipStream_t>(stream), pitch);
-    return check_launch();
+    return map_gather(ctx, false, true, map, texels, pitch, C, pts, P, src_poses, NV, focal, cx, cy, out, stream);
 }
 
 int neo_tp_gather_map_slice_backward(neo_ctx* ctx, long texels, long pitch, int C, const float* pts, long P, const float* src_poses, int NV,
                                      float focal, float cx, float cy, const float* g_out, float* g_map, void* stream) {
-    ENTER(ctx);
-    REQUIRE(P >= 0 && C >= 64 && C <= 1024 && C % 64 == 0 && pitch >= C, "bad shape (C a multiple of 64, <= 1024; pitch >= C)");
-    if (P == 0) return NEO_OK;
-    REQUIRE(pts && src_poses && g_out && g_map, "null pointer");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene geometry not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    REQUIRE(texels == static_cast<long>(ctx->scene.nv) * ctx->scene.Hf * ctx->scene.Wf,
-            "map rows differ from NV*Hf*Wf of the uploaded scene geometry (stale scene, or a map of another resolution)");
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
-    neo::launch_map_gather_bwd(sc, views, pts, P, g_out, C, g_map, static_cast<hipStream_t>(stream), pitch);
-    return check_launch();
+    return map_gather_backward(ctx, false, true, texels, pitch, C, pts, P, src_poses, NV, focal, cx, cy, g_out, g_map, stream);
 }
 
 // the same lookup at the PixelNeRF decoder's taps (geometry of neo_pix_set_scene: (f, f) projection, model_pixel.py:198-206)
 int neo_pix_gather_map(neo_ctx* ctx, const float* map, long texels, int C, const float* pts, long P, const float* src_poses, int NV, float focal,
                       float cx, float cy, float* out, void* stream) {
-    ENTER(ctx);
-    REQUIRE(P >= 0 && C >= 64 && C <= 1024 && C % 64 == 0, "bad shape (C a multiple of 64, <= 1024)");
-    if (P == 0) return NEO_OK;
-    REQUIRE(map && pts && src_poses && out, "null pointer");
-    if (!ctx->pix_scene_ready) return fail(NEO_ERR_STATE, "scene geometry not set (neo_pix_set_scene)");
-    REQUIRE(NV == ctx->pix_scene.nv, "NV differs from the uploaded scene");
-    REQUIRE(texels == static_cast<long>(ctx->pix_scene.nv) * ctx->pix_scene.Hf * ctx->pix_scene.Wf,
-            "map rows differ from NV*Hf*Wf of the uploaded scene geometry (stale scene, or a map of another resolution)");
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->pix_scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
-    neo::launch_map_gather(sc, views, pts, P, map, C, out, static_cast<hipStream_t>(stream));
-    return check_launch();
+    return map_gather(ctx, true, false, map, texels, 0, C, pts, P, src_poses, NV, focal, cx, cy, out, stream);
 }
 
 int neo_pix_gather_map_backward(neo_ctx* ctx, long texels, int C, const float* pts, long P, const float* src_poses, int NV, float focal, float cx,
                                float cy, const float* g_out, float* g_map, void* stream) {
-    ENTER(ctx);
-    REQUIRE(P >= 0 && C >= 64 && C <= 1024 && C % 64 == 0, "bad shape (C a multiple of 64, <= 1024)");
-    if (P == 0) return NEO_OK;
-    REQUIRE(pts && src_poses && g_out && g_map, "null pointer");
-    if (!ctx->pix_scene_ready) return fail(NEO_ERR_STATE, "scene geometry not set (neo_pix_set_scene)");
-    REQUIRE(NV == ctx->pix_scene.nv, "NV differs from the uploaded scene");
-    REQUIRE(texels == static_cast<long>(ctx->pix_scene.nv) * ctx->pix_scene.Hf * ctx->pix_scene.Wf,
-            "map rows differ from NV*Hf*Wf of the uploaded scene geometry (stale scene, or a map of another resolution)");
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->pix_scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
-    neo::launch_map_gather_bwd(sc, views, pts, P, g_out, C, g_map, static_cast<hipStream_t>(stream));
-    return check_launch();
+    return map_gather_backward(ctx, true, false, texels, 0, C, pts, P, src_poses, NV, focal, cx, cy, g_out, g_map, stream);
 }
 
 int neo_tp_render_train(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
@@ -300,10 +262,7 @@ int neo_tp_render_train(neo_ctx* ctx, const float* rays_o, const float* rays_d, 
     if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
     REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    neo::TpViews views{};
-    fill_views(src_poses, NV, views);
-    neo::TpScene sc = ctx->scene;
-    sc.focal = focal; sc.cx = cx; sc.cy = cy;
+    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
     const int N0 = n_coarse + 1, N1 = N0 + n_fine;
     const float* edges = ctx->get_edges(n_coarse, 0.0f, 1.0f, s);
     const float* u_det = ctx->get_quantiles(n_fine, s);
@@ -384,12 +343,10 @@ int neo_tp_mlp_train_forward(neo_ctx* ctx, int input_ch, const float* const* w, 
                              const float* local_feat, const float* world_feat, const float* cond, int NV, long P, float* tape,
                              float* raw_rgb, float* raw_sigma, void* stream) {
     ENTER(ctx);
-    REQUIRE(input_ch == 3 || input_ch == 4, "input_ch must be 3 (inside the sphere) or 4 (outside)");
-    REQUIRE(NV >= 1 && P >= 0, "bad shape");
+    if (int rc = chain_train_checks(true, input_ch == 3 || input_ch == 4, NV, P,
+                                    w && b && x_enc && local_feat && world_feat && cond && tape && raw_rgb && raw_sigma, w, b, nullptr))
+        return rc;
     if (P == 0) return NEO_OK;
-    REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
-    REQUIRE(w && b && x_enc && local_feat && world_feat && cond && tape && raw_rgb && raw_sigma, "null pointer");
-    for (int i = 0; i < 9; ++i) REQUIRE(w[i] && b[i], "null weight / bias pointer");
     neo::launch_tp_train_forward(input_ch * 21, w, b, x_enc, local_feat, world_feat, cond, NV, P, tape, raw_rgb, raw_sigma,
                                  static_cast<hipStream_t>(stream));
     return check_launch();
@@ -400,12 +357,10 @@ int neo_tp_mlp_train_backward(neo_ctx* ctx, int input_ch, const float* const* w,
                               const float* g_rgb, const float* g_sigma, float* const* gw, float* const* gb, float* g_x_enc,
                               float* g_local, float* g_world, void* stream) {
     ENTER(ctx);
-    REQUIRE(NV >= 1 && P >= 0, "bad shape");
+    if (int rc = chain_train_checks(false, input_ch == 3 || input_ch == 4, NV, P,
+                                    w && x_enc && local_feat && world_feat && cond && tape && g_rgb && g_sigma && gw && gb, w, gw, gb))
+        return rc;
     if (P == 0) return NEO_OK;
-    REQUIRE(input_ch == 3 || input_ch == 4, "input_ch must be 3 (inside the sphere) or 4 (outside)");
-    REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
-    REQUIRE(w && x_enc && local_feat && world_feat && cond && tape && g_rgb && g_sigma && gw && gb, "null pointer");
-    for (int i = 0; i < 9; ++i) REQUIRE(w[i] && gw[i] && gb[i], "null weight / gradient pointer");
     ORDERED(ctx, static_cast<hipStream_t>(stream));
     if (ctx->train_scratch.reserve(neo::tp_train_scratch_floats(NV, P) * sizeof(float))) return NEO_ERR_NOMEM;
     neo::launch_tp_train_backward(input_ch * 21, w, x_enc, local_feat, world_feat, cond, NV, P, tape,
@@ -421,12 +376,10 @@ int neo_tp_mlp_train_forward_pre(neo_ctx* ctx, int input_ch, const float* const*
     ENTER(ctx);
     const int chain = neo::train_chain_mode(-1);          // read ONCE: the tape layout this forward writes (returned for the backward)
     if (chain_mode) *chain_mode = chain;
-    REQUIRE(input_ch == 3 || input_ch == 4, "input_ch must be 3 (inside the sphere) or 4 (outside)");
-    REQUIRE(NV >= 1 && P >= 0, "bad shape");
+    if (int rc = chain_train_checks(true, input_ch == 3 || input_ch == 4, NV, P,
+                                    w && b && x_enc && pre && world_feat && cond && tape && raw_rgb && raw_sigma, w, b, nullptr))
+        return rc;
     if (P == 0) return NEO_OK;
-    REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
-    REQUIRE(w && b && x_enc && pre && world_feat && cond && tape && raw_rgb && raw_sigma, "null pointer");
-    for (int i = 0; i < 9; ++i) REQUIRE(w[i] && b[i], "null weight / bias pointer");
     neo::launch_tp_train_forward(input_ch * 21, w, b, x_enc, nullptr, world_feat, cond, NV, P, tape, raw_rgb, raw_sigma,
                                  static_cast<hipStream_t>(stream), pre, chain);
     return check_launch();
@@ -438,12 +391,10 @@ int neo_tp_mlp_train_backward_pre(neo_ctx* ctx, int input_ch, const float* const
                                   void* stream) {
     ENTER(ctx);
     REQUIRE(chain_mode == 0 || chain_mode == 1, "chain_mode must be the 0 / 1 the forward returned");
-    REQUIRE(NV >= 1 && P >= 0, "bad shape");
+    if (int rc = chain_train_checks(false, input_ch == 3 || input_ch == 4, NV, P,
+                                    w && x_enc && world_feat && cond && tape && g_rgb && g_sigma && gw && gb && g_pre, w, gw, gb))
+        return rc;
     if (P == 0) return NEO_OK;
-    REQUIRE(input_ch == 3 || input_ch == 4, "input_ch must be 3 (inside the sphere) or 4 (outside)");
-    REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
-    REQUIRE(w && x_enc && world_feat && cond && tape && g_rgb && g_sigma && gw && gb && g_pre, "null pointer");
-    for (int i = 0; i < 9; ++i) REQUIRE(w[i] && gw[i] && gb[i], "null weight / gradient pointer");
     ORDERED(ctx, static_cast<hipStream_t>(stream));
     if (ctx->train_scratch.reserve(neo::tp_train_scratch_floats(NV, P) * sizeof(float))) return NEO_ERR_NOMEM;
     neo::launch_tp_train_backward(input_ch * 21, w, x_enc, nullptr, world_feat, cond, NV, P, tape, ctx->train_scratch.as<float>(),
@@ -461,11 +412,8 @@ int neo_pix_mlp_train_forward_pre(neo_ctx* ctx, const float* const* w, const flo
     ENTER(ctx);
     const int chain = neo::train_chain_mode(-1);          // read ONCE: the tape layout this forward writes (returned for the backward)
     if (chain_mode) *chain_mode = chain;
-    REQUIRE(NV >= 1 && P >= 0, "bad shape");
+    if (int rc = chain_train_checks(true, true, NV, P, w && b && x_enc && pre && cond && tape && raw_rgb && raw_sigma, w, b, nullptr)) return rc;
     if (P == 0) return NEO_OK;
-    REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
-    REQUIRE(w && b && x_enc && pre && cond && tape && raw_rgb && raw_sigma, "null pointer");
-    for (int i = 0; i < 9; ++i) REQUIRE(w[i] && b[i], "null weight / bias pointer");
     neo::launch_pix_train_forward(w, b, x_enc, pre, cond, NV, P, tape, raw_rgb, raw_sigma, static_cast<hipStream_t>(stream), chain);
     return check_launch();
 }
@@ -475,11 +423,8 @@ int neo_pix_mlp_train_backward_pre(neo_ctx* ctx, const float* const* w, const fl
                                    float* g_x_enc, float* g_pre, int chain_mode, void* stream) {
     ENTER(ctx);
     REQUIRE(chain_mode == 0 || chain_mode == 1, "chain_mode must be the 0 / 1 the forward returned");
-    REQUIRE(NV >= 1 && P >= 0, "bad shape");
+    if (int rc = chain_train_checks(false, true, NV, P, w && x_enc && cond && tape && g_rgb && g_sigma && gw && gb && g_pre, w, gw, gb)) return rc;
     if (P == 0) return NEO_OK;
-    REQUIRE((long)NV * P <= 4190000L, "at most 4.19 M rows (point-views) per call");
-    REQUIRE(w && x_enc && cond && tape && g_rgb && g_sigma && gw && gb && g_pre, "null pointer");
-    for (int i = 0; i < 9; ++i) REQUIRE(w[i] && gw[i] && gb[i], "null weight / gradient pointer");
     ORDERED(ctx, static_cast<hipStream_t>(stream));
     if (ctx->train_scratch.reserve(neo::pix_train_scratch_floats(NV, P) * sizeof(float))) return NEO_ERR_NOMEM;
     neo::launch_pix_train_backward(w, x_enc, cond, NV, P, tape, ctx->train_scratch.as<float>(), g_rgb, g_sigma, gw, gb, g_x_enc, g_pre,

@@ -108,6 +108,34 @@ inline int check_launch() {
     return 0;
 }
 
+// world -> camera of the source views: rot = c2w[:3,:3]^T ; trans = -rot @ c2w[:3,3]   (neo360/util.py:64-66,
+// vanilla_nerf/util.py:20-34), fp32
+inline void fill_views(const float* poses, int nv, neo::TpViews& v) {
+    for (int i = 0; i < nv; ++i) {
+        const float* m = poses + i * 16;
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) v.rot[i][r * 3 + c] = m[c * 4 + r];
+        for (int r = 0; r < 3; ++r) {
+            float acc = v.rot[i][r * 3 + 0] * m[0 * 4 + 3];
+            acc = acc + v.rot[i][r * 3 + 1] * m[1 * 4 + 3];
+            acc = acc + v.rot[i][r * 3 + 2] * m[2 * 4 + 3];
+            v.trans[i][r] = -acc;
+        }
+    }
+}
+
+// What one call hands to the kernels: a copy of the uploaded scene descriptor carrying THIS call's intrinsics, and its views.
+struct CallScene {
+    neo::TpScene sc;
+    neo::TpViews views;
+};
+inline CallScene call_scene(const neo::TpScene& uploaded, const float* src_poses, int NV, float focal, float cx, float cy) {
+    CallScene cs{uploaded, {}};
+    cs.sc.focal = focal; cs.sc.cx = cx; cs.sc.cy = cy;
+    fill_views(src_poses, NV, cs.views);
+    return cs;
+}
+
 }  // namespace neo_host
 
 // Orders this call behind the previous call of the same context when the stream differs (neo_ctx::order_begin) and

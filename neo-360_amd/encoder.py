@@ -25,8 +25,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .context import f32, ptr
-from .models import _HipModule, _fingerprint, _ptr_table
+from .context import f32, ptr, ptr_table
+from .models import _HipModule, _fingerprint
 
 
 def _kaiming(m):
@@ -98,7 +98,7 @@ class GridEncoder(_HipModule):
         fp = _fingerprint(ws + bs)
         if ctx.uploaded.get("enc") == fp:
             return
-        _lib.check(ctx.lib.neo_enc_upload(ctx.handle, _ptr_table(ws), _ptr_table(bs), ctx.stream()))
+        _lib.check(ctx.lib.neo_enc_upload(ctx.handle, ptr_table(ws), ptr_table(bs), ctx.stream()))
         ctx.uploaded["enc"] = fp
 
     @torch.no_grad()
@@ -214,8 +214,8 @@ class _PillarStage(torch.autograd.Function):
         gw = [torch.zeros_like(w) for w in ws]
         gb = [torch.zeros_like(b) for b in bs]
         g_lat = torch.zeros_like(latent) if ctx_.needs_input_grad[2] else None
-        _lib.check(ctx.lib.neo_enc_floorplans_backward(ctx.handle, _ptr_table(ws), _ptr_table(bs), ptr(latent), *geo, host_poses,
+        _lib.check(ctx.lib.neo_enc_floorplans_backward(ctx.handle, ptr_table(ws), ptr_table(bs), ptr(latent), *geo, host_poses,
                                                        f0, cx, cy, G0, G1, G2, ptr(ctx_.tape), ptr(grads[0]), ptr(grads[1]),
-                                                       ptr(grads[2]), _ptr_table(gw), _ptr_table(gb), ptr(g_lat), ctx.stream()))
+                                                       ptr(grads[2]), ptr_table(gw), ptr_table(gb), ptr(g_lat), ctx.stream()))
         out = [g if need else None for g, need in zip(gw + gb, ctx_.needs_input_grad[3:])]
         return (None, None, g_lat, *out)

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .context import CallOverlap, f32, new_context, ptr
+from .context import CallOverlap, f32, new_context, ptr, ptr_table
 
 
 def _xavier_linear(n_in, n_out, xavier=True):
@@ -56,13 +56,6 @@ class _SceneKey:
         tensors = tuple(tensors)
         return (len(tensors) == len(self.tensors) and all(a is b for a, b in zip(tensors, self.tensors))
                 and tuple(t._version for t in tensors) == self.versions and self._enc_fp(encoder) == self.enc)
-
-
-def _ptr_table(tensors):
-    arr = (ctypes.c_void_p * len(tensors))()
-    for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr()
-    return arr
 
 
 class NeRFMLP(nn.Module):
@@ -158,6 +151,39 @@ class _HipModule(nn.Module):
             ctx.set_precision(want)
             ctx._precision = want
         return ctx
+
+    @staticmethod
+    def _set_mode(ctx, attr, setter, mode):
+        """An integer mode of the library context, set only when it differs from the one cached on `ctx` as `attr`."""
+        if getattr(ctx, attr, None) != mode:
+            _lib.check(getattr(ctx.lib, setter)(ctx.handle, int(mode)))
+            setattr(ctx, attr, mode)
+
+    # the renderer's upload: (key in ctx.uploaded, library function), its MLPs in slot order, and per MLP what the call takes
+    # besides the two tables - (arguments in front of them, tensors behind them: uploaded too, so part of the fingerprint)
+    _upload = None
+
+    def _mlps(self):
+        raise NotImplementedError
+
+    @staticmethod
+    def _upload_extra(mlp):
+        return (), []
+
+    def _sync_weights(self, ctx):
+        """Re-packs on the device every MLP whose parameters moved or changed in place since its last upload."""
+        kind, upload = self._upload
+        for slot, mlp in enumerate(self._mlps()):
+            layers = mlp.ordered_layers()
+            ws = [f32(l.weight.detach(), "weight") for l in layers]
+            bs = [f32(l.bias.detach(), "bias") for l in layers]
+            lead, tail = self._upload_extra(mlp)
+            fp = _fingerprint(ws + bs + tail)
+            if ctx.uploaded.get((kind, slot)) == fp:
+                continue
+            _lib.check(getattr(ctx.lib, upload)(ctx.handle, slot, *lead, ptr_table(ws), ptr_table(bs), *[ptr(t) for t in tail],
+                                                ctx.stream()))
+            ctx.uploaded[(kind, slot)] = fp
 
     def close(self):
         """Release the library contexts (packed weights, scene features, workspaces) now.  Deferred reads of the
@@ -298,16 +324,10 @@ class NeRF(_HipModule):
         self.coarse_mlp = NeRFMLP(min_deg_point, max_deg_point, deg_view)
         self.fine_mlp = NeRFMLP(min_deg_point, max_deg_point, deg_view)
 
-    def _sync_weights(self, ctx):
-        for slot, mlp in enumerate((self.coarse_mlp, self.fine_mlp)):
-            layers = mlp.ordered_layers()
-            ws = [f32(l.weight.detach(), "weight") for l in layers]
-            bs = [f32(l.bias.detach(), "bias") for l in layers]
-            fp = _fingerprint(ws + bs)
-            if ctx.uploaded.get(("vanilla", slot)) == fp:
-                continue
-            _lib.check(ctx.lib.neo_vanilla_upload_mlp(ctx.handle, slot, _ptr_table(ws), _ptr_table(bs), ctx.stream()))
-            ctx.uploaded[("vanilla", slot)] = fp
+    _upload = ("vanilla", "neo_vanilla_upload_mlp")
+
+    def _mlps(self):
+        return (self.coarse_mlp, self.fine_mlp)
 
     def forward(self, rays, randomized, white_bkgd, near, far, seed=None):
         """Returns [(rgb (B,3), acc (B,), depth (B,))] * 2, as the reference.  randomized=True (stratified samples, random
@@ -436,25 +456,17 @@ class NeRF_TP(_HipModule):
     def _context(self, device):
         ctx = super()._context(device)
         mode = int(self.preproject) if (self.preproject in (2, 3) and self.preproject is not True) else int(bool(self.preproject))
-        if getattr(ctx, "_preproject", None) != mode:
-            _lib.check(ctx.lib.neo_tp_set_preproject(ctx.handle, mode))
-            ctx._preproject = mode
+        self._set_mode(ctx, "_preproject", "neo_tp_set_preproject", mode)
         return ctx
 
     def _mlps(self):
         return (self.fg_coarse_mlp, self.fg_fine_mlp, self.bg_coarse_mlp, self.bg_fine_mlp)
 
-    def _sync_weights(self, ctx):
-        for slot, mlp in enumerate(self._mlps()):
-            layers = mlp.ordered_layers()
-            ws = [f32(l.weight.detach(), "weight") for l in layers]
-            bs = [f32(l.bias.detach(), "bias") for l in layers]
-            fp = _fingerprint(ws + bs)
-            if ctx.uploaded.get(("tp", slot)) == fp:
-                continue
-            _lib.check(ctx.lib.neo_tp_upload_mlp(ctx.handle, slot, mlp.input_ch, _ptr_table(ws), _ptr_table(bs),
-                                                 ctx.stream()))
-            ctx.uploaded[("tp", slot)] = fp
+    _upload = ("tp", "neo_tp_upload_mlp")
+
+    @staticmethod
+    def _upload_extra(mlp):
+        return (mlp.input_ch,), []
 
     @torch.no_grad()
     def set_scene(self, plane_xz, plane_xy, plane_yz, latent, image_wh, preproject=None, _source=None):
@@ -767,21 +779,13 @@ class PixelNeRF(_HipModule):
 
     def _context(self, device):
         ctx = super()._context(device)
-        if getattr(ctx, "_pix_preproject", None) != bool(self.preproject):
-            _lib.check(ctx.lib.neo_pix_set_preproject(ctx.handle, int(bool(self.preproject))))
-            ctx._pix_preproject = bool(self.preproject)
+        self._set_mode(ctx, "_pix_preproject", "neo_pix_set_preproject", bool(self.preproject))
         return ctx
 
-    def _sync_weights(self, ctx):
-        for slot, mlp in enumerate((self.coarse_mlp, self.fine_mlp)):
-            layers = mlp.ordered_layers()
-            ws = [f32(l.weight.detach(), "weight") for l in layers]
-            bs = [f32(l.bias.detach(), "bias") for l in layers]
-            fp = _fingerprint(ws + bs)
-            if ctx.uploaded.get(("pix", slot)) == fp:
-                continue
-            _lib.check(ctx.lib.neo_pix_upload_mlp(ctx.handle, slot, _ptr_table(ws), _ptr_table(bs), ctx.stream()))
-            ctx.uploaded[("pix", slot)] = fp
+    _upload = ("pix", "neo_pix_upload_mlp")
+
+    def _mlps(self):
+        return (self.coarse_mlp, self.fine_mlp)
 
     @torch.no_grad()
     def set_scene(self, latent, image_wh):
@@ -972,24 +976,17 @@ class MipNeRF360(_HipModule):
     def _context(self, device):
         ctx = super()._context(device)
         mode = -1 if self.layered is None else int(bool(self.layered))
-        if getattr(ctx, "_mip_layered", None) != mode:
-            _lib.check(ctx.lib.neo_mip_set_layered(ctx.handle, mode))
-            ctx._mip_layered = mode
+        self._set_mode(ctx, "_mip_layered", "neo_mip_set_layered", mode)
         return ctx
 
-    def _sync_weights(self, ctx):
-        for slot, mlp in enumerate(self.mlps):
-            layers = mlp.ordered_layers()
-            ws = [f32(l.weight.detach(), "weight") for l in layers]
-            bs = [f32(l.bias.detach(), "bias") for l in layers]
-            basis = f32(mlp.pos_basis_t, "pos_basis_t")
-            fp = _fingerprint(ws + bs + [basis])
-            if ctx.uploaded.get(("mip", slot)) == fp:
-                continue
-            _lib.check(ctx.lib.neo_mip_upload_mlp(ctx.handle, slot, mlp.netwidth, mlp.netdepth,
-                                                  0 if mlp.disable_rgb else 1, _ptr_table(ws), _ptr_table(bs),
-                                                  ptr(basis), ctx.stream()))
-            ctx.uploaded[("mip", slot)] = fp
+    _upload = ("mip", "neo_mip_upload_mlp")
+
+    def _mlps(self):
+        return self.mlps
+
+    @staticmethod
+    def _upload_extra(mlp):
+        return (mlp.netwidth, mlp.netdepth, 0 if mlp.disable_rgb else 1), [f32(mlp.pos_basis_t, "pos_basis_t")]
 
     def forward(self, batch, train_frac, randomized, is_train, near, far, seed=None):
         """randomized=True (one sampling jitter per ray and level) or a call that wants gradients (`_wants_grad()`: the

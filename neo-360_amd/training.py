@@ -16,7 +16,7 @@ import os
 import torch
 
 from . import _lib
-from .context import f32, get_context, ptr
+from .context import f32, get_context, ptr, ptr_table
 
 
 def _ctx(t, ctx):
@@ -344,6 +344,15 @@ def channels_last_rows(x, ctx=None):
     return _ChannelsLast.apply(x, ctx)
 
 
+def _map_gather_call(lib, kind, col, mshape, backward=False):
+    """Which entry point looks up in (or scatters into) a map of shape mshape: (function, its row arguments - texels, and the row
+    pitch for a column slice -, byte offset of the lookup's first column)."""
+    suffix = "_backward" if backward else ""
+    if col is not None:
+        return getattr(lib, "neo_tp_gather_map_slice" + suffix), (mshape[0], mshape[1]), 4 * int(col)
+    return getattr(lib, ("neo_pix_gather_map" if kind == "pix" else "neo_tp_gather_map") + suffix), (mshape[0],), 0
+
+
 class _MapGather(torch.autograd.Function):
     """Bilinear lookup in a caller-owned channels-last map (NV Hf Wf, C) at get_local_feats' taps, with the run-merged
     scatter-add as its backward (neo_tp_gather_map / _backward).  `col` / `width`: a column slice of a wider map (round 6:
@@ -359,8 +368,7 @@ class _MapGather(torch.autograd.Function):
         c = module._context(pts.device)
         host_poses, NV, focal, cx, cy = module._camera_args(rays)
         P = pts.shape[0]
-        sliced = col is not None
-        if sliced:
+        if col is not None:
             if kind != "tp" or width % 64 or col % 4 or col < 0 or col + width > gmap.shape[1]:
                 raise ValueError("bad map slice [%s, +%s) of %s (kind %s)" % (col, width, tuple(gmap.shape), kind))
             C = int(width)
@@ -369,12 +377,8 @@ class _MapGather(torch.autograd.Function):
         out = torch.empty(NV * P, C, device=pts.device)
         # the row count travels with the pointer: the library rejects a map that is not NV*Hf*Wf rows of the geometry uploaded in
         # this module's context (it used to be indexed - and, in the backward, scattered into - unchecked)
-        if sliced:
-            _lib.check(c.lib.neo_tp_gather_map_slice(c.handle, gmap.data_ptr() + 4 * int(col), gmap.shape[0], gmap.shape[1], C, ptr(pts), P,
-                                                     host_poses, NV, focal, cx, cy, ptr(out), c.stream()))
-        else:
-            fn = c.lib.neo_pix_gather_map if kind == "pix" else c.lib.neo_tp_gather_map
-            _lib.check(fn(c.handle, ptr(gmap), gmap.shape[0], C, ptr(pts), P, host_poses, NV, focal, cx, cy, ptr(out), c.stream()))
+        fn, rows, first_col = _map_gather_call(c.lib, kind, col, gmap.shape)
+        _lib.check(fn(c.handle, gmap.data_ptr() + first_col, *rows, C, ptr(pts), P, host_poses, NV, focal, cx, cy, ptr(out), c.stream()))
         ctx_.save_for_backward(pts)
         ctx_.meta = (c, host_poses, NV, focal, cx, cy, tuple(gmap.shape), kind, col, C, shared)
         return out
@@ -395,13 +399,12 @@ class _MapGather(torch.autograd.Function):
                 if first:
                     shared["buf"] = torch.zeros(mshape, device=pts.device)
                 buf = shared["buf"]
-            _lib.check(c.lib.neo_tp_gather_map_slice_backward(c.handle, mshape[0], mshape[1], C, ptr(pts), pts.shape[0], host_poses, NV, focal,
-                                                              cx, cy, ptr(g), buf.data_ptr() + 4 * int(col), c.stream()))
-            return None, (buf if first else None), None, None, None, None, None, None
-        g_map = torch.zeros(mshape, device=pts.device)
-        fn = c.lib.neo_pix_gather_map_backward if kind == "pix" else c.lib.neo_tp_gather_map_backward
-        _lib.check(fn(c.handle, mshape[0], mshape[1], ptr(pts), pts.shape[0], host_poses, NV, focal, cx, cy, ptr(g), ptr(g_map), c.stream()))
-        return None, g_map, None, None, None, None, None, None
+        else:
+            first, buf = True, torch.zeros(mshape, device=pts.device)
+        fn, rows, first_col = _map_gather_call(c.lib, kind, col, mshape, backward=True)
+        _lib.check(fn(c.handle, *rows, C, ptr(pts), pts.shape[0], host_poses, NV, focal, cx, cy, ptr(g), buf.data_ptr() + first_col,
+                      c.stream()))
+        return None, (buf if first else None), None, None, None, None, None, None
 
 
 class _GradSink(torch.autograd.Function):
@@ -441,6 +444,51 @@ def _zeros_like_shapes(wshapes, bshapes, dev):
     return views[:len(wshapes)], views[len(wshapes):]
 
 
+# ---- a native MLP chain under autograd: the steps every such Function shares -------------------------------------------------
+
+def _mlp_params(mlp):
+    """The parameters of an MLP container as the chains take them: weights, then biases, in the library's layer order."""
+    layers = mlp.ordered_layers()
+    return [l.weight for l in layers] + [l.bias for l in layers]
+
+
+def _check_layers(what, ws, bs, want):
+    """The library reads weights of fixed shapes: anything else is caught here, as the reference's matmuls would."""
+    for i, (w, b) in enumerate(zip(ws, bs)):
+        if tuple(w.shape) != want[i] or tuple(b.shape) != (want[i][0],):
+            raise ValueError("%s %d: weight %s / bias %s, expected %s / (%d,)"
+                             % (what, i, tuple(w.shape), tuple(b.shape), want[i], want[i][0]))
+
+
+def _check_rows(rows, *named):
+    """View-major row tensors (name, tensor, width): each must be (NV*P, width)."""
+    for name, t, width in named:
+        if tuple(t.shape) != (rows, width):
+            raise ValueError("%s must be (NV*P, %d) = (%d, %d), got %s" % (name, width, rows, width, tuple(t.shape)))
+
+
+def _detached(ws, bs):
+    return [f32(w.detach(), "weight") for w in ws], [f32(b.detach(), "bias") for b in bs]
+
+
+def _grad_or_zeros(g, name, rows, width, dev):
+    """The incoming gradient of an output as dense fp32 (rows, width), or zeros when autograd has none for it."""
+    return f32(g.reshape(rows, width).contiguous(), name) if g is not None else torch.zeros(rows, width, device=dev)
+
+
+def _zero_param_grads(wd, one_buffer=False):
+    """Zeroed gradient tensors for the weights wd and their biases: one tensor each, or (one_buffer) views of a single fill."""
+    wshapes = [tuple(w.shape) for w in wd]
+    bshapes = [(sh[0],) for sh in wshapes]
+    if one_buffer:
+        return _zeros_like_shapes(wshapes, bshapes, wd[0].device)
+    return [torch.zeros(sh, device=wd[0].device) for sh in wshapes], [torch.zeros(sh, device=wd[0].device) for sh in bshapes]
+
+
+def _nerfpp_layer_shapes(pe):
+    return [(128, pe + 640), (128, 128), (128, 128), (128, 128 + pe + 640), (64, 155), (64, 64), (128, 128), (1, 128), (3, 64)]
+
+
 class _TrainMLPPre(torch.autograd.Function):
     """NeRFPPMLP on the PROJECTED latent: `pre` (NV*P, 256) = [W0_loc f | W3_loc f] replaces the (NV*P, 512) local feature rows
     (neo_tp_mlp_train_forward_pre / _backward_pre).  The gradient of the local weight columns is NOT produced here: it flows
@@ -452,48 +500,40 @@ class _TrainMLPPre(torch.autograd.Function):
         pe, npts = input_ch * 21, x_enc.shape[1]
         if x_enc.dim() != 3 or tuple(x_enc.shape) != (nv, npts, pe):
             raise ValueError("x_enc must be (NV, P, %d), got %s" % (pe, tuple(x_enc.shape)))
-        for name, t, width in (("cond_rows", cond_rows, 27), ("world_feat", world_feat, 128), ("pre", pre, 256)):
-            if tuple(t.shape) != (nv * npts, width):
-                raise ValueError("%s must be (NV*P, %d) = (%d, %d), got %s" % (name, width, nv * npts, width, tuple(t.shape)))
-        want = [(128, pe + 640), (128, 128), (128, 128), (128, 128 + pe + 640), (64, 155), (64, 64), (128, 128), (1, 128), (3, 64)]
-        for i, (w, b) in enumerate(zip(ws, bs)):
-            if tuple(w.shape) != want[i] or tuple(b.shape) != (want[i][0],):
-                raise ValueError("layer %d: weight %s / bias %s, expected %s / (%d,)"
-                                 % (i, tuple(w.shape), tuple(b.shape), want[i], want[i][0]))
+        _check_rows(nv * npts, ("cond_rows", cond_rows, 27), ("world_feat", world_feat, 128), ("pre", pre, 256))
+        _check_layers("layer", ws, bs, _nerfpp_layer_shapes(pe))
         xe = f32(x_enc, "x_enc").reshape(-1, pe)
         pf, wf, cond = f32(pre, "pre"), f32(world_feat, "world_feat"), f32(cond_rows, "cond_rows")
         c = _ctx(xe, lib_ctx)
-        wd = [f32(w.detach(), "weight") for w in ws]
-        bd = [f32(b.detach(), "bias") for b in bs]
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        wd, bd = _detached(ws, bs)
         raw_rgb = torch.empty(npts, 3, device=xe.device)
         raw_sigma = torch.empty(npts, 1, device=xe.device)
         tape = torch.empty(c.lib.neo_tp_mlp_train_tape_floats(nv, npts), device=xe.device)
         chain = ctypes.c_int(-1)        # the tape layout this forward wrote (neo_train_chain_mode at THIS call), for the backward
-        _lib.check(c.lib.neo_tp_mlp_train_forward_pre(c.handle, input_ch, tab(wd), tab(bd), ptr(xe), ptr(pf), ptr(wf), ptr(cond), nv,
-                                                      npts, ptr(tape), ptr(raw_rgb), ptr(raw_sigma), ctypes.byref(chain), c.stream()))
+        _lib.check(c.lib.neo_tp_mlp_train_forward_pre(c.handle, input_ch, ptr_table(wd), ptr_table(bd), ptr(xe), ptr(pf), ptr(wf),
+                                                      ptr(cond), nv, npts, ptr(tape), ptr(raw_rgb), ptr(raw_sigma),
+                                                      ctypes.byref(chain), c.stream()))
         ctx_.save_for_backward(xe, wf, cond, tape, *wd)
-        ctx_.meta = (c, input_ch, nv, npts, x_enc.shape, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs], chain.value)
+        ctx_.meta = (c, input_ch, nv, npts, x_enc.shape, chain.value)
         return raw_rgb, raw_sigma
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx_, g_rgb, g_sigma):
         xe, wf, cond, tape, *wd = ctx_.saved_tensors
-        c, input_ch, nv, npts, xshape, wshapes, bshapes, chain = ctx_.meta
+        c, input_ch, nv, npts, xshape, chain = ctx_.meta
         if ctx_.needs_input_grad[4]:
             raise NotImplementedError("nerfpp_mlp: no gradient for cond_rows (the reference's view directions are data)")
         dev = xe.device
-        g_rgb = f32(g_rgb.contiguous(), "g_rgb") if g_rgb is not None else torch.zeros(npts, 3, device=dev)
-        g_sigma = f32(g_sigma.contiguous(), "g_sigma") if g_sigma is not None else torch.zeros(npts, 1, device=dev)
-        gw, gb = _zeros_like_shapes(wshapes, bshapes, dev)
+        g_rgb = _grad_or_zeros(g_rgb, "g_rgb", npts, 3, dev)
+        g_sigma = _grad_or_zeros(g_sigma, "g_sigma", npts, 1, dev)
+        gw, gb = _zero_param_grads(wd, one_buffer=True)
         gx = torch.empty_like(xe) if ctx_.needs_input_grad[3] else None
         gworld = torch.empty_like(wf) if ctx_.needs_input_grad[5] else None
         gpre = torch.empty(nv * npts, 256, device=dev)
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.check(c.lib.neo_tp_mlp_train_backward_pre(c.handle, input_ch, tab(wd), ptr(xe), ptr(wf), ptr(cond), nv, npts, ptr(tape),
-                                                       ptr(g_rgb), ptr(g_sigma), tab(gw), tab(gb), ptr(gx), ptr(gpre), ptr(gworld),
-                                                       chain, c.stream()))
+        _lib.check(c.lib.neo_tp_mlp_train_backward_pre(c.handle, input_ch, ptr_table(wd), ptr(xe), ptr(wf), ptr(cond), nv, npts,
+                                                       ptr(tape), ptr(g_rgb), ptr(g_sigma), ptr_table(gw), ptr_table(gb), ptr(gx),
+                                                       ptr(gpre), ptr(gworld), chain, c.stream()))
         return (None, None, None, gx.reshape(xshape) if gx is not None else None, None, gworld, gpre, *gw, *gb)
 
 
@@ -545,15 +585,12 @@ def linear(x, w, b=None, relu=False, ctx=None):
     return _Linear.apply(ctx, x, w, b, relu)
 
 
-class _LinearNoBias:
+def _linear_no_bias(lib_ctx, x, w):
     """y = x W^T for a texel-space projection (230,400 x 512 -> 256 at the bench size), forward and both backward products on
     the library's OWN GEMM kernels (round 6: neo_linear_forward / neo_linear_input_grad = k_sgemm, neo_linear_weight_grad = k_dw;
     rounds 4-5 called torch's matmul here - hipBLASLt `Cijk_*` kernels, 11.5 % of a training step in
     profiles/r05_train_step_kernel_stats.csv)."""
-
-    @staticmethod
-    def apply(lib_ctx, x, w):
-        return _Linear.apply(lib_ctx, x, w, None, False)
+    return _Linear.apply(lib_ctx, x, w, None, False)
 
 
 def weight_grad(gy, x, bias=False, ctx=None):
@@ -578,7 +615,7 @@ def project_latent(mlp, latent_cl, ctx=None):
     pe = mlp.input_ch * 21
     w0, w3 = mlp.pts_linears[0].weight, mlp.pts_linears[3].weight
     wcat = torch.cat([w0[:, pe:pe + 512], w3[:, 128 + pe:128 + pe + 512]], dim=0)          # (256, 512)
-    return _LinearNoBias.apply(ctx, latent_cl, wcat)
+    return _linear_no_bias(ctx, latent_cl, wcat)
 
 
 def project_latent_all(mlps, latent_cl, ctx=None):
@@ -592,15 +629,13 @@ def project_latent_all(mlps, latent_cl, ctx=None):
         w0, w3 = mlp.pts_linears[0].weight, mlp.pts_linears[3].weight
         blocks += [w0[:, pe:pe + 512], w3[:, 128 + pe:128 + pe + 512]]
     shared = {"buf": None}
-    return _GradSink.apply(_LinearNoBias.apply(ctx, latent_cl, torch.cat(blocks, dim=0)), shared), shared
+    return _GradSink.apply(_linear_no_bias(ctx, latent_cl, torch.cat(blocks, dim=0)), shared), shared
 
 
 def nerfpp_mlp_projected(mlp, x_enc, cond_rows, world_feat, pre, nv, ctx=None):
     """nerfpp_mlp with the gathered projected latent `pre` (NV*P, 256) in place of the (NV*P, 512) local features: the
     512-wide segments of layer 0 and of the skip layer - forward, dX and dW - are not executed per row."""
-    layers = mlp.ordered_layers()
-    params = [l.weight for l in layers] + [l.bias for l in layers]
-    return _TrainMLPPre.apply(ctx, mlp.input_ch, nv, x_enc, cond_rows, world_feat, pre, *params)
+    return _TrainMLPPre.apply(ctx, mlp.input_ch, nv, x_enc, cond_rows, world_feat, pre, *_mlp_params(mlp))
 
 
 class _TrainMLP(torch.autograd.Function):
@@ -609,57 +644,45 @@ class _TrainMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, lib_ctx, input_ch, nv, x_enc, cond_rows, world_feat, local_feat, *params):
         ws, bs = params[:9], params[9:]
-        # the library reads rows of fixed widths: anything else is caught here, as the reference's matmuls would
         pe, npts = input_ch * 21, x_enc.shape[1]
         if x_enc.dim() != 3 or tuple(x_enc.shape) != (nv, npts, pe):
             raise ValueError("x_enc must be (NV, P, %d), got %s" % (pe, tuple(x_enc.shape)))
-        for name, t, width in (("cond_rows", cond_rows, 27), ("world_feat", world_feat, 128), ("local_feat", local_feat, 512)):
-            if tuple(t.shape) != (nv * npts, width):
-                raise ValueError("%s must be (NV*P, %d) = (%d, %d), got %s" % (name, width, nv * npts, width, tuple(t.shape)))
-        want = [(128, pe + 640), (128, 128), (128, 128), (128, 128 + pe + 640), (64, 155), (64, 64), (128, 128), (1, 128), (3, 64)]
-        for i, (w, b) in enumerate(zip(ws, bs)):
-            if tuple(w.shape) != want[i] or tuple(b.shape) != (want[i][0],):
-                raise ValueError("NeRFPPMLP layer %d: weight %s / bias %s, expected %s / (%d,)"
-                                 % (i, tuple(w.shape), tuple(b.shape), want[i], want[i][0]))
+        _check_rows(nv * npts, ("cond_rows", cond_rows, 27), ("world_feat", world_feat, 128), ("local_feat", local_feat, 512))
+        _check_layers("NeRFPPMLP layer", ws, bs, _nerfpp_layer_shapes(pe))
         # the three input tensors go to the library as they are: the (NV*P, 703) concatenation the reference forms is never built
         xe = f32(x_enc, "x_enc").reshape(-1, pe)
         lf, wf = f32(local_feat, "local_feat"), f32(world_feat, "world_feat")
         cond = f32(cond_rows, "cond_rows")
         c = _ctx(xe, lib_ctx)
-        wd = [f32(w.detach(), "weight") for w in ws]
-        bd = [f32(b.detach(), "bias") for b in bs]
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        wd, bd = _detached(ws, bs)
         raw_rgb = torch.empty(npts, 3, device=xe.device)
         raw_sigma = torch.empty(npts, 1, device=xe.device)
         # the activations live in a tensor owned by THIS autograd node: a training step runs several MLP forwards
         # (inside / outside the sphere, coarse / fine) before the first backward
         tape = torch.empty(c.lib.neo_tp_mlp_train_tape_floats(nv, npts), device=xe.device)
-        _lib.check(c.lib.neo_tp_mlp_train_forward(c.handle, input_ch, tab(wd), tab(bd), ptr(xe), ptr(lf), ptr(wf), ptr(cond), nv,
-                                                  npts, ptr(tape), ptr(raw_rgb), ptr(raw_sigma), c.stream()))
+        _lib.check(c.lib.neo_tp_mlp_train_forward(c.handle, input_ch, ptr_table(wd), ptr_table(bd), ptr(xe), ptr(lf), ptr(wf),
+                                                  ptr(cond), nv, npts, ptr(tape), ptr(raw_rgb), ptr(raw_sigma), c.stream()))
         ctx_.save_for_backward(xe, lf, wf, cond, tape, *wd)
-        ctx_.meta = (c, input_ch, nv, npts, x_enc.shape, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs])
+        ctx_.meta = (c, input_ch, nv, npts, x_enc.shape)
         return raw_rgb, raw_sigma
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx_, g_rgb, g_sigma):
         xe, lf, wf, cond, tape, *wd = ctx_.saved_tensors
-        c, input_ch, nv, npts, xshape, wshapes, bshapes = ctx_.meta
+        c, input_ch, nv, npts, xshape = ctx_.meta
         if ctx_.needs_input_grad[4]:
             raise NotImplementedError("nerfpp_mlp: no gradient for cond_rows (the reference's view directions are data)")
-        dev = xe.device
-        g_rgb = f32(g_rgb.contiguous(), "g_rgb") if g_rgb is not None else torch.zeros(npts, 3, device=dev)
-        g_sigma = f32(g_sigma.contiguous(), "g_sigma") if g_sigma is not None else torch.zeros(npts, 1, device=dev)
-        gw = [torch.zeros(s, device=dev) for s in wshapes]
-        gb = [torch.zeros(s, device=dev) for s in bshapes]
+        g_rgb = _grad_or_zeros(g_rgb, "g_rgb", npts, 3, xe.device)
+        g_sigma = _grad_or_zeros(g_sigma, "g_sigma", npts, 1, xe.device)
+        gw, gb = _zero_param_grads(wd)
         # only the input gradients somebody asked for are computed (each its own dense tensor, no slicing afterwards)
         gx = torch.empty_like(xe) if ctx_.needs_input_grad[3] else None
         gworld = torch.empty_like(wf) if ctx_.needs_input_grad[5] else None
         glocal = torch.empty_like(lf) if ctx_.needs_input_grad[6] else None
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.check(c.lib.neo_tp_mlp_train_backward(c.handle, input_ch, tab(wd), ptr(xe), ptr(lf), ptr(wf), ptr(cond), nv, npts,
-                                                   ptr(tape), ptr(g_rgb), ptr(g_sigma), tab(gw), tab(gb), ptr(gx), ptr(glocal),
-                                                   ptr(gworld), c.stream()))
+        _lib.check(c.lib.neo_tp_mlp_train_backward(c.handle, input_ch, ptr_table(wd), ptr(xe), ptr(lf), ptr(wf), ptr(cond), nv, npts,
+                                                   ptr(tape), ptr(g_rgb), ptr(g_sigma), ptr_table(gw), ptr_table(gb), ptr(gx),
+                                                   ptr(glocal), ptr(gworld), c.stream()))
         return (None, None, None, gx.reshape(xshape) if gx is not None else None, None, gworld, glocal, *gw, *gb)
 
 
@@ -670,9 +693,7 @@ def nerfpp_mlp(mlp, x_enc, cond_rows, world_feat, local_feat, nv, ctx=None):
     models.NeRFPPMLP (parameter container, reference state_dict layout); gradients flow to all of its parameters and to
     x_enc / world_feat / local_feat (the latter two continue into gather_features' backward).  Exact fp32 matrix
     arithmetic; the fused inference evaluators are untouched."""
-    layers = mlp.ordered_layers()
-    params = [l.weight for l in layers] + [l.bias for l in layers]
-    return _TrainMLP.apply(ctx, mlp.input_ch, nv, x_enc, cond_rows, world_feat, local_feat, *params)
+    return _TrainMLP.apply(ctx, mlp.input_ch, nv, x_enc, cond_rows, world_feat, local_feat, *_mlp_params(mlp))
 
 
 class _TrainVanillaMLP(torch.autograd.Function):
@@ -683,42 +704,35 @@ class _TrainVanillaMLP(torch.autograd.Function):
         ws, bs = params[:12], params[12:]
         if x_enc.dim() != 3 or x_enc.shape[-1] != 63 or tuple(dir_enc.shape) != (x_enc.shape[0], 27):
             raise ValueError("x_enc must be (B, N, 63) and dir_enc (B, 27), got %s / %s" % (tuple(x_enc.shape), tuple(dir_enc.shape)))
-        want = [(256, 63)] + [(256, 256)] * 4 + [(256, 319)] + [(256, 256)] * 2 + [(128, 283), (256, 256), (1, 256), (3, 128)]
-        for i, (w, b) in enumerate(zip(ws, bs)):
-            if tuple(w.shape) != want[i] or tuple(b.shape) != (want[i][0],):
-                raise ValueError("NeRFMLP layer %d: weight %s / bias %s, expected %s / (%d,)"
-                                 % (i, tuple(w.shape), tuple(b.shape), want[i], want[i][0]))
+        _check_layers("NeRFMLP layer", ws, bs,
+                      [(256, 63)] + [(256, 256)] * 4 + [(256, 319)] + [(256, 256)] * 2 + [(128, 283), (256, 256), (1, 256), (3, 128)])
         B, N, F = x_enc.shape
         x0 = f32(x_enc, "x_enc").reshape(-1, F).contiguous()
         cond = torch.tile(f32(dir_enc, "dir_enc")[:, None, :], (1, N, 1)).reshape(-1, dir_enc.shape[-1]).contiguous()
         c = _ctx(x0, lib_ctx)
-        wd = [f32(w.detach(), "weight") for w in ws]
-        bd = [f32(b.detach(), "bias") for b in bs]
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        wd, bd = _detached(ws, bs)
         R = B * N
         raw_rgb, raw_sigma = torch.empty(R, 3, device=x0.device), torch.empty(R, 1, device=x0.device)
         tape = torch.empty(c.lib.neo_vanilla_mlp_train_tape_floats(R), device=x0.device)
-        _lib.check(c.lib.neo_vanilla_mlp_train_forward(c.handle, tab(wd), tab(bd), ptr(x0), ptr(cond), R, ptr(tape), ptr(raw_rgb),
-                                                       ptr(raw_sigma), c.stream()))
+        _lib.check(c.lib.neo_vanilla_mlp_train_forward(c.handle, ptr_table(wd), ptr_table(bd), ptr(x0), ptr(cond), R, ptr(tape),
+                                                       ptr(raw_rgb), ptr(raw_sigma), c.stream()))
         ctx_.save_for_backward(x0, cond, tape, *wd)
-        ctx_.meta = (c, B, N, F, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs])
+        ctx_.meta = (c, B, N, F)
         return raw_rgb.reshape(B, N, 3), raw_sigma.reshape(B, N, 1)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx_, g_rgb, g_sigma):
         x0, cond, tape, *wd = ctx_.saved_tensors
-        c, B, N, F, wshapes, bshapes = ctx_.meta
-        dev, R = x0.device, B * N
-        g_rgb = f32(g_rgb.reshape(R, 3).contiguous(), "g_rgb") if g_rgb is not None else torch.zeros(R, 3, device=dev)
-        g_sigma = f32(g_sigma.reshape(R, 1).contiguous(), "g_sigma") if g_sigma is not None else torch.zeros(R, 1, device=dev)
-        gw = [torch.zeros(s, device=dev) for s in wshapes]
-        gb = [torch.zeros(s, device=dev) for s in bshapes]
+        c, B, N, F = ctx_.meta
+        R = B * N
+        g_rgb = _grad_or_zeros(g_rgb, "g_rgb", R, 3, x0.device)
+        g_sigma = _grad_or_zeros(g_sigma, "g_sigma", R, 1, x0.device)
+        gw, gb = _zero_param_grads(wd)
         g_x0 = torch.empty_like(x0) if ctx_.needs_input_grad[1] else None
         g_cond = torch.empty_like(cond) if ctx_.needs_input_grad[2] else None
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.check(c.lib.neo_vanilla_mlp_train_backward(c.handle, tab(wd), ptr(x0), ptr(cond), R, ptr(tape), ptr(g_rgb), ptr(g_sigma),
-                                                        tab(gw), tab(gb), ptr(g_x0), ptr(g_cond), c.stream()))
+        _lib.check(c.lib.neo_vanilla_mlp_train_backward(c.handle, ptr_table(wd), ptr(x0), ptr(cond), R, ptr(tape), ptr(g_rgb),
+                                                        ptr(g_sigma), ptr_table(gw), ptr_table(gb), ptr(g_x0), ptr(g_cond), c.stream()))
         gx = g_x0.reshape(B, N, F) if g_x0 is not None else None
         gd = g_cond.reshape(B, N, -1).sum(dim=1) if g_cond is not None else None      # the tiling's backward
         return (None, gx, gd, *gw, *gb)
@@ -728,9 +742,7 @@ def nerf_mlp(mlp, x_enc, dir_enc, ctx=None):
     """The reference's vanilla NeRFMLP.forward (vanilla_nerf/model.py:100-125) with autograd support: x_enc (B,N,63) encoded
     sample points, dir_enc (B,27) per-ray view-direction encodings -> raw_rgb (B,N,3), raw_sigma (B,N,1).  `mlp` is a
     models.NeRFMLP; gradients flow to all 24 parameter tensors and to both inputs.  Exact fp32 matrix arithmetic."""
-    layers = mlp.ordered_layers()
-    params = [l.weight for l in layers] + [l.bias for l in layers]
-    return _TrainVanillaMLP.apply(ctx, x_enc, dir_enc, *params)
+    return _TrainVanillaMLP.apply(ctx, x_enc, dir_enc, *_mlp_params(mlp))
 
 
 # ---- the module-level training call (neo360/model.py:697-820 calls self.model(batch, randomized=True, ...)) ------------------
@@ -921,56 +933,45 @@ class _PixTrainMLPPre(torch.autograd.Function):
         npts = x_enc.shape[1]
         if x_enc.dim() != 3 or tuple(x_enc.shape) != (nv, npts, 63):
             raise ValueError("x_enc must be (NV, P, 63), got %s" % (tuple(x_enc.shape),))
-        for name, t, width in (("cond_rows", cond_rows, 27), ("pre", pre, 128)):
-            if tuple(t.shape) != (nv * npts, width):
-                raise ValueError("%s must be (NV*P, %d) = (%d, %d), got %s" % (name, width, nv * npts, width, tuple(t.shape)))
-        want = [(128, 575), (128, 128), (128, 128), (128, 128), (128, 155), (128, 128), (128, 128), (1, 128), (3, 128)]
-        for i, (w, b) in enumerate(zip(ws, bs)):
-            if tuple(w.shape) != want[i] or tuple(b.shape) != (want[i][0],):
-                raise ValueError("PixelNeRF MLP layer %d: weight %s / bias %s, expected %s / (%d,)"
-                                 % (i, tuple(w.shape), tuple(b.shape), want[i], want[i][0]))
+        _check_rows(nv * npts, ("cond_rows", cond_rows, 27), ("pre", pre, 128))
+        _check_layers("PixelNeRF MLP layer", ws, bs,
+                      [(128, 575), (128, 128), (128, 128), (128, 128), (128, 155), (128, 128), (128, 128), (1, 128), (3, 128)])
         xe = f32(x_enc, "x_enc").reshape(-1, 63)
         pf, cond = f32(pre, "pre"), f32(cond_rows, "cond_rows")
         c = _ctx(xe, lib_ctx)
-        wd = [f32(w.detach(), "weight") for w in ws]
-        bd = [f32(b.detach(), "bias") for b in bs]
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        wd, bd = _detached(ws, bs)
         raw_rgb = torch.empty(npts, 3, device=xe.device)
         raw_sigma = torch.empty(npts, 1, device=xe.device)
         tape = torch.empty(c.lib.neo_pix_mlp_train_tape_floats(nv, npts), device=xe.device)
         chain = ctypes.c_int(-1)        # the tape layout this forward wrote: handed to the backward (see _TrainMLPPre)
-        _lib.check(c.lib.neo_pix_mlp_train_forward_pre(c.handle, tab(wd), tab(bd), ptr(xe), ptr(pf), ptr(cond), nv, npts, ptr(tape),
-                                                       ptr(raw_rgb), ptr(raw_sigma), ctypes.byref(chain), c.stream()))
+        _lib.check(c.lib.neo_pix_mlp_train_forward_pre(c.handle, ptr_table(wd), ptr_table(bd), ptr(xe), ptr(pf), ptr(cond), nv, npts,
+                                                       ptr(tape), ptr(raw_rgb), ptr(raw_sigma), ctypes.byref(chain), c.stream()))
         ctx_.save_for_backward(xe, cond, tape, *wd)
-        ctx_.meta = (c, nv, npts, x_enc.shape, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs], chain.value)
+        ctx_.meta = (c, nv, npts, x_enc.shape, chain.value)
         return raw_rgb, raw_sigma
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx_, g_rgb, g_sigma):
         xe, cond, tape, *wd = ctx_.saved_tensors
-        c, nv, npts, xshape, wshapes, bshapes, chain = ctx_.meta
+        c, nv, npts, xshape, chain = ctx_.meta
         if ctx_.needs_input_grad[3]:
             raise NotImplementedError("pixel_mlp: no gradient for cond_rows (the reference's view directions are data)")
         dev = xe.device
-        g_rgb = f32(g_rgb.contiguous(), "g_rgb") if g_rgb is not None else torch.zeros(npts, 3, device=dev)
-        g_sigma = f32(g_sigma.contiguous(), "g_sigma") if g_sigma is not None else torch.zeros(npts, 1, device=dev)
-        gw = [torch.zeros(s, device=dev) for s in wshapes]
-        gb = [torch.zeros(s, device=dev) for s in bshapes]
+        g_rgb = _grad_or_zeros(g_rgb, "g_rgb", npts, 3, dev)
+        g_sigma = _grad_or_zeros(g_sigma, "g_sigma", npts, 1, dev)
+        gw, gb = _zero_param_grads(wd)
         gx = torch.empty_like(xe) if ctx_.needs_input_grad[2] else None
         gpre = torch.empty(nv * npts, 128, device=dev)
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.check(c.lib.neo_pix_mlp_train_backward_pre(c.handle, tab(wd), ptr(xe), ptr(cond), nv, npts, ptr(tape), ptr(g_rgb), ptr(g_sigma),
-                                                        tab(gw), tab(gb), ptr(gx), ptr(gpre), chain, c.stream()))
+        _lib.check(c.lib.neo_pix_mlp_train_backward_pre(c.handle, ptr_table(wd), ptr(xe), ptr(cond), nv, npts, ptr(tape), ptr(g_rgb),
+                                                        ptr(g_sigma), ptr_table(gw), ptr_table(gb), ptr(gx), ptr(gpre), chain, c.stream()))
         return (None, None, gx.reshape(xshape) if gx is not None else None, None, gpre, *gw, *gb)
 
 
 def pixel_mlp_fused(mlp, x_enc, cond_rows, pre, nv, ctx=None):
     """pixel_mlp_projected as one native chain each way (round 6; the analogue of nerfpp_mlp_projected for the PixelNeRF decoder):
     same inputs, same outputs, gradients to all 18 parameter tensors and to `pre`."""
-    layers = mlp.ordered_layers()
-    params = [l.weight for l in layers] + [l.bias for l in layers]
-    return _PixTrainMLPPre.apply(ctx, nv, x_enc, cond_rows, pre, *params)
+    return _PixTrainMLPPre.apply(ctx, nv, x_enc, cond_rows, pre, *_mlp_params(mlp))
 
 
 def pixel_mlp_projected(mlp, x_enc, cond_rows, pre, nv, ctx=None):
@@ -998,7 +999,7 @@ def pixel_mlp_projected(mlp, x_enc, cond_rows, pre, nv, ctx=None):
 def project_pixel_latent(mlp, latent_cl, ctx=None):
     """G = F W0_loc^T per texel (texels, 512) -> (texels, 128): the latent's only path into PixelNeRF's MLP (no skip fires at
     depth 4), as project_latent does for NeRFPPMLP."""
-    return _LinearNoBias.apply(ctx, latent_cl, mlp.pts_linears[0].weight[:, 63:575])
+    return _linear_no_bias(ctx, latent_cl, mlp.pts_linears[0].weight[:, 63:575])
 
 
 def pix_render_train(module, rays, randomized, white_bkgd, near, far, latent, seed=None, return_samples=False):
@@ -1172,39 +1173,29 @@ class _MipTrainMLP(torch.autograd.Function):
         want = [(width, 504)] + [(width, width + 504 if (i - 1) % 4 == 0 and i - 1 > 0 else width) for i in range(1, depth)] + [(1, width)]
         if rgb:
             want += [(256, width), (128, 283), (3, 128)]
-        for i, (w, b) in enumerate(zip(ws, bs)):
-            if tuple(w.shape) != want[i] or tuple(b.shape) != (want[i][0],):
-                raise ValueError("Mip-NeRF 360 MLP layer %d: weight %s / bias %s, expected %s / (%d,)"
-                                 % (i, tuple(w.shape), tuple(b.shape), want[i], want[i][0]))
+        _check_layers("Mip-NeRF 360 MLP layer", ws, bs, want)
         xf = f32(x0, "x0")
         de = f32(d_enc, "d_enc") if rgb else None
         c = _ctx(xf, lib_ctx)
-        wd = [f32(w.detach(), "weight") for w in ws]
-        bd = [f32(b.detach(), "bias") for b in bs]
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        wd, bd = _detached(ws, bs)
         out = torch.empty(rows, 4, device=xf.device)
         tape = torch.empty(c.lib.neo_mip_mlp_train_tape_floats(width, depth, int(rgb), R, n), device=xf.device)
-        _lib.check(c.lib.neo_mip_mlp_train_forward(c.handle, width, depth, int(rgb), tab(wd), tab(bd), ptr(xf), ptr(de), R, n, ptr(tape),
-                                                   ptr(out), c.stream()))
+        _lib.check(c.lib.neo_mip_mlp_train_forward(c.handle, width, depth, int(rgb), ptr_table(wd), ptr_table(bd), ptr(xf), ptr(de), R, n,
+                                                   ptr(tape), ptr(out), c.stream()))
         ctx_.save_for_backward(xf, tape, out, *wd) if not rgb else ctx_.save_for_backward(xf, tape, out, *wd, de)
-        ctx_.meta = (c, width, depth, bool(rgb), R, n, [tuple(w.shape) for w in ws], [tuple(b.shape) for b in bs])
+        ctx_.meta = (c, width, depth, bool(rgb), R, n)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx_, g):
-        c, width, depth, rgb, R, n, wshapes, bshapes = ctx_.meta
-        saved = ctx_.saved_tensors
-        xf, tape, out = saved[:3]
-        wd = list(saved[3:3 + len(wshapes)])
-        de = saved[-1] if rgb else None
-        dev = xf.device
+        c, width, depth, rgb, R, n = ctx_.meta
+        xf, tape, out, *wd = ctx_.saved_tensors
+        de = wd.pop() if rgb else None
         g = f32(g.contiguous(), "g_rgbdens")
-        gw = [torch.zeros(s, device=dev) for s in wshapes]
-        gb = [torch.zeros(s, device=dev) for s in bshapes]
-        tab = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.check(c.lib.neo_mip_mlp_train_backward(c.handle, width, depth, int(rgb), tab(wd), ptr(xf), ptr(de), R, n, ptr(tape), ptr(out),
-                                                    ptr(g), tab(gw), tab(gb), c.stream()))
+        gw, gb = _zero_param_grads(wd)
+        _lib.check(c.lib.neo_mip_mlp_train_backward(c.handle, width, depth, int(rgb), ptr_table(wd), ptr(xf), ptr(de), R, n, ptr(tape),
+                                                    ptr(out), ptr(g), ptr_table(gw), ptr_table(gb), c.stream()))
         return (None, None, None, None, None, None, None, *gw, *gb)
 
 
@@ -1215,9 +1206,7 @@ def mip_mlp_fused(mlp, x0, d_enc, n, ctx=None):
     W, D = mlp.netwidth, len(mlp.pts_linear)
     if W % 64 or W > 1024 or D > 8 or ((D - 1) % 4 == 0 and D - 1 > 0):
         return mip_mlp(mlp, x0, d_enc, n, ctx=ctx)
-    layers = mlp.ordered_layers()
-    params = [l.weight for l in layers] + [l.bias for l in layers]
-    out = _MipTrainMLP.apply(ctx, W, D, not mlp.disable_rgb, n, x0, d_enc, *params)
+    out = _MipTrainMLP.apply(ctx, W, D, not mlp.disable_rgb, n, x0, d_enc, *_mlp_params(mlp))
     R = x0.shape[0] // n
     out = out.reshape(R, n, 4)
     return out[..., 3], out[..., :3]
