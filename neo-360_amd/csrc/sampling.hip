@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void k_composite(int mode, const float4* __res
                 delta = mode == 1 ? far - ti : 1e10f;
             }
             if (mode != 2) delta = delta * dnorm;
-            alpha = 1.0f - expf(-c.w * delta);
+            alpha = alpha_of(c.w * delta);
         }
         const float keep = valid ? (1.0f - alpha) + 1e-10f : 1.0f;
         // inclusive product scan in fp64

@@ -64,7 +64,7 @@ __global__ void k_tp_level0_rand(const float* __restrict__ far, const float* __r
 }
 
 // ---- compositing backward ---------------------------------------------------------------------------------------
-// Forward (sampling.hip:k_composite): delta_i, e_i = exp(-sigma_i delta_i), alpha_i = 1 - e_i, a_i = (1 - alpha_i) + 1e-10,
+// Forward (sampling.hip:k_composite): delta_i, e_i = exp(-sigma_i delta_i), alpha_i = 1 - e_i (common.h:alpha_of), a_i = (1 - alpha_i) + 1e-10,
 // T_i = prod_{j<=i} a_j, w_i = alpha_i T_{i-1}, acc = sum w, rgb = sum w c (+ 1 - acc), depth = sum w t, lambda = T_last.
 // With G_i = dL/dw_i = g_w_i + g_acc + g_rgb.(c_i - white) + g_depth t_i and S_i = sum_{k>i} G_k w_k:
 //   dL/dc_i = w_i g_rgb ;  dL/dsigma_i = delta_i e_i [ G_i T_{i-1} - (S_i + g_lambda T_last) / a_i ].
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(int mode, const float4* _
         if (valid) {
             ti = tr[i];
             c = cs[i];
-            alpha = 1.0f - expf(-c.w * delta_of(i, ti));
+            alpha = alpha_of(c.w * delta_of(i, ti));          // as k_composite: the transmittance must be the forward's, bit for bit
         }
         const float keep = valid ? (1.0f - alpha) + 1e-10f : 1.0f;
         double incl = (double)keep;
@@ -135,15 +135,16 @@ __global__ __launch_bounds__(256) void k_composite_bwd(int mode, const float4* _
     for (int rd = rounds - 1; rd >= 0; --rd) {
         const int i = rd * 64 + lane;
         const bool valid = i < N;
-        float ti = 0.f, delta = 0.f, e = 1.f, trans = 0.f, w = 0.f, G = 0.f;
+        float ti = 0.f, delta = 0.f, e = 1.f, alpha = 0.f, trans = 0.f, w = 0.f, G = 0.f;
         float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
         if (valid) {
             ti = tr[i];
             c = cs[i];
             delta = delta_of(i, ti);
-            e = expf(-c.w * delta);
+            e = expf(-c.w * delta);            // d alpha / d (sigma delta): wanted to an ulp of ITSELF (1e10 x e on a sentinel entry)
+            alpha = alpha_of(c.w * delta);     // the forward's alpha
             trans = s_T[wv][i];
-            w = (1.0f - e) * trans;
+            w = alpha * trans;
             G = s_G[wv][i];
         }
         const double v = (double)(G * w);
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(int mode, const float4* _
         const double S = suffix + (incl - v);  // strictly later samples
         suffix += __shfl(incl, 0, 64);
         if (valid) {
-            const float a = (1.0f - (1.0f - e)) + 1e-10f;
+            const float a = (1.0f - alpha) + 1e-10f;
             const float gs = delta * e * (G * trans - (float)((S + (double)gl * (double)T_last) / (double)a));
             g_out[(long)ray * N + i] = make_float4(w * gr, w * gg, w * gb, gs);
         }

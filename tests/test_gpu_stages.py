@@ -6,6 +6,7 @@ import torch
 
 import cases
 import oracle
+from alongray_cases import cdf_space
 from conftest import max_abs, record_parity
 from neo360_amd import ops, synth
 
@@ -113,22 +114,7 @@ def test_pos_enc(golden):
     assert max_abs(ops.pos_enc(x3.to(DEV), 0, 4).cpu(), g["pe3v"]) < 5e-7
 
 
-def _cdf_space(x, bins, w_inner):
-    """Evaluate the piecewise-linear CDF the sampler inverts (fp64) at positions x.
-    Sample POSITIONS are ill-conditioned where the density is ~0 (an ulp of the
-    cdf moves them by ulp/density), their CDF VALUES are not: stage parity of the
-    resampler is asserted in cdf space, plus in position space on well-conditioned rows."""
-    w = w_inner.double()
-    tot = w.sum(-1, keepdim=True)
-    pad = torch.clamp(1e-5 - tot, min=0)
-    w = w + pad / w.shape[-1]
-    pdf = w / (tot + pad)
-    cdf = torch.cat([torch.zeros_like(pdf[:, :1]), torch.cumsum(pdf[:, :-1], -1).clamp(max=1), torch.ones_like(pdf[:, :1])], -1)
-    b = bins.double()
-    out = torch.empty_like(x, dtype=torch.float64)
-    for r in range(x.shape[0]):
-        out[r] = torch.from_numpy(__import__("numpy").interp(x[r].double().numpy(), b[r].numpy(), cdf[r].numpy()))
-    return out
+_cdf_space = cdf_space      # the helper lives in the shared case table now (tests/alongray_cases.py)
 
 
 @pytest.mark.parametrize("desc", [False, True])
