@@ -577,6 +577,26 @@ int neo_mip_encode(neo_ctx* ctx, const float* rays_o, const float* rays_d, const
 int neo_mip_composite_backward(neo_ctx* ctx, const float* rgbdens, const float* tdist, const float* rays_d, int R, int n, float bg,
                                const float* g_weights, const float* g_rgb, float* g_rgbdens, void* stream);
 
+/* The regularisers of LitMipNeRF360.training_step (mipnerf360/model.py:444-449, :725-741) in linear time per ray.  t (R, N+1) and
+ * w (R, N) are the histogram whose loss is taken (the final level's for the interlevel loss), t_env (R, Ne+1) and w_env (R, Ne) a
+ * proposal level's; edges do not decrease along a row; 1 <= N, Ne <= 1024.  Inputs and outputs are fp32, every prefix sum,
+ * difference and quotient in between is fp64 and each output entry is rounded once; no atomics, results repeat bit for bit.
+ *
+ * neo_mip_lossfun_outer: helper.py:135-137 (lossfun_outer over inner_outer :116-131 and searchsorted :108-113):
+ * loss (R, N) = max(w - w_outer, 0)^2 / (w + eps), w_outer the envelope weight of the proposal bins a fine interval touches,
+ * eps = 1.1920929e-07 (helper.py:18).  The reference takes its mean per proposal level (model.py:733). */
+int neo_mip_lossfun_outer(neo_ctx* ctx, const float* t, const float* w, const float* t_env, const float* w_env, int R, int N, int Ne,
+                          float* loss, void* stream);
+/* Backward of neo_mip_lossfun_outer (autograd of helper.py:116-137 with respect to the two weight tensors): upstream g_loss (R, N)
+ * -> g_w (R, N), g_w_env (R, Ne); either may be NULL, not both.  The edges carry no gradient (it is zero almost everywhere). */
+int neo_mip_lossfun_outer_backward(neo_ctx* ctx, const float* t, const float* w, const float* t_env, const float* w_env,
+                                   const float* g_loss, int R, int N, int Ne, float* g_w, float* g_w_env, void* stream);
+/* helper.py:141-148 (lossfun_distortion): loss_rays (R) = sum_ij w_i w_j |u_i - u_j| + sum_i w_i^2 (t_{i+1} - t_i) / 3 with u the
+ * interval midpoints (the reference takes the mean over rays, model.py:740); grad_w (R, N), or NULL, = d loss_ray / d w.  No
+ * gradient with respect to the edges. */
+int neo_mip_lossfun_distortion(neo_ctx* ctx, const float* t, const float* w, int R, int N, float* loss_rays, float* grad_w,
+                               void* stream);
+
 /* MipNeRF360.forward(batch, train_frac, randomized=False, is_train=False, near, far)
  * (model.py:236-365), 3 levels (n_prop, n_prop, n_nerf samples).  Per level l (any pointer may be
  * NULL): rgb_l (R,3), sdist_l (R,n_l+1), weights_l (R,n_l), rgbdens_l (R,n_l,4) = per-interval

@@ -138,6 +138,42 @@ int neo_mip_composite_backward(neo_ctx* ctx, const float* rgbdens, const float* 
     return check_launch();
 }
 
+int neo_mip_lossfun_outer(neo_ctx* ctx, const float* t, const float* w, const float* t_env, const float* w_env, int R, int N, int Ne,
+                          float* loss, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && N >= 1 && N <= 1024 && Ne >= 1 && Ne <= 1024, "bad shape (1 <= N, Ne <= 1024)");
+    if (R == 0) return NEO_OK;
+    REQUIRE(t && w && t_env && w_env && loss, "null pointer");
+    ORDERED(ctx, static_cast<hipStream_t>(stream));
+    if (neo::launch_mip_lossfun_outer(t, w, t_env, w_env, R, N, Ne, loss, static_cast<hipStream_t>(stream)))
+        return fail(NEO_ERR_INVALID, "unsupported interval count");
+    return check_launch();
+}
+
+int neo_mip_lossfun_outer_backward(neo_ctx* ctx, const float* t, const float* w, const float* t_env, const float* w_env,
+                                   const float* g_loss, int R, int N, int Ne, float* g_w, float* g_w_env, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && N >= 1 && N <= 1024 && Ne >= 1 && Ne <= 1024, "bad shape (1 <= N, Ne <= 1024)");
+    if (R == 0) return NEO_OK;
+    REQUIRE(t && w && t_env && w_env && g_loss && (g_w || g_w_env), "null pointer");
+    ORDERED(ctx, static_cast<hipStream_t>(stream));
+    if (neo::launch_mip_lossfun_outer_bwd(t, w, t_env, w_env, g_loss, R, N, Ne, g_w, g_w_env, static_cast<hipStream_t>(stream)))
+        return fail(NEO_ERR_INVALID, "unsupported interval count");
+    return check_launch();
+}
+
+int neo_mip_lossfun_distortion(neo_ctx* ctx, const float* t, const float* w, int R, int N, float* loss_rays, float* grad_w,
+                               void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && N >= 1 && N <= 1024, "bad shape (1 <= N <= 1024)");
+    if (R == 0) return NEO_OK;
+    REQUIRE(t && w && loss_rays, "null pointer");
+    ORDERED(ctx, static_cast<hipStream_t>(stream));
+    if (neo::launch_mip_lossfun_distortion(t, w, R, N, loss_rays, grad_w, static_cast<hipStream_t>(stream)))
+        return fail(NEO_ERR_INVALID, "unsupported interval count");
+    return check_launch();
+}
+
 int neo_mip_mlp(neo_ctx* ctx, int slot, const float* rays_o, const float* rays_d, const float* viewdirs,
                 const float* radii, const float* tdist, int R, int n, float* out, void* stream) {
     ENTER(ctx);

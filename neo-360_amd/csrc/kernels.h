@@ -188,6 +188,16 @@ int launch_mip_resample(const float* s_prev, const float* w_prev, int n_prev, in
 void launch_mip_composite(const float* rgbdens, const float* tdist, const float* rays_d, int R, int n, float bg,
                           float* weights, float* rgb, hipStream_t s);
 
+// mip_losses.hip — Mip-NeRF 360's interlevel and distortion losses (helper.py:108-148), one wave per ray, fp64 between fp32 ends.
+// t (R,N+1) / w (R,N): the histogram whose loss is taken; t_env (R,Ne+1) / w_env (R,Ne): a proposal level's; edges non-decreasing.
+// loss (R,N); backward: g_loss (R,N) -> g_w (R,N), g_w_env (R,Ne), either may be null.  Return -1 outside 1 <= N, Ne <= 1024.
+int launch_mip_lossfun_outer(const float* t, const float* w, const float* t_env, const float* w_env, int R, int N, int Ne, float* loss,
+                             hipStream_t s);
+int launch_mip_lossfun_outer_bwd(const float* t, const float* w, const float* t_env, const float* w_env, const float* g_loss, int R, int N,
+                                 int Ne, float* g_w, float* g_w_env, hipStream_t s);
+// loss_rays (R) and, when not null, d loss_ray / d w (R,N)
+int launch_mip_lossfun_distortion(const float* t, const float* w, int R, int N, float* loss_rays, float* grad_w, hipStream_t s);
+
 // mlp_tp_h.hip — the NeO-360 evaluator on the fp16 matrix cores (hi/lo-split operands, fp32-equivalent)
 struct TpMlpHDev {
     const void* wpack;    // fp16 hi/lo fragments

@@ -3,6 +3,8 @@
   composite(...)        volumetric_rendering with a HIP backward (neo360/helper.py:128-171, vanilla :521-559)
   gather_features(...)  index_grid + get_local_feats as one op, backward = scatter-add into the feature maps
   eff_distloss(w, m, interval)   torch_efficient_distloss.eff_distloss (call site neo360/model.py:1246-1260)
+  lossfun_outer / lossfun_distortion   Mip-NeRF 360's interlevel and distortion losses (mipnerf360/helper.py:108-148), and
+                        mip_interlevel_loss / mip_distortion_loss / mip_training_loss over them (model.py:439-449, :725-741)
   rand_uniform / sample_level0 / resample_u   the randomized=True samplers on a counter-based generator
 
 The fused MLP evaluators are inference kernels: these ops cover the parts of the training step around them
@@ -1218,7 +1220,8 @@ def mip_render_train(module, batch, train_frac, randomized, near, far, seed=None
     softmax cdf, interval sampling; randomized = one jitter per ray, helper.py:358-365, drawn from the library's counter-based
     generator, stream = level), IPE rows (neo_mip_encode), the level's MLP on the linear-layer operators (mip_mlp: gradients
     to every parameter), compositing with a native backward (mip_composite: gradients arrive through the colour AND through
-    `weights`, which the interlevel / distortion losses of training_step read).  sdist is detached (stop_level_grad)."""
+    `weights`, which the interlevel / distortion losses of training_step read: mip_interlevel_loss / mip_distortion_loss /
+    mip_training_loss below).  sdist is detached (stop_level_grad)."""
     from . import ops
     rays_o, rays_d = f32(batch["rays_o"], "rays_o"), f32(batch["rays_d"], "rays_d")
     viewdirs, radii = f32(batch["viewdirs"], "viewdirs"), f32(batch["radii"], "radii")
@@ -1260,3 +1263,123 @@ def mip_render_train(module, batch, train_frac, randomized, near, far, seed=None
     module._raise_flags(c.poll_flags())
     return renderings, history
 
+
+# ---- Mip-NeRF 360: the regularisers of training_step (mipnerf360/helper.py:108-148, model.py:439-449, :725-741) -------------------
+def _no_edge_grad(x, name, what):
+    if isinstance(x, torch.Tensor) and x.requires_grad:
+        raise ValueError("%s: %s requires grad, and the gradient with respect to the edges is not implemented "
+                         "(mip_render_train returns a detached sdist: stop_level_grad); pass %s.detach()" % (what, name, name))
+
+
+class _LossfunOuter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx_, t, w, t_env, w_env, lib_ctx):
+        N, Ne = w.shape[-1], w_env.shape[-1]
+        if t.shape[-1] != N + 1 or t_env.shape[-1] != Ne + 1:
+            raise ValueError("t / t_env must hold one more entry per row than w / w_env, got %s %s %s %s"
+                             % (tuple(t.shape), tuple(w.shape), tuple(t_env.shape), tuple(w_env.shape)))
+        t2, w2 = f32(t, "t").reshape(-1, N + 1), f32(w, "w").reshape(-1, N)
+        te2, we2 = f32(t_env, "t_env").reshape(-1, Ne + 1), f32(w_env, "w_env").reshape(-1, Ne)
+        R = w2.shape[0]
+        if not (t2.shape[0] == te2.shape[0] == we2.shape[0] == R):
+            raise ValueError("t, w, t_env and w_env must hold the same rays")
+        c = _ctx(w2, lib_ctx)
+        loss = torch.empty(R, N, device=w2.device)
+        _lib.check(c.lib.neo_mip_lossfun_outer(c.handle, ptr(t2), ptr(w2), ptr(te2), ptr(we2), R, N, Ne, ptr(loss), c.stream()))
+        ctx_.save_for_backward(t2, w2, te2, we2)
+        ctx_.meta = (c, tuple(w.shape), tuple(w_env.shape))
+        return loss.reshape(w.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx_, g):
+        t2, w2, te2, we2 = ctx_.saved_tensors
+        c, w_shape, we_shape = ctx_.meta
+        need_w, need_we = ctx_.needs_input_grad[1], ctx_.needs_input_grad[3]
+        if not (need_w or need_we):
+            return (None,) * 5
+        (R, N), Ne = w2.shape, we2.shape[1]
+        g = f32(g.reshape(R, N).contiguous(), "grad")
+        g_w = torch.empty(R, N, device=w2.device) if need_w else None
+        g_we = torch.empty(R, Ne, device=w2.device) if need_we else None
+        _lib.check(c.lib.neo_mip_lossfun_outer_backward(c.handle, ptr(t2), ptr(w2), ptr(te2), ptr(we2), ptr(g), R, N, Ne, ptr(g_w), ptr(g_we),
+                                                        c.stream()))
+        return (None, g_w.reshape(w_shape) if need_w else None, None, g_we.reshape(we_shape) if need_we else None, None)
+
+
+def lossfun_outer(t, w, t_env, w_env, ctx=None):
+    """helper.lossfun_outer (mipnerf360/helper.py:135-137 over inner_outer :116-131): t (..., N+1) / w (..., N) the histogram whose
+    loss is taken, t_env (..., Ne+1) / w_env (..., Ne) the proposal histogram that should bound it -> (..., N)
+    max(w - w_outer, 0)^2 / (w + eps).  Native forward and backward in linear time per ray (neo_mip_lossfun_outer[_backward]);
+    gradients flow to w and w_env.  fp64 between the fp32 inputs and outputs: where the reference's fp32 autograd is
+    ill-conditioned (a difference of two fp32 cumulative sums divided by w + eps) this is closer to the reference's fp64 evaluation
+    than the reference's own fp32 run.  Raises ValueError if t or t_env requires grad: that gradient is zero almost everywhere,
+    and the training chain detaches the edges."""
+    _no_edge_grad(t, "t", "lossfun_outer")
+    _no_edge_grad(t_env, "t_env", "lossfun_outer")
+    return _LossfunOuter.apply(t, w, t_env, w_env, ctx)
+
+
+class _LossfunDistortion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx_, t, w, lib_ctx):
+        N = w.shape[-1]
+        if t.shape[-1] != N + 1:
+            raise ValueError("t must hold one more entry per row than w, got %s %s" % (tuple(t.shape), tuple(w.shape)))
+        t2, w2 = f32(t, "t").reshape(-1, N + 1), f32(w, "w").reshape(-1, N)
+        R = w2.shape[0]
+        if t2.shape[0] != R:
+            raise ValueError("t and w must hold the same rays")
+        c = _ctx(w2, lib_ctx)
+        loss = torch.empty(R, device=w2.device)
+        grad = torch.empty(R, N, device=w2.device) if ctx_.needs_input_grad[1] else None
+        _lib.check(c.lib.neo_mip_lossfun_distortion(c.handle, ptr(t2), ptr(w2), R, N, ptr(loss), ptr(grad), c.stream()))
+        if grad is not None:
+            ctx_.save_for_backward(grad)
+        ctx_.w_shape = tuple(w.shape)
+        return loss.reshape(w.shape[:-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx_, g):
+        (grad,) = ctx_.saved_tensors
+        return None, (grad * g.reshape(-1, 1)).reshape(ctx_.w_shape), None
+
+
+def lossfun_distortion(t, w, ctx=None):
+    """helper.lossfun_distortion (mipnerf360/helper.py:141-148): t (..., N+1) non-decreasing edges, w (..., N) -> (...,)
+    sum_ij w_i w_j |u_i - u_j| + sum_i w_i^2 (t_{i+1} - t_i) / 3, u the interval midpoints, from prefix sums in linear time
+    (neo_mip_lossfun_distortion, fp64 between the fp32 ends).  Gradient to w.  The reference's gradient with respect to t is NOT
+    implemented - mip_render_train returns a detached sdist - and a t that requires grad raises ValueError."""
+    _no_edge_grad(t, "t", "lossfun_distortion")
+    return _LossfunDistortion.apply(t, w, ctx)
+
+
+def mip_interlevel_loss(ray_history):
+    """LitMipNeRF360.interlevel_loss (model.py:725-734): the last level's histogram, detached, against every proposal level's;
+    the mean over all entries per level, summed over the levels."""
+    last = ray_history[-1]
+    c, w = last["sdist"].detach(), last["weights"].detach()
+    loss = 0.0
+    for level in ray_history[:-1]:
+        loss = loss + torch.mean(lossfun_outer(c, w, level["sdist"], level["weights"]))
+    return loss
+
+
+def mip_distortion_loss(ray_history):
+    """LitMipNeRF360.distortion_loss (model.py:736-741): the mean over rays of lossfun_distortion on the last level."""
+    last = ray_history[-1]
+    return torch.mean(lossfun_distortion(last["sdist"], last["weights"]))
+
+
+def mip_training_loss(renderings, ray_history, target, data_loss_mult=1.0, interlevel_loss_mult=1.0, distortion_loss_mult=0.01,
+                      charb_padding=0.001):
+    """The loss of LitMipNeRF360.training_step (model.py:439-449) on what mip_render_train returns: Charbonnier of the final
+    level's rgb mse + interlevel + distortion, with the reference's default multipliers.  Returns (loss, dict(rgb_mse, interlevel,
+    distortion)) - the terms before their multipliers."""
+    rgb_mse = torch.mean((renderings[-1]["rgb"] - target) ** 2)
+    interlevel = mip_interlevel_loss(ray_history)
+    distortion = mip_distortion_loss(ray_history)
+    loss = torch.sqrt(rgb_mse + charb_padding ** 2) * data_loss_mult
+    loss = loss + interlevel * interlevel_loss_mult + distortion * distortion_loss_mult
+    return loss, dict(rgb_mse=rgb_mse, interlevel=interlevel, distortion=distortion)
