@@ -255,7 +255,8 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d,
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).
  * weights/biases [host arrays of 9 device pointers], order: depth_fc.common_branch.0 (512x518), depth_fc.common_branch.2,
  * depth_fc.depth_encoder, pillar_aggregator_xz.0 (512x513), pillar_aggregator_xz.2 (1x512), pillar_aggregator_yz.0, .2,
- * pillar_aggregator_xy.0, .2. */
+ * pillar_aggregator_xy.0, .2.  Packs the fragments of both arithmetics (split fp16, and about 6 MB of fp32 fragments for
+ * the exact kernels), so neo_ctx_set_precision may change between calls without another upload. */
 int neo_enc_upload(neo_ctx* ctx, const float* const* weights, const float* const* biases, void* stream);
 
 /* GridEncoder.forward from the world grid to the inputs of its floor-plan conv nets (:472-578): for every cell of the
@@ -263,7 +264,9 @@ int neo_enc_upload(neo_ctx* ctx, const float* const* weights, const float* const
  * direction] -> depth_fc -> three axis scorers -> softmax along x / y / z -> weighted sums.  latent (NV,512,Hf,Wf) NCHW =
  * SpatialEncoder's output; src_poses [host] NV*16; focal / cx / cy = view 0's intrinsics (:491-493).  Outputs
  * channels-last: fp_yz (NV,G1,G2,512), fp_xz (NV,G0,G2,512), fp_xy (NV,G0,G1,512) (the reference permutes them to NCHW
- * for its conv nets, :580-592).  Split-fp16 arithmetic (neo_ctx_set_precision mode 1). */
+ * for its conv nets, :580-592).  Runs in the context's arithmetic (neo_ctx_set_precision): mode 1 = fp16 MFMA on hi/lo-split
+ * operands behind the range guard (a latent texel or a weight at or beyond 65504 raises flag bit 1; bit 2 as well when it
+ * is a weight); mode 0 = exact fp32 MFMA, no range check, no flag bit - what a caller whose guard tripped runs again. */
 int neo_enc_floorplans(neo_ctx* ctx, const float* latent, int NV, int Hf, int Wf, float image_w, float image_h,
                        const float* src_poses, float focal, float cx, float cy, int G0, int G1, int G2,
                        float* fp_yz, float* fp_xz, float* fp_xy, void* stream);
@@ -271,8 +274,9 @@ int neo_enc_floorplans(neo_ctx* ctx, const float* latent, int NV, int Hf, int Wf
 /* The pillar stage under autograd (GridEncoder trained as the reference trains it, models/neo360/model.py:697-820).
  * neo_enc_floorplans_train: neo_enc_floorplans with the activations the backward needs written to `tape`, a CALLER-owned
  * device buffer of neo_enc_train_tape_floats(NV, G0, G1, G2) floats = h1, h2, L (M x 512 each, M = NV G0 G1 G2 cell-views)
- * and the three score vectors (xz, yz, xy); same kernels, same split-fp16 arithmetic, same range guard and flags: the
- * floor-plans are bitwise those of neo_enc_floorplans.  At most 8,388,480 cell-views per call.
+ * and the three score vectors (xz, yz, xy); same kernels, same arithmetic (either mode), same range guard and flags: the
+ * floor-plans are bitwise those of neo_enc_floorplans in the same mode, and the tape layout does not depend on the mode.
+ * At most 8,388,480 cell-views per call.
  * neo_enc_floorplans_backward: exact fp32 MFMA.  w / b: the nine layers as fp32 device tensors in neo_enc_upload's order;
  * latent / geometry: the forward's arguments; tape: the forward's, only read (a second backward of the same tape gives the
  * same gradients); g_yz / g_xz / g_xy: gradients of the floor-plans, channels-last like the outputs; gw / gb [host arrays of
@@ -490,7 +494,8 @@ int neo_tp_render_train(neo_ctx* ctx, const float* rays_o, const float* rays_d, 
 /* Upload one NeRFMLP of model_pixel.py:35-94 (slot 0 = coarse_mlp, 1 = fine_mlp).  weights/biases
  * [host arrays of 9 device pointers], order: pts_linears.0..3 (128x575, 128x128 x3), views_linear.0
  * (128x155), views_linear.1 (128x128), bottleneck_layer, density_layer, rgb_layer (3x128).
- * This evaluator exists in the split-fp16 arithmetic only: neo_ctx_set_precision(ctx, 1). */
+ * Packs the fragments of both arithmetics (neo_ctx_set_precision): every evaluator of the library, the scene encoder's
+ * pillar stage included, has a split-fp16 and an exact-fp32 form. */
 int neo_pix_upload_mlp(neo_ctx* ctx, int slot, const float* const* weights,
                        const float* const* biases, void* stream);
 

@@ -34,6 +34,7 @@ EXTRA_FLAGS = {
     "mlp_tp_hpp.hip": _NO_PK_F32,
     "pillar.hip": _NO_PK_F32,        # built with packed ops it returned ~20 wrong rows of 786,432, differently on every run (r02)
     "pillar_train.hip": _NO_PK_F32,  # fp32 epilogue / gather VALU work next to the backward's MFMA stream
+    "pillar_f32.hip": _NO_PK_F32,    # pillar.hip's structure (gather / blend VALU work under the MFMA stream): same precaution
 }
 
 

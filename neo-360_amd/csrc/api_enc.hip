@@ -1,6 +1,7 @@
 // Scene-encoder entry points of the C ABI: the pillar stage of GridEncoder (SURVEY.md §8f row 1;
 // models/neo360/encoder_tp_fusion_conv.py:472-578) between the ResNet latent and the floor-plan conv nets.
 #include "ctx.h"
+#include "pillar_f32.h"
 #include "pillar_train.h"
 
 using namespace neo_host;
@@ -50,16 +51,25 @@ int enc_prepare(neo_ctx* ctx, const float* latent, int NV, int Hf, int Wf, float
     return NEO_OK;
 }
 
-// the split-fp16 forward: range guards, then launch_pillar with the activations in h1 / h2 / Lf / score
+// the forward in the context's arithmetic, with the activations in h1 / h2 / Lf / score.  Split fp16 (precision 1): range guards,
+// then launch_pillar; the latent is this call's input, not an uploaded map, so a trip on it does not carry the static bit.
+// Exact fp32 (precision 0): launch_pillar_f32, no range check, no flag bit.
 int enc_forward(neo_ctx* ctx, const neo::PillarGeom& gm, float* h1, float* h2, float* Lf, float* score, float* fp_yz, float* fp_xz,
                 float* fp_xy, hipStream_t s) {
     const long M = static_cast<long>(gm.nv) * gm.G0 * gm.G1 * gm.G2;
     MlpSlot& sl = ctx->enc;
-    guard_split_weights(sl, sl.wpack_h.p, neo::pillar_wpack_bytes(), ctx->flags, s);
-    neo::launch_f32_range_check(ctx->enc_latent.as<float>(), static_cast<size_t>(gm.nv) * 512 * gm.Hf * gm.Wf, 65504.0f, ctx->flags, s);
-    ctx->span_begin(s);
-    const int rc = neo::launch_pillar(gm, ctx->enc_latent.as<float>(), sl.wpack_h.p, sl.bias.as<float>(), sl.heads.as<float>(),
-                                      ctx->enc_head_b, h1, h2, Lf, score, ctx->flags, fp_yz, fp_xz, fp_xy, s);
+    int rc;
+    if (ctx->precision == 1) {
+        guard_split_weights(sl, sl.wpack_h.p, neo::pillar_wpack_bytes(), ctx->flags, s);
+        neo::launch_f32_input_range_check(ctx->enc_latent.as<float>(), static_cast<size_t>(gm.nv) * 512 * gm.Hf * gm.Wf, 65504.0f, ctx->flags, s);
+        ctx->span_begin(s);
+        rc = neo::launch_pillar(gm, ctx->enc_latent.as<float>(), sl.wpack_h.p, sl.bias.as<float>(), sl.heads.as<float>(),
+                                ctx->enc_head_b, h1, h2, Lf, score, ctx->flags, fp_yz, fp_xz, fp_xy, s);
+    } else {
+        ctx->span_begin(s);
+        rc = neo::launch_pillar_f32(gm, ctx->enc_latent.as<float>(), sl.wpack.as<float>(), sl.bias.as<float>(), sl.heads.as<float>(),
+                                    ctx->enc_head_b, h1, h2, Lf, score, fp_yz, fp_xz, fp_xy, s);
+    }
     // algorithmic MACs per cell-view: 518*512 + 2*512^2 + 3*(513*512 + 512) (encoder_tp_fusion_conv.py:263-279, :364-373)
     ctx->span_end(s, static_cast<double>(M), 2.0 * (518.0 * 512 + 2.0 * 512 * 512 + 3.0 * (513.0 * 512 + 512)));
     if (rc) return fail(NEO_ERR_INVALID, "unsupported grid");
@@ -78,12 +88,14 @@ int neo_enc_upload(neo_ctx* ctx, const float* const* weights, const float* const
     hipStream_t s = static_cast<hipStream_t>(stream);
     MlpSlot& sl = ctx->enc;
     if (sl.wpack_h.reserve(neo::pillar_wpack_bytes())) return NEO_ERR_NOMEM;
+    if (sl.wpack.reserve(neo::pillar_wpack_f32_bytes())) return NEO_ERR_NOMEM;       // the exact-fp32 twin's fragments
     if (sl.bias.reserve(6 * 512 * sizeof(float))) return NEO_ERR_NOMEM;
     if (sl.heads.reserve(3 * 512 * sizeof(float))) return NEO_ERR_NOMEM;
     // order: depth_fc.common_branch.0, .2, depth_fc.depth_encoder, then per axis (xz, yz, xy): aggregator .0, .2
     const float* hidden[6] = {weights[0], weights[1], weights[2], weights[3], weights[5], weights[7]};
     const float* hidden_b[6] = {biases[0], biases[1], biases[2], biases[3], biases[5], biases[7]};
     neo::launch_pillar_pack(hidden, sl.wpack_h.p, s);
+    neo::launch_pillar_pack_f32(hidden, sl.wpack.as<float>(), s);
     for (int i = 0; i < 6; ++i) neo::copy_floats(hidden_b[i], 512, sl.bias.as<float>() + 512 * i, s);
     for (int a = 0; a < 3; ++a) {
         neo::copy_floats(weights[4 + 2 * a], 512, sl.heads.as<float>() + 512 * a, s);
@@ -104,7 +116,6 @@ int neo_enc_floorplans(neo_ctx* ctx, const float* latent, int NV, int Hf, int Wf
     REQUIRE(latent && src_poses && fp_yz && fp_xz && fp_xy, "null pointer");
     if (const int rc = enc_check(NV, Hf, Wf, G0, G1, G2)) return rc;
     if (!ctx->enc.ready) return fail(NEO_ERR_STATE, "encoder weights not uploaded (neo_enc_upload)");
-    if (ctx->precision != 1) return fail(NEO_ERR_STATE, "the pillar stage exists in the split-fp16 arithmetic only (neo_ctx_set_precision(ctx, 1))");
     hipStream_t s = static_cast<hipStream_t>(stream);
     neo::PillarGeom gm;
     if (const int rc = enc_prepare(ctx, latent, NV, Hf, Wf, image_w, image_h, src_poses, focal, cx, cy, G0, G1, G2, s, gm)) return rc;
@@ -130,7 +141,6 @@ int neo_enc_floorplans_train(neo_ctx* ctx, const float* latent, int NV, int Hf, 
     if (const int rc = enc_check(NV, Hf, Wf, G0, G1, G2)) return rc;
     REQUIRE(static_cast<long>(NV) * G0 * G1 * G2 <= 65535L * 128, "at most 8,388,480 cell-views per call");
     if (!ctx->enc.ready) return fail(NEO_ERR_STATE, "encoder weights not uploaded (neo_enc_upload)");
-    if (ctx->precision != 1) return fail(NEO_ERR_STATE, "the pillar stage exists in the split-fp16 arithmetic only (neo_ctx_set_precision(ctx, 1))");
     hipStream_t s = static_cast<hipStream_t>(stream);
     neo::PillarGeom gm;
     if (const int rc = enc_prepare(ctx, latent, NV, Hf, Wf, image_w, image_h, src_poses, focal, cx, cy, G0, G1, G2, s, gm)) return rc;

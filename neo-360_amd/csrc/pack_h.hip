@@ -55,7 +55,7 @@ __global__ void k_half_range_check(const uint16_t* __restrict__ h, size_t n, uin
     if (bad) atomicOr(flags, FLAG_SPLIT_RANGE | FLAG_SPLIT_STATIC);
 }
 
-__global__ void k_f32_range_check(const float* __restrict__ x, size_t n4, size_t n, float limit, uint32_t* __restrict__ flags) {
+__global__ void k_f32_range_check(const float* __restrict__ x, size_t n4, size_t n, float limit, uint32_t* __restrict__ flags, uint32_t bits) {
     bool bad = false;
     const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
@@ -63,7 +63,7 @@ __global__ void k_f32_range_check(const float* __restrict__ x, size_t n4, size_t
         bad = bad || !(fabsf(v[0]) < limit) || !(fabsf(v[1]) < limit) || !(fabsf(v[2]) < limit) || !(fabsf(v[3]) < limit);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) bad |= !(fabsf(x[n4 * 4 + threadIdx.x]) < limit);
-    if (bad) atomicOr(flags, FLAG_SPLIT_RANGE | FLAG_SPLIT_STATIC);
+    if (bad) atomicOr(flags, bits);
 }
 
 // Bottleneck folded into the layer that consumes it (tp_hp_layout.h NEO_TP_FOLDB; the same algebra for the vanilla NeRFMLP,
@@ -108,10 +108,19 @@ void launch_half_range_check(const void* halves, size_t n, uint32_t* flags, hipS
                        reinterpret_cast<const uint16_t*>(halves), n, flags);
 }
 
-void launch_f32_range_check(const float* x, size_t n, float limit, uint32_t* flags, hipStream_t s) {
+static void f32_range_check(const float* x, size_t n, float limit, uint32_t* flags, hipStream_t s, bool static_operand) {
     if (n == 0) return;
     const size_t n4 = n / 4, blocks = (n4 + 255) / 256 + 1;
-    hipLaunchKernelGGL(k_f32_range_check, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, x, n4, n, limit, flags);
+    hipLaunchKernelGGL(k_f32_range_check, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, x, n4, n, limit, flags,
+                       static_operand ? FLAG_SPLIT_RANGE | FLAG_SPLIT_STATIC : FLAG_SPLIT_RANGE);
+}
+
+void launch_f32_range_check(const float* x, size_t n, float limit, uint32_t* flags, hipStream_t s) {
+    f32_range_check(x, n, limit, flags, s, true);
+}
+
+void launch_f32_input_range_check(const float* x, size_t n, float limit, uint32_t* flags, hipStream_t s) {
+    f32_range_check(x, n, limit, flags, s, false);
 }
 
 void pack_h_perm(const float* src, int ld, int rows, int KS, int nt0, const PackPerm& perm, _Float16* dst, hipStream_t s) {

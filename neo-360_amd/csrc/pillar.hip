@@ -16,6 +16,7 @@
 
 #include <cstdlib>
 
+#include "pillar_f32.h"
 #include "split_tile.h"
 #include "tp_common.h"
 
@@ -331,11 +332,17 @@ int launch_pillar(const PillarGeom& gm, const float* latent_cl, const void* wpac
     for (int a = 0; a < 3; ++a)
         hipLaunchKernelGGL((k_pillar_dense<2, 2>), dim3(tiles), dim3(512), lds, s, gm, nullptr, Lf, wp + stage_off_h8(3 + a),
                            bias + 1536 + 512 * a, head_w + 512 * a, head_b_host[a], coord[a], M, flags, nullptr, score + (long)a * M);
+    launch_pillar_aggregate(gm, Lf, score, fp_yz, fp_xz, fp_xy, s);
+    return 0;
+}
+
+void launch_pillar_aggregate(const PillarGeom& gm, const float* Lf, const float* score /* 3 x M: xz, yz, xy */, float* fp_yz,
+                             float* fp_xz, float* fp_xy, hipStream_t s) {
+    const long M = (long)gm.nv * gm.G0 * gm.G1 * gm.G2;
     // softmax along y -> xz plan, along x -> yz plan, along z -> xy plan
     hipLaunchKernelGGL((k_pillar_aggregate<1>), dim3((unsigned)(gm.nv * gm.G0 * gm.G2)), dim3(128), 0, s, gm.G0, gm.G1, gm.G2, Lf, score, fp_xz);
     hipLaunchKernelGGL((k_pillar_aggregate<0>), dim3((unsigned)(gm.nv * gm.G1 * gm.G2)), dim3(128), 0, s, gm.G0, gm.G1, gm.G2, Lf, score + M, fp_yz);
     hipLaunchKernelGGL((k_pillar_aggregate<2>), dim3((unsigned)(gm.nv * gm.G0 * gm.G1)), dim3(128), 0, s, gm.G0, gm.G1, gm.G2, Lf, score + 2 * M, fp_xy);
-    return 0;
 }
 
 }  // namespace neo

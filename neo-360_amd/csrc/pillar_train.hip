@@ -396,18 +396,22 @@ __global__ __launch_bounds__(1024) void k_tile_reduce(long tiles, const float* _
     }
 }
 
-// out[0] += sum x[0..n) in a fixed order (one workgroup)
+// out[0] += sum x[0..n) in a fixed order (one workgroup), accumulated in fp64.  What it sums are the g_s of one scorer, whose
+// exact sum is zero pillar by pillar (softmax shift invariance): in fp32 the partial sums over equal positions of ALL pillars
+// (~1e-3) cancelled only in the last additions, so the result was a small multiple of THEIR ulp (2^-35 on the z axis) and every
+// tenth call or so it came out as exactly 0.0 by chance; in fp64 it is the sum of the fp32 terms themselves - what their own
+// rounding left, ~1e-12 - and still the same bits on every run.
 __global__ __launch_bounds__(1024) void k_sum_fixed(long n, const float* __restrict__ x, float* __restrict__ out) {
-    __shared__ float red[1024];
-    float s = 0.0f;
-    for (long i = threadIdx.x; i < n; i += 1024) s += x[i];
+    __shared__ double red[1024];
+    double s = 0.0;
+    for (long i = threadIdx.x; i < n; i += 1024) s += (double)x[i];
     red[threadIdx.x] = s;
     __syncthreads();
     for (int o = 512; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[0] += red[0];
+    if (threadIdx.x == 0) out[0] += (float)red[0];
 }
 
 // x[m] = [bilinear latent (512) | cam xyz | masked dir] (pitch 518): the first layer's input as k_pillar_dense<0, *> forms it

@@ -6,20 +6,33 @@ focal, c)` -> (scene_grid_xz, scene_grid_xy, scene_grid_yz), same state_dict key
 
   spatial_encoder        the caller's image CNN (the reference's ResNet-34 SpatialEncoder): PyTorch, out of scope
   pillar stage           world grid -> per cell-view [latent | camera xyz | direction] -> depth_fc -> three axis scorers ->
-                         softmax-weighted sums = three floor-plans: ONE library call (csrc/pillar.hip), 1.58 MMAC per
-                         cell-view x 786,432 cell-views, the part the reference pays 300 x per frame
+                         softmax-weighted sums = three floor-plans: ONE library call, 1.58 MMAC per cell-view x 786,432
+                         cell-views, the part the reference pays 300 x per frame.  Two arithmetics, as on the renderers:
+                         "f16x3" (default; csrc/pillar.hip, fp16 MFMA on hi/lo-split operands) and "f32" (csrc/pillar_f32.hip,
+                         exact fp32 MFMA) - `precision` / $NEO360_PRECISION choose
   floorplan_convnet_*    the reference's 2-D conv stacks on 64 x 64 floor-plans: PyTorch (MIOpen), once per scene
 
 Attach it to `models.NeRF_TP(encoder=GridEncoder(spatial_encoder=...))`: the module runs it once per distinct src_imgs.
+The encoder's `precision` and `on_range` are its own: `NeRF_TP.precision` does not propagate to an attached encoder
+($NEO360_PRECISION sets both).
+
+Range guard: a latent texel or a pillar weight at or beyond 65504 cannot be split into fp16 planes.  `on_range = "retry_f32"`
+(default; the names are render.render_rays_test's): the same call runs again on the exact kernels into the same output and
+tape buffers, a RuntimeWarning says so once per module, `last_precision_used` names the arithmetic of the last call, and when
+the operand that left the range is a packed weight (`NeoRangeError.static_operand`) the module is latched to "f32" until its
+parameters change (`operands_key()`); a trip on the latent is per call and does not latch.  `on_range = "raise"`: the
+NeoRangeError goes to the caller.  An un-normalised encoder therefore never turns a frame into an exception.
 
 Training: with autograd on and a pillar parameter or the latent requiring grad, `forward` runs the pillar stage as a
-`torch.autograd.Function` (`_PillarStage`): the same split-fp16 forward kernels (bitwise the floor-plans of `floorplans`)
-writing their activations to a tape, and a native backward on exact fp32 MFMA (csrc/pillar_train.hip) that returns the
+`torch.autograd.Function` (`_PillarStage`): the same forward kernels in the same arithmetic (bitwise the floor-plans of
+`floorplans`) writing their activations to a tape, and a native backward on exact fp32 MFMA (csrc/pillar_train.hip) that returns the
 gradients of all nine depth_fc / pillar_aggregator layers (weights and biases) and of the latent.  `differentiable`
 (None = automatic, True / False = always / never) overrides the choice, as on the renderers.  No gradient reaches the poses,
 focal length or principal point (the reference's cameras are data).
 """
 import ctypes
+import os
+import warnings
 
 import torch
 import torch.nn as nn
@@ -78,10 +91,57 @@ class GridEncoder(_HipModule):
                   self.floorplan_convnet_yz, self.floorplan_convnet_xz):
             m.apply(_kaiming)
 
-    def _context(self, device):
+    # what a tripped range guard of the split arithmetic does: "retry_f32" = the call runs again on the exact fp32 kernels,
+    # "raise" = the NeoRangeError goes to the caller (the names of render.render_rays_test's argument)
+    on_range = "retry_f32"
+
+    def _wanted_precision(self):
+        return self.precision or os.environ.get("NEO360_PRECISION", self.default_precision)
+
+    def _context(self, device, exact=False):
+        """exact: this one call runs on the fp32 kernels whatever `precision` says (the next plain call sets it back)."""
         ctx = super()._context(device)
-        if getattr(ctx, "_precision", None) != "f16x3":
-            raise _lib.NeoError("the pillar stage exists in the split-fp16 arithmetic only (precision 'f16x3')")
+        if exact and ctx._precision != "f32":
+            ctx.set_precision("f32")
+            ctx._precision = "f32"
+        return ctx
+
+    def _run_pillar(self, device, call):
+        """One pillar-stage library call, `call(ctx)`, behind the range-guard policy of `on_range`; a retry calls it again with
+        the same buffers.  Returns the context the last call ran on."""
+        if self.on_range not in ("retry_f32", "raise"):
+            raise ValueError("on_range must be 'retry_f32' or 'raise', got %r" % (self.on_range,))
+        want = self._wanted_precision()
+        retry = self.on_range == "retry_f32" and want != "f32" and bool(self.poll_flags)
+        exact = False
+        if retry and self._range_latch is not None:
+            if self._range_latch == self.operands_key():
+                exact = True                 # the packed weights that tripped are still the ones in use: no failed attempt first
+            else:
+                self._range_latch = None     # parameters changed: the split arithmetic gets another chance
+        ctx = self._context(device, exact)
+        self._sync_weights(ctx)
+        call(ctx)
+        used = "f32" if exact else want
+        if self.poll_flags:
+            try:
+                self._raise_flags(ctx.poll_flags())
+            except _lib.NeoRangeError as err:
+                if not retry or exact:
+                    raise
+                if not getattr(self, "_warned_range_downgrade", False):
+                    self._warned_range_downgrade = True
+                    warnings.warn("%s: an operand of the pillar stage left the fp16 range of the split arithmetic (precision "
+                                  "'f16x3'); this call (and any later one that trips the guard) runs again on the exact fp32 "
+                                  "kernels (~2x slower). Set encoder.precision = 'f32' to skip the failed attempt."
+                                  % type(self).__name__, RuntimeWarning, stacklevel=3)
+                if getattr(err, "static_operand", False):
+                    self._range_latch = self.operands_key()
+                ctx = self._context(device, True)
+                call(ctx)
+                self._raise_flags(ctx.poll_flags())      # the exact kernels raise nothing: the word is clean for the next call
+                used = "f32"
+        self.last_precision_used = used
         return ctx
 
     def ordered_layers(self):
@@ -108,8 +168,6 @@ class GridEncoder(_HipModule):
         channels-last floor-plans (yz (NV,G1,G2,512), xz (NV,G0,G2,512), xy (NV,G0,G1,512))."""
         latent = f32(latent, "latent")
         dev = latent.device
-        ctx = self._context(dev)
-        self._sync_weights(ctx)
         NV, C, Hf, Wf = latent.shape
         if C != self.LATENT:
             raise _lib.NeoError("the pillar stage is specialised for the reference's 512-channel latent")
@@ -121,10 +179,9 @@ class GridEncoder(_HipModule):
         yz = torch.empty(NV, G1, G2, 512, device=dev)
         xz = torch.empty(NV, G0, G2, 512, device=dev)
         xy = torch.empty(NV, G0, G1, 512, device=dev)
-        _lib.check(ctx.lib.neo_enc_floorplans(ctx.handle, ptr(latent), NV, Hf, Wf, float(image_wh[0]), float(image_wh[1]),
-                                              host_poses, f0, cx, cy, G0, G1, G2, ptr(yz), ptr(xz), ptr(xy), ctx.stream()))
-        if self.poll_flags:
-            self._raise_flags(ctx.poll_flags())
+        self._run_pillar(dev, lambda ctx: _lib.check(ctx.lib.neo_enc_floorplans(
+            ctx.handle, ptr(latent), NV, Hf, Wf, float(image_wh[0]), float(image_wh[1]), host_poses, f0, cx, cy, G0, G1, G2,
+            ptr(yz), ptr(xz), ptr(xy), ctx.stream())))
         return yz, xz, xy
 
     def _pillar_params(self):
@@ -177,22 +234,19 @@ class _PillarStage(torch.autograd.Function):
         poses, focal, c, image_wh = cams
         latent32 = f32(latent.detach(), "latent")
         dev = latent32.device
-        ctx = enc._context(dev)
-        enc._sync_weights(ctx)
         NV, C, Hf, Wf = latent32.shape
         if C != enc.LATENT:
             raise _lib.NeoError("the pillar stage is specialised for the reference's 512-channel latent")
         G0, G1, G2 = enc.grid_size
         host_poses, f0, cx, cy = _camera_args(poses, focal, c)
-        tape = torch.empty(int(ctx.lib.neo_enc_train_tape_floats(NV, G0, G1, G2)), device=dev)
+        tape = torch.empty(int(_lib.load().neo_enc_train_tape_floats(NV, G0, G1, G2)), device=dev)
         yz = torch.empty(NV, G1, G2, 512, device=dev)
         xz = torch.empty(NV, G0, G2, 512, device=dev)
         xy = torch.empty(NV, G0, G1, 512, device=dev)
         geo = (NV, Hf, Wf, float(image_wh[0]), float(image_wh[1]))
-        _lib.check(ctx.lib.neo_enc_floorplans_train(ctx.handle, ptr(latent32), *geo, host_poses, f0, cx, cy, G0, G1, G2,
-                                                    ptr(tape), ptr(yz), ptr(xz), ptr(xy), ctx.stream()))
-        if enc.poll_flags:
-            enc._raise_flags(ctx.poll_flags())
+        # a retry after a tripped range guard rewrites the same tape and floor-plans; the tape layout is the same in both arithmetics
+        enc._run_pillar(dev, lambda ctx: _lib.check(ctx.lib.neo_enc_floorplans_train(
+            ctx.handle, ptr(latent32), *geo, host_poses, f0, cx, cy, G0, G1, G2, ptr(tape), ptr(yz), ptr(xz), ptr(xy), ctx.stream())))
         ctx_.enc, ctx_.tape = enc, tape
         ctx_.args = (geo, host_poses, f0, cx, cy, (G0, G1, G2))
         ctx_.save_for_backward(latent, *params)
