@@ -608,7 +608,10 @@ inline int split_k(int M, int N, long K) {
 // W (M x N, row pitch ldw) += Z^T X over K rows, db (M) += column sums of Z (null: a later segment of the same layer);
 // enough K slices for one resident wave of workgroups (2 per CU), each at least 1024 rows
 // part: DW_PART_FLOATS of scratch (the slices' partial tiles and bias sums)
-constexpr long DW_PART_TILES = 520;        // slices x tiles of one call: <= 512 + tiles - 1, tiles <= 8 (256 x 256: 4)
+constexpr long DW_PART_TILES = 520;        // slices x tiles of one call.  The slice rule below asks for <= 512 + tiles - 1 partial tiles, which fits
+                                           // while tiles <= 9; wider layers have more (the Mip-NeRF 360 chain: 1024 x 1024 = 64 tiles, the entry point's
+                                           // limits M <= 1024, N <= 4096: 256), and it is the clamp `nz * tiles > DW_PART_TILES` in dw_gemm that keeps
+                                           // the scratch in range: it leaves >= 520 / 256 = 2 slices (tests/test_train_matrix_cases_cpu.py)
 constexpr long DW_PART_FLOATS = DW_PART_TILES * (128 * 128 + 128);
 void dw_gemm(int M, int N, int K, const float* Z, long ldz, const float* X, long ldx, float* W, long ldw, float* db, float* part,
              hipStream_t s) {
