@@ -251,6 +251,26 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d,
                   float focal, float cx, float cy, int n_coarse, int n_fine, int white_bkgd,
                   const neo_tp_level_out* level0, const neo_tp_level_out* level1, void* stream);
 
+/* The same render with BACKGROUND CULLING (opt-in).  The composite is rgb = fg_rgb + bg_lambda * bg_rgb and depth = fg_depth +
+ * bg_lambda * bg_depth, bg_lambda being the foreground's final transmittance, and nothing in a ray's background half feeds
+ * its foreground half.  The foreground of BOTH levels is therefore finished first; a ray survives iff
+ * !(bg_lambda_0 < eps) || !(bg_lambda_1 < eps) (a NaN survives); the survivors are compacted in ascending ray order
+ * (deterministic) and background level 0, its resampling and background level 1 run on them only.
+ * Bound: bg_rgb is a sum of weights (<= 1 up to the 1e-10 terms of the transmittance product) times colours in
+ * (-0.001, 1.001), bg_depth a sum of weights times inverse radii in [0, 1]; dropping a ray's background changes its rgb by
+ * less than 1.002 * bg_lambda and its depth by less than 1.001 * bg_lambda, at either level (both lambdas are below eps).
+ * A surviving ray's six outputs per level are bitwise those of neo_tp_render (the quirk-Q1 direction index is taken from the
+ * ray's own index and R); a culled ray gets rgb = fg_rgb, bg_rgb = 0, depth = fg_depth at both levels; fg_rgb, fg_acc and
+ * bg_lambda are neo_tp_render's for every ray.  Sphere-miss assertions cover every ray.  A culled ray's background is not
+ * evaluated, so it takes no part in the fp16 range check of the split arithmetic either.
+ * eps in (0, 1).  survivors_out [device, may be NULL]: receives the number of surviving rays; the call never reads it on the
+ * host and synchronises nothing (the background launches are sized for R rays and take their row count from the device). */
+int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
+                         const float* viewdirs, int R, int chunk, const float* src_poses, int NV,
+                         float focal, float cx, float cy, int n_coarse, int n_fine, int white_bkgd,
+                         const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps,
+                         int* survivors_out, void* stream);
+
 /* ---- scene encoder: pillar stage -------------------------------------------------------- */
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).
  * weights/biases [host arrays of 9 device pointers], order: depth_fc.common_branch.0 (512x518), depth_fc.common_branch.2,
@@ -625,7 +645,8 @@ int neo_ctx_read_timing(neo_ctx* ctx, double* total_ms, int* launches, double* t
  * 1 k_tp_mlp_hp, 2 k_tp_mlp_hpp, 3 k_tp_mlp_h, 4 k_tp_mlp; Mip-NeRF 360: 5 proposal MLP (fused split evaluator), 6 NeRF MLP fused,
  * 7 NeRF MLP layer by layer - one span covers all batches of the call -, 8 exact fp32), points and algorithmic flops of each.  A NeO-360 frame is four
  * launches (inside / outside the sphere x coarse / fine) and, in pre-projection mode 3, two different kernels: the bench's
- * roofline object prices each kernel with ITS launches.  Arrays may be NULL; *count = launches recorded (may exceed capacity). */
+ * roofline object prices each kernel with ITS launches.  The two compact background launches of neo_tp_render_culled record
+ * points = flops = 0: how many rows they evaluated is known on the device only.  Arrays may be NULL; *count = launches recorded (may exceed capacity). */
 int neo_ctx_read_spans(neo_ctx* ctx, int capacity, double* ms, int* kernel_id, double* points, double* flops, int* count);
 
 #ifdef __cplusplus

@@ -54,7 +54,7 @@ int ensure_projections(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, bool p
 // one region's evaluator launch in the context's arithmetic mode
 int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
               const float* rays_d, const float* viewdirs, const float* tvals, const float* far, int R, int N, int chunk,
-              float* out, hipStream_t s) {
+              float* out, hipStream_t s, const int* cull_map = nullptr, const int* cull_count = nullptr) {
     ORDERED(ctx, s);      // context scratch (tp_dirsum, projected maps, ws[]) is shared by all streams
     const int slot_index = static_cast<int>(&sl - ctx->tp);
     // Patch shape of the ray-patch tile order (neo_ctx_set_ray_grid), per region - measured fabric-side bytes per full-frame launch
@@ -62,6 +62,11 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
     // neighbours of a ray are still in the XCD's 4 MB L2: 2 x 2 patches (59.8 -> 41.7 GB; 4 x 4: 45.3, 8 x 8: 51.5); outside, where
     // most taps are the zero-weight placeholder, 8 x 8 (11.6 -> 1.8 GB).  $NEO_TP_PATCH = "<log2 w>,<log2 h>" overrides both.
     neo::TpScene scp = sc;
+    if (cull_map) {       // compact launch (neo_tp_render_culled): rows are map[] entries, no pixel grid behind them
+        scp.cull_map = cull_map;
+        scp.cull_count = cull_count;
+        scp.grid_w = 0;
+    }
     if (scp.grid_w > 0) {
         static int epw = -2, eph = -2;
         if (epw == -2) {
@@ -133,7 +138,9 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
                            ctx->preproject ? sl.proj.as<float>() : nullptr, planes ? &pp : nullptr,
                            ctx->preproject ? ctx->tp_dirsum->as<float>() : nullptr);
     }
-    ctx->span_end(s, static_cast<double>(R) * N, tp_flop_per_point(sl.input_ch, sc.nv));
+    // a compact launch's row count exists on the device only: its span carries 0 points / 0 flops (duration and kernel id are
+    // real), so nothing derived from the spans prices rows that were never evaluated
+    ctx->span_end(s, cull_map ? 0.0 : static_cast<double>(R) * N, tp_flop_per_point(sl.input_ch, sc.nv));
     return NEO_OK;
 }
 
@@ -331,6 +338,98 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const 
             bg_s = bg_s1;
         }
     }
+    return check_launch();
+}
+
+
+int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                         const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                         int white_bkgd, const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps,
+                         int* survivors_out, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
+    REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
+    REQUIRE(eps > 0.0f && eps < 1.0f, "eps must lie in (0, 1)");
+    if (R == 0) {
+        if (survivors_out) HIP_TRY(hipMemsetAsync(survivors_out, 0, sizeof(int), static_cast<hipStream_t>(stream)));
+        return NEO_OK;
+    }
+    REQUIRE(rays_o && rays_d && viewdirs && src_poses, "null pointer");
+    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
+    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
+    for (int i = 0; i < 4; ++i)
+        if (!ctx->tp[i].ready) return fail(NEO_ERR_STATE, "NeRF_TP MLP slot %d has no weights", i);
+    REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3 && ctx->tp[2].input_ch == 4 && ctx->tp[3].input_ch == 4,
+            "slots 0,1 must be fg (input_ch 3), slots 2,3 bg (input_ch 4)");
+    (void)white_bkgd;  // as neo_tp_render
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
+    sc.grid_w = ctx->ray_grid_w;              // the foreground launches keep the ray-patch order; compact launches drop it (tp_launch)
+    sc.grid_first = ctx->ray_grid_first;
+
+    const int N0 = n_coarse + 1, N1 = N0 + n_fine;
+    const float near = 1e-4f;
+    const float* edges = ctx->get_edges(n_coarse, 0.0f, 1.0f, s);
+    const float* u = ctx->get_quantiles(n_fine, s);
+    if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
+
+    // workspaces: this lane's set, as neo_tp_render (W[0..9]); W[9] holds the per-ray foreground results of BOTH levels (they are
+    // merged only after the background has run) and the compact background results, W[10] the compaction's map / slot / count
+    ORDERED_LANE(ctx, s);
+    auto* W = ctx->ws;
+    const size_t r = static_cast<size_t>(R);
+    if (W[0].reserve(r * 4) || W[1].reserve(r * N0 * 4) || W[2].reserve(r * N0 * 4) || W[3].reserve(r * N1 * 16) ||
+        W[4].reserve(r * N1 * 16) || W[5].reserve(r * N0 * 4) || W[6].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) ||
+        W[8].reserve(r * N1 * 4) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)))
+        return NEO_ERR_NOMEM;
+    float* far = W[0].as<float>();
+    float* fg_t0 = W[1].as<float>();
+    float* bg_s0 = W[2].as<float>();      // the same row for every ray (k_tp_level0): its first `count` rows ARE the compact level-0 rows
+    float* fg_out = W[3].as<float>();
+    float* bg_out = W[4].as<float>();     // compact from here on: row k belongs to ray map[k]
+    float* fg_w0 = W[5].as<float>();
+    float* bg_w0 = W[6].as<float>();
+    float* fg_t1 = W[7].as<float>();
+    float* bg_s1 = W[8].as<float>();
+    float* scratch = W[9].as<float>();    // per level: fg_rgb(3) fg_depth fg_acc lambda bg_rgb(3) = 9 floats a ray; then compact bg_rgb(3) bg_depth, reused
+    float* c_bg_rgb = scratch + r * 18;
+    float* c_bg_depth = scratch + r * 21;
+    int* cws = W[10].as<int>();
+    const int* map = neo::cull_map_of(cws, R);
+    const int* slot = neo::cull_slot_of(cws, R);
+    const int* count = neo::cull_count_of(cws, R);
+
+    neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);       // sphere-miss assertions: every ray, culled or not
+    neo::launch_tp_level0(far, edges, R, N0, near, fg_t0, bg_s0, s);
+
+    struct LevelFg { float* fg_rgb; float* fg_depth; float* fg_acc; float* lam; float* bg_rgb; } L[2];
+    for (int level = 0; level < 2; ++level) {
+        const neo_tp_level_out* lo = level == 0 ? level0 : level1;
+        float* b = scratch + r * 9 * level;
+        L[level] = {(lo && lo->fg_rgb) ? lo->fg_rgb : b, b + r * 3, (lo && lo->fg_acc) ? lo->fg_acc : b + r * 4,
+                    (lo && lo->bg_lambda) ? lo->bg_lambda : b + r * 5, lo ? lo->bg_rgb : nullptr};
+    }
+    // foreground of both levels first: nothing in a ray's background half feeds its foreground half
+    if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, fg_t0, nullptr, R, N0, chunk, fg_out, s)) return rc;
+    neo::launch_composite(1, fg_out, fg_t0, N0, rays_d, far, R, N0, 0, L[0].fg_rgb, L[0].fg_acc, L[0].fg_depth, fg_w0, L[0].lam, s);
+    if (neo::launch_resample(fg_t0, N0, fg_w0, u, 0, R, N0, n_fine, 0, fg_t1, s)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    if (int rc = tp_launch(ctx, ctx->tp[1], sc, views, rays_o, rays_d, viewdirs, fg_t1, nullptr, R, N1, chunk, fg_out, s)) return rc;
+    neo::launch_composite(1, fg_out, fg_t1, N1, rays_d, far, R, N1, 0, L[1].fg_rgb, L[1].fg_acc, L[1].fg_depth, nullptr, L[1].lam, s);
+
+    neo::launch_cull_compact(L[0].lam, L[1].lam, R, eps, cws, survivors_out, s);
+
+    // background on the survivors: grids sized for R, every kernel takes its row count from the device word
+    if (int rc = tp_launch(ctx, ctx->tp[2], sc, views, rays_o, rays_d, viewdirs, bg_s0, far, R, N0, chunk, bg_out, s, map, count)) return rc;
+    neo::launch_composite(2, bg_out, bg_s0, N0, nullptr, nullptr, R, N0, 0, c_bg_rgb, nullptr, c_bg_depth, bg_w0, nullptr, s, count);
+    if (neo::launch_resample(bg_s0, N0, bg_w0, u, 0, R, N0, n_fine, 1, bg_s1, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    if (level0 && (level0->rgb || level0->depth || level0->bg_rgb))
+        neo::launch_tp_merge_culled(L[0].fg_rgb, L[0].fg_depth, L[0].lam, c_bg_rgb, c_bg_depth, slot, R, level0->rgb, level0->depth,
+                                    L[0].bg_rgb, s);
+    if (int rc = tp_launch(ctx, ctx->tp[3], sc, views, rays_o, rays_d, viewdirs, bg_s1, far, R, N1, chunk, bg_out, s, map, count)) return rc;
+    neo::launch_composite(2, bg_out, bg_s1, N1, nullptr, nullptr, R, N1, 0, c_bg_rgb, nullptr, c_bg_depth, nullptr, nullptr, s, count);
+    if (level1 && (level1->rgb || level1->depth || level1->bg_rgb))
+        neo::launch_tp_merge_culled(L[1].fg_rgb, L[1].fg_depth, L[1].lam, c_bg_rgb, c_bg_depth, slot, R, level1->rgb, level1->depth,
+                                    L[1].bg_rgb, s);
     return check_launch();
 }
 

@@ -22,14 +22,16 @@ void launch_sphere(const float* rays_o, const float* rays_d, int R, float* far, 
 
 // sampling.hip
 void launch_pos_enc(const float* x, int n, int C, int min_deg, int max_deg, float* out, hipStream_t s);
+// r_dev (composite, resample): null, or a device word holding the number of rows actually present (<= R): the grid is sized for R
+// and the surplus leaves early - compact arrays whose length the host never reads (cull.hip)
 // mode 0 vanilla, 1 NeO-360 inside sphere, 2 NeO-360 outside sphere.
 void launch_composite(int mode, const float* rgbsigma, const float* t, int t_row_stride, const float* rays_d,
                       const float* t_far, int R, int N, int white_bkgd, float* rgb, float* acc, float* depth, float* weights,
-                      float* lambda, hipStream_t s);
+                      float* lambda, hipStream_t s, const int* r_dev = nullptr);
 // u: n_new quantiles (device), see Ctx::quantiles; u_row_stride 0 = one row shared by all rays (randomized=False),
 // n_new = one row per ray (randomized=True: uniform draws)
 int launch_resample(const float* t_prev, int t_prev_stride, const float* weights, const float* u, int u_row_stride, int R,
-                    int n_prev, int n_new, int descending, float* t_out, hipStream_t s);
+                    int n_prev, int n_new, int descending, float* t_out, hipStream_t s, const int* r_dev = nullptr);
 
 // training.hip — training-side operators
 void launch_uniform(uint64_t seed, uint32_t stream, int rows, int cols, float* out, hipStream_t s);
@@ -119,6 +121,12 @@ struct TpScene {                     // channels-last feature maps owned by the 
     int grid_w = 0;
     long grid_first = 0;
     int grid_pw = 3, grid_ph = 3;   // log2 of the patch width / height in pixels (bands are 2^grid_ph image rows)
+    // Compact launch (neo_tp_render_culled, cull.hip): row g' of the launch stands for sample g' % N of ray cull_map[g' / N];
+    // tvals and the output are indexed by g', the rays' own arrays and the quirk-Q1 direction index by the ray and the
+    // launch's R.  The launch holds *cull_count rays (device word, never read on the host): the grid is sized for R and the
+    // surplus workgroups exit.  Null (every other caller): rows are the caller's rays.  grid_w must be 0 with a map.
+    const int* cull_map = nullptr;
+    const int* cull_count = nullptr;
 };
 struct TpViews {                     // world -> camera per source view (neo360/util.py:52-70)
     float rot[TP_MAX_VIEWS][9];     // c2w[:3,:3]^T, row-major
@@ -290,5 +298,18 @@ void launch_tp_level0(const float* far, const float* edges, int R, int N, float 
                       hipStream_t s);
 void launch_tp_merge(const float* fg_rgb, const float* fg_depth, const float* lambda, const float* bg_rgb,
                      const float* bg_depth, int R, float* rgb, float* depth, hipStream_t s);
+
+// cull.hip - background culling of neo_tp_render_culled: stable compaction of the rays whose foreground still lets light through
+size_t cull_ws_ints(int R);        // ints of workspace for R rays: [map R | slot R | count 1 | block totals]
+// keep[ray] = !(lam0 < eps) || !(lam1 < eps) (a NaN survives); map[k] = k-th kept ray (ascending), slot[ray] = k or -1, *count = kept
+// rays (also written to *count_out when not null).  Two launches, no atomics: the same map on every run.
+void launch_cull_compact(const float* lam0, const float* lam1, int R, float eps, int* ws, int* count_out, hipStream_t s);
+inline int* cull_map_of(int* ws, int R) { (void)R; return ws; }
+inline int* cull_slot_of(int* ws, int R) { return ws + R; }
+inline int* cull_count_of(int* ws, int R) { return ws + 2 * (size_t)R; }
+// merge of a culled render: survivors as launch_tp_merge from the COMPACT background rows bg_rgb_c / bg_depth_c at slot[ray];
+// a culled ray gets rgb = fg_rgb, depth = fg_depth; bg_rgb (R,3, may be null) receives the survivor's background or exactly 0
+void launch_tp_merge_culled(const float* fg_rgb, const float* fg_depth, const float* lambda, const float* bg_rgb_c,
+                            const float* bg_depth_c, const int* slot, int R, float* rgb, float* depth, float* bg_rgb, hipStream_t s);
 
 }  // namespace neo

@@ -157,7 +157,7 @@ __device__ __forceinline__ void gemm1(f32x16& acc, const f32x4* __restrict__ wp,
 #define NEO_TP_F32_WGS 2     // workgroups per CU the register budget is set for.  3 (<= 168 VGPRs, 43-48 spilled) measured: 180 k against
                              // 188 k rays/s (profiles/r05_exact_f32_experiments.log) - the kernel is phase-bound (MFMA busy 55 % at 2.38 GHz, 1.04 kW)
 #endif
-template <int PE_C, int PROJ>
+template <int PE_C, int PROJ, bool CULL = false>
 __global__ __launch_bounds__(256, NEO_TP_F32_WGS) void k_tp_mlp(TpMlpDev m, const float* __restrict__ proj, TpPlaneProj pp, TpScene sc, TpViews views,
                                                     const float* __restrict__ rays_o,
                                                     const float* __restrict__ rays_d,
@@ -179,8 +179,8 @@ __global__ __launch_bounds__(256, NEO_TP_F32_WGS) void k_tp_mlp(TpMlpDev m, cons
     LaneCtx L;
     L.init();
     int tid = threadIdx.x;
-    const long P = (long)R * N;
-    const long tile0 = tp::xcd_tile(blockIdx.x, (P + TM - 1) / TM) * TM;      // contiguous tile range per XCD (tp_common.h)
+    const long P = tp::launch_points<CULL>(sc, R, N);
+    const long tile0 = tp::xcd_tile<CULL>(blockIdx.x, (P + TM - 1) / TM) * TM;      // contiguous tile range per XCD (tp_common.h)
     if (tile0 >= P) return;       // surplus workgroup of the rounded-up grid (uniform exit before any barrier)
     const f32x4* wp = reinterpret_cast<const f32x4*>(m.wpack);
     constexpr int KCX = kc_x(PE_C);
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256, NEO_TP_F32_WGS) void k_tp_mlp(TpMlpDev m, cons
 #if NEO_TP32_TRACE
     unsigned long long tr_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #endif
-    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
+    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr);
     __syncthreads();
     if constexpr (FOLD) {
         // the view branch needs only the SUM over the views of each point's direction encoding, and that depends on the ray alone:
@@ -706,6 +706,12 @@ void launch_tp_mlp(int input_ch, const TpMlpDev& m, const TpScene& sc, const TpV
                        tvals, far, R, N, chunk, flags, o4, dirsum)
     if (input_ch == 3) {
         if (mode == 0) NEO_TP_F32_LAUNCH(3, 0); else if (mode == 1) NEO_TP_F32_LAUNCH(3, 1); else NEO_TP_F32_LAUNCH(3, 2);
+    } else if (sc.cull_map) {      // compact launch of the culled render: its own instantiations
+#define NEO_TP_F32_LAUNCH_CULL(PR)                                                                                                \
+    hipLaunchKernelGGL((k_tp_mlp<4, PR, true>), grid, dim3(256), lds, s, m, proj, planes, sc, views, rays_o, rays_d, viewdirs, \
+                       tvals, far, R, N, chunk, flags, o4, dirsum)
+        if (mode == 0) NEO_TP_F32_LAUNCH_CULL(0); else if (mode == 1) NEO_TP_F32_LAUNCH_CULL(1); else NEO_TP_F32_LAUNCH_CULL(2);
+#undef NEO_TP_F32_LAUNCH_CULL
     } else {
         if (mode == 0) NEO_TP_F32_LAUNCH(4, 0); else if (mode == 1) NEO_TP_F32_LAUNCH(4, 1); else NEO_TP_F32_LAUNCH(4, 2);
     }

@@ -44,7 +44,7 @@ __host__ __device__ constexpr int hpack_h8(int pe_c) { return hoff_v1(pe_c) + 2 
 constexpr int B_0 = 0, B_3 = 128, B_1 = 256, B_2 = 384, B_B = 512, B_V0 = 640, B_V1 = 704;
 constexpr int HD_DW = 0, HD_DB = 128, HD_RW = 132, HD_RB = 324;
 
-template <int PE_C>
+template <int PE_C, bool CULL = false>
 __global__ __launch_bounds__(256, NEO_GATHER_WAVES_PER_SIMD) void k_tp_mlp_h(TpMlpHDev m, TpScene sc, TpViews views,
                                                       const float* __restrict__ rays_o,
                                                       const float* __restrict__ rays_d,
@@ -68,14 +68,14 @@ __global__ __launch_bounds__(256, NEO_GATHER_WAVES_PER_SIMD) void k_tp_mlp_h(TpM
     LaneCtx L;
     L.init();
     int tid = threadIdx.x;
-    const long P = (long)R * N;
-    const long tile0 = tp::xcd_tile(blockIdx.x, (P + TM - 1) / TM) * TM;
+    const long P = tp::launch_points<CULL>(sc, R, N);
+    const long tile0 = tp::xcd_tile<CULL>(blockIdx.x, (P + TM - 1) / TM) * TM;
     if (tile0 >= P) return;       // surplus workgroup of the rounded-up grid (uniform exit before any barrier)
     const h8* wp = reinterpret_cast<const h8*>(m.wpack);
     constexpr int KSX = ks_x(PE_C);
     constexpr int NST = PE_C == 3 ? 11 : 12;   // streamed stages of 64 features: 8 local, 2 world, 1-2 pos_enc
 
-    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
+    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr);
     __syncthreads();
 
     // View means by linearity.  Everything after relu(L3_v) is linear up to the view mean: the density head acts on
@@ -406,6 +406,9 @@ void launch_tp_mlp_h(int input_ch, const TpMlpHDev& m, const TpScene& sc, const 
     const long tiles = tp::xcd_grid((P + TM - 1) / TM);
     if (input_ch == 3)
         hipLaunchKernelGGL(k_tp_mlp_h<3>, dim3((unsigned)tiles), dim3(256), lds, s, m, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out));
+    else if (sc.cull_map)      // compact launch of the culled render: its own instantiation
+        hipLaunchKernelGGL((k_tp_mlp_h<4, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out));
     else
         hipLaunchKernelGGL(k_tp_mlp_h<4>, dim3((unsigned)tiles), dim3(256), lds, s, m, sc, views, rays_o, rays_d,

@@ -63,7 +63,7 @@ namespace {
 using namespace hp;
 constexpr int RING = NEO_TP_RING;
 
-template <int PE_C>
+template <int PE_C, bool CULL = false>
 __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, const float* __restrict__ proj, TpScene sc,
                                                              TpViews views, const float* __restrict__ rays_o,
                                                              const float* __restrict__ rays_d,
@@ -95,8 +95,8 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
     LaneCtx L;
     L.init();
     int tid = threadIdx.x;
-    const long P = (long)R * N;
-    const long tile0 = tp::xcd_tile(blockIdx.x, (P + TM - 1) / TM) * TM;
+    const long P = tp::launch_points<CULL>(sc, R, N);
+    const long tile0 = tp::xcd_tile<CULL>(blockIdx.x, (P + TM - 1) / TM) * TM;
     if (tile0 >= P) return;       // surplus workgroup of the rounded-up grid (uniform exit before any barrier)
     const h8* wp = reinterpret_cast<const h8*>(m.wpack);
     constexpr int KSX = ks_x(PE_C);
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
 #if NEO_TP_TRACE
     unsigned long long tr_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #endif
-    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
+    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr);
     float* dens_w = smem + tp::OFF_DENSW;
     if (tid < 128) dens_w[tid] = m.heads[HD_DW + tid];
     // biases and head weights are read from LDS: an accumulator initialisation is on the critical path of every layer
@@ -802,10 +802,14 @@ void launch_tp_mlp_hp(int input_ch, const TpMlpHDev& m, const float* proj, const
     if (lds > 65536) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     const long tiles = tp::xcd_grid((P + TM - 1) / TM);
     if (input_ch == 3)
         hipLaunchKernelGGL(k_tp_mlp_hp<3>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
+    else if (sc.cull_map)      // compact launch of the culled render: its own instantiation
+        hipLaunchKernelGGL((k_tp_mlp_hp<4, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
     else
         hipLaunchKernelGGL(k_tp_mlp_hp<4>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,

@@ -81,7 +81,7 @@ static_assert(PP_LDS_WORDS * 4 <= 81920, "two workgroups per CU");
 
 struct TpPlaneBase { int texels[3]; };      // first texel of each projected tri-plane inside the one projected-maps buffer
 
-template <int PE_C>
+template <int PE_C, bool CULL = false>
 __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, const float* __restrict__ proj, TpPlaneBase plb,
                                                                TpScene sc, TpViews views, const float* __restrict__ rays_o,
                                                                const float* __restrict__ rays_d,
@@ -115,8 +115,8 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
     LaneCtx L;
     L.init();
     int tid = threadIdx.x;
-    const long P = (long)R * N;
-    const long tile0 = tp::xcd_tile(blockIdx.x, (P + TM - 1) / TM) * TM;
+    const long P = tp::launch_points<CULL>(sc, R, N);
+    const long tile0 = tp::xcd_tile<CULL>(blockIdx.x, (P + TM - 1) / TM) * TM;
     if (tile0 >= P) return;       // surplus workgroup of the rounded-up grid (uniform exit before any barrier)
     const h8* wp = reinterpret_cast<const h8*>(m.wpack);
     constexpr int KSX = ks_x(PE_C);              // k-steps per N-tile in the packed streamed stage: 8 world (unused here) + pos_enc
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
 #if NEO_TP_TRACE
     unsigned long long tr_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #endif
-    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
+    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr);
     float* dens_w = smem + PP_OFF_DENSW;
     if (tid < 128) dens_w[tid] = m.heads[HD_DW + tid];
     if (tid < DESC_BLOCK) {                            // the all-zero descriptor block (offset 0 = the buffer's first texel, weight 0)
@@ -643,11 +643,15 @@ void launch_tp_mlp_hpp(int input_ch, const TpMlpHDev& m, const float* proj_all, 
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
     const long tiles = tp::xcd_grid((P + TM - 1) / TM);
     if (input_ch == 3)
         hipLaunchKernelGGL(k_tp_mlp_hpp<3>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, pp, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), dirsum);
+    else if (sc.cull_map)      // compact launch of the culled render: its own instantiation
+        hipLaunchKernelGGL((k_tp_mlp_hpp<4, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, pp, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), dirsum);
     else
         hipLaunchKernelGGL(k_tp_mlp_hpp<4>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, pp, sc, views, rays_o, rays_d,

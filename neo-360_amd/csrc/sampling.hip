@@ -59,7 +59,9 @@ __global__ __launch_bounds__(256) void k_composite(int mode, const float4* __res
                                                    const float* __restrict__ t_far, int R, int N, int white_bkgd,
                                                    float* __restrict__ rgb_out, float* __restrict__ acc_out,
                                                    float* __restrict__ depth_out, float* __restrict__ w_out,
-                                                   float* __restrict__ lambda_out) {
+                                                   float* __restrict__ lambda_out,
+                                                   const int* __restrict__ r_dev) {
+    if (r_dev) R = *r_dev;       // compact arrays (cull.hip): the row count lives on the device, the grid covers the caller's rays
     const int ray = blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= R) return;
     const int lane = lane_id();
@@ -127,10 +129,10 @@ __global__ __launch_bounds__(256) void k_composite(int mode, const float4* __res
 void launch_composite(int mode, const float* rgbsigma, const float* t, int t_row_stride, const float* rays_d,
                       const float* t_far,
                       int R, int N, int white_bkgd, float* rgb, float* acc, float* depth, float* weights,
-                      float* lambda, hipStream_t s) {
+                      float* lambda, hipStream_t s, const int* r_dev) {
     hipLaunchKernelGGL(k_composite, dim3((R + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK), dim3(256), 0, s, mode,
                        (const float4*)rgbsigma, t, t_row_stride, rays_d, t_far, R, N, white_bkgd, rgb, acc, depth,
-                       weights, lambda);
+                       weights, lambda, r_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -152,7 +154,12 @@ template <int MAXB, int SORT_N>
 __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ t_prev, int t_prev_stride,
                                                   const float* __restrict__ weights,
                                                   const float* __restrict__ u_arr, int u_row_stride, int R, int n_prev,
-                                                  int n_new, int descending, float* __restrict__ t_out) {
+                                                  int n_new, int descending, float* __restrict__ t_out,
+                                                  const int* __restrict__ r_dev) {
+    if (r_dev) {                 // compact arrays (cull.hip): row count on the device; whole surplus workgroups leave before any barrier
+        R = *r_dev;
+        if ((int)(blockIdx.x * RAYS_PER_BLOCK) >= R) return;
+    }
     __shared__ float s_bins[RAYS_PER_BLOCK][MAXB];
     __shared__ float s_pmax[RAYS_PER_BLOCK][MAXB];
     __shared__ float s_smin[RAYS_PER_BLOCK][MAXB];
@@ -253,16 +260,16 @@ __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ t_pr
 }
 
 int launch_resample(const float* t_prev, int t_prev_stride, const float* weights, const float* u, int u_row_stride, int R,
-                    int n_prev, int n_new, int descending, float* t_out, hipStream_t s) {
+                    int n_prev, int n_new, int descending, float* t_out, hipStream_t s, const int* r_dev) {
     const int n_out = n_prev + n_new;
     const dim3 grid((R + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK), block(256);
     if (n_prev < 4 || n_prev - 1 > 256) return -1;
     if (n_out <= 256)
-        hipLaunchKernelGGL((k_resample<256, 256>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out);
+        hipLaunchKernelGGL((k_resample<256, 256>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev);
     else if (n_out <= 512)
-        hipLaunchKernelGGL((k_resample<256, 512>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out);
+        hipLaunchKernelGGL((k_resample<256, 512>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev);
     else if (n_out <= 1024)
-        hipLaunchKernelGGL((k_resample<256, 1024>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out);
+        hipLaunchKernelGGL((k_resample<256, 1024>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev);
     else
         return -1;
     return 0;

@@ -30,13 +30,22 @@ constexpr int LDS_WORDS = OFF_DENSW + 128;
 // samples that share feature texels, so each XCD is given a CONTIGUOUS range of tiles: workgroup b works on tile
 // (b % 8) * ceil(T / 8) + b / 8.  The launch rounds the grid up to a multiple of 8; surplus workgroups exit.
 constexpr int XCDS = 8;
+// COMPACT (the CULL instantiations only): the grid was sized for more tiles than the launch holds
+template <bool COMPACT = false>
 __device__ __forceinline__ long xcd_tile(unsigned bid, long tiles) {
 #ifdef NEO_NO_XCD_REMAP
     return bid;
 #else
     const long per = (tiles + XCDS - 1) / XCDS;
+    if (COMPACT && bid / XCDS >= per) return tiles;      // beyond this XCD's range of the compact launch: past the end
     return (long)(bid % XCDS) * per + bid / XCDS;
 #endif
+}
+// points of this launch: R * N, or - a compact launch (the evaluators' CULL instantiations, which every other launch stays clear of:
+// the default path's machine code is what it was before compact launches existed) - the device-side survivor count times N
+template <bool CULL>
+__device__ __forceinline__ long launch_points(const TpScene& sc, int R, int N) {
+    return (long)(CULL ? *sc.cull_count : R) * N;
 }
 inline long xcd_grid(long tiles) { return ((tiles + XCDS - 1) / XCDS) * XCDS; }
 
@@ -157,7 +166,8 @@ __device__ __forceinline__ void point_setup_row(const Scratch& S, int tid, long 
                                                 const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                 const float* __restrict__ viewdirs, const float* __restrict__ tvals,
                                                 const float* __restrict__ far_arr, uint32_t* __restrict__ flags,
-                                                bool t_shared = false, int grid_w = 0, long grid_first = 0, int pw = 3, int ph = 3) {
+                                                bool t_shared = false, int grid_w = 0, long grid_first = 0, int pw = 3, int ph = 3,
+                                                const int* __restrict__ cull_map = nullptr) {
     float* pe_world = S.pe_world;
     float* feat_world = S.feat_world;
     float* vdir_world = S.vdir_world;
@@ -165,8 +175,9 @@ __device__ __forceinline__ void point_setup_row(const Scratch& S, int tid, long 
         long g = tile0 + tid;
         if (g >= P) g = P - 1;
         g = patch_point(g, N, R, grid_w, grid_first, pw, ph);
-        const int ray = (int)(g / N);
-        const int s = (int)(g - (long)ray * N);
+        const int row = (int)(g / N);                            // ray of the launch: the row of tvals and of the output
+        const int s = (int)(g - (long)row * N);
+        const int ray = cull_map ? cull_map[row] : row;          // compact launch: the caller's ray behind that row
         const int c0 = (ray / chunk) * chunk;                    // first ray of this ray's reference chunk
         const int bc = min(chunk, R - c0);                       // rays in that chunk (last one may be short)
         const int gl = (ray - c0) * N + s;                       // flattened (ray, sample) index inside the chunk
@@ -231,9 +242,10 @@ __device__ __forceinline__ void point_setup(const Scratch& S, int tid, long tile
                                             const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                             const float* __restrict__ viewdirs, const float* __restrict__ tvals,
                                             const float* __restrict__ far_arr, uint32_t* __restrict__ flags,
-                                            bool t_shared = false, int grid_w = 0, long grid_first = 0, int pw = 3, int ph = 3) {
+                                            bool t_shared = false, int grid_w = 0, long grid_first = 0, int pw = 3, int ph = 3,
+                                            const int* __restrict__ cull_map = nullptr) {
     if (tid < TM)
-        point_setup_row<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, t_shared, grid_w, grid_first, pw, ph);
+        point_setup_row<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, t_shared, grid_w, grid_first, pw, ph, cull_map);
 }
 
 // ---- per-view descriptors (all 4 waves; lane = row) ---------------------------------------------------

@@ -452,6 +452,22 @@ class NeRF_TP(_HipModule):
         # 2: the tri-planes are pre-projected through the world columns as well (csrc/mlp_tp_hpp.hip): no world GEMM stage.
         # 3 (default): planes projected for the two outside-sphere MLPs only (measured best: profiles/r04_tp_hp_experiments.log).
         self.preproject = {"0": False, "1": True, "2": 2, "3": 3}.get(os.environ.get("NEO360_TP_PREPROJECT", "3"), 3)
+        # background culling of the deterministic out_depth=True call (neo_tp_render_culled): None = off (the default path,
+        # untouched); a float eps in (0, 1): rays whose foreground transmittance bg_lambda is below eps at BOTH levels skip the two
+        # background evaluations and return rgb = fg_rgb, bg_rgb = 0, depth = fg_depth (|rgb change| < 1.002 bg_lambda,
+        # |depth change| < 1.001 bg_lambda); every other ray is bitwise the un-culled result.  The training calls do not read it.
+        self.cull_background = None
+        self.last_cull_survivors = None      # int32 device tensor: rays of the last culled call that kept their background
+
+    @property
+    def cull_background(self):
+        return self._cull_background
+
+    @cull_background.setter
+    def cull_background(self, eps):
+        if eps is not None and not (isinstance(eps, float) and 0.0 < eps < 1.0):
+            raise ValueError("cull_background must be None or a float in (0, 1), got %r" % (eps,))
+        self._cull_background = eps
 
     def _context(self, device):
         ctx = super()._context(device)
@@ -698,6 +714,7 @@ class NeRF_TP(_HipModule):
         grid = getattr(self, "ray_grid", None)
         ctx.set_ray_grid(*(grid if grid and grid[0] % 8 == 0 and B >= 8 * grid[0] else (0, 0)))
         levels = []
+        eps = self.cull_background
 
         def launch():
             structs = []
@@ -707,16 +724,24 @@ class NeRF_TP(_HipModule):
                          bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
                 levels.append(t)
                 structs.append(_lib.TpLevelOut(*(t[k].data_ptr() for k in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth"))))
-            _lib.check(ctx.lib.neo_tp_render(
-                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), B, int(chunk or max(B, 1)), host_poses, NV, focal, cx, cy,
-                self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
-                ctypes.byref(structs[0]), ctypes.byref(structs[1]), ctx.stream()))
+            args = (ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), B, int(chunk or max(B, 1)), host_poses, NV, focal, cx, cy,
+                    self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
+                    ctypes.byref(structs[0]), ctypes.byref(structs[1]))
+            extra = []
+            if eps is None:
+                _lib.check(ctx.lib.neo_tp_render(*args, ctx.stream()))
+            else:
+                # the survivor count stays on the device: written by the compaction, never read inside the call
+                extra.append(torch.empty((), dtype=torch.int32, device=dev))
+                _lib.check(ctx.lib.neo_tp_render_culled(*args, eps, extra[0].data_ptr(), ctx.stream()))
             self._after_call(ctx)
-            return [v for t in levels for v in t.values()]
+            return [v for t in levels for v in t.values()] + extra
         try:
-            self._launch_overlapped(ctx, dev, raw, (rays_o, rays_d, viewdirs), launch)
+            made = self._launch_overlapped(ctx, dev, raw, (rays_o, rays_d, viewdirs), launch)
         finally:
             ctx.set_ray_grid(0)
+        if eps is not None:
+            self.last_cull_survivors = made[-1]
         return [(t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"]) for t in levels]
 
 
