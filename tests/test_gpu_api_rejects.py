@@ -205,3 +205,33 @@ def test_projected_forward_with_null_context_leaves_chain_mode_alone(env):
         chain = ctypes.c_int(-1)
         assert getattr(lib, name)(*_chain_args(env, name, ctx=None, chain_out=ctypes.byref(chain))) == INVALID
         assert lib.neo_last_error().decode() == NO_CTX and chain.value == -1
+
+
+VIEWS = "1..8 source views supported"
+
+
+def _view_count_args(env, entry, nv):
+    """Valid arguments of a scene, PixelNeRF-scene or encoder entry point (every pointer non-null) with NV = nv."""
+    b, h = env["buf"], env["bare"].handle
+    cams = [env["poses"], 50.0, 32.0, 24.0]
+    if entry == "neo_tp_set_scene":
+        return [h, b, b, b, nv, 128, 2, 2, b, 512, 2, 2, 64.0, 48.0, None]
+    if entry == "neo_pix_set_scene":
+        return [h, b, nv, 512, 2, 2, 64.0, 48.0, None]
+    geo = [b, nv, 2, 2, 64.0, 48.0] + cams + [1, 1, 1]
+    if entry == "neo_enc_floorplans":
+        return [h] + geo + [b, b, b, None]
+    if entry == "neo_enc_floorplans_train":
+        return [h] + geo + [b, b, b, b, None]
+    return [h, _table(env), _table(env)] + geo + [b, b, b, b, _table(env), _table(env), b, None]
+
+
+@pytest.mark.parametrize("nv", [0, 9])
+@pytest.mark.parametrize("entry", ["neo_tp_set_scene", "neo_pix_set_scene", "neo_enc_floorplans", "neo_enc_floorplans_train",
+                                   "neo_enc_floorplans_backward"])
+def test_view_count_limits(env, entry, nv):
+    """The library takes 1..8 source views: 0 and 9 are refused by the scene, PixelNeRF-scene and encoder entry points before
+    anything is launched (on a context without scenes or encoder weights: the view count is judged first)."""
+    lib = env["bare"].lib
+    assert getattr(lib, entry)(*_view_count_args(env, entry, nv)) == INVALID
+    assert lib.neo_last_error().decode() == VIEWS
