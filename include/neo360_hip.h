@@ -271,6 +271,28 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
                          const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps,
                          int* survivors_out, void* stream);
 
+/* OBJECT-LEVEL render of NeRF_TP (evaluation, randomized=False): the two inside-sphere MLPs (slots 0, 1; slots 2, 3 are not
+ * needed) are marched between a caller-given per-ray interval [near_obj, far_obj] (R floats each, device) - e.g. the output of
+ * neo_aabb_multi for all boxes of a scene or for one of them - only for the rays that have one.  No background, no sphere
+ * intersection and no sphere assertion.
+ * HIT RULE: lo = max(near_obj, 1e-4) (the reference's near, neo360/model.py:277; also for an origin inside a box, where the
+ * slab test gives tmin <= 0), hi = far_obj; a ray is a hit iff both bounds are finite and hi > lo.  The test is the negation of
+ * the failing comparisons, so a NaN bound makes the ray a miss; the reference's "0 = no hit" sentinel falls out of the rule.
+ * Hit rays, with the reference's own functions on the object interval: level 0 t = lo (1 - s) + hi s, s = linspace(0, 1,
+ * n_coarse + 1) (helper.py:36-42); the evaluators of neo_tp_render with the quirk-Q1 direction index taken from the ray's own
+ * index, R and `chunk` (a hit ray's result does not depend on which other rays hit); volumetric_rendering(in_sphere=True,
+ * t_far=far_obj, white_bkgd) (helper.py:128-171): rgb (+ 1 - acc when white_bkgd: honoured here, unlike neo_tp_render), acc =
+ * sum w, depth = sum w t; level 1 sample_pdf on the level-0 mids and weights[1:-1] with n_fine quantiles, sorted merge
+ * (helper.py:218-231).  Missed rays, both levels: rgb = white_bkgd ? 1 : 0, acc = 0, depth = 0, tvals row = 0.
+ * The hit rays are compacted in ascending ray order (deterministic, no atomics) and every kernel in between runs on compact rows.
+ * hits_out [device, may be NULL]: receives the number of hit rays; the call never reads it on the host and synchronises nothing
+ * (all launches are sized for R rays and take their row count from the device).  R == 0 zeroes hits_out and returns. */
+typedef struct { float* rgb; float* acc; float* depth; float* tvals; } neo_tp_object_out;   /* any may be NULL; tvals (R, N_level) */
+int neo_tp_render_objects(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs,
+                          const float* near_obj, const float* far_obj, int R, int chunk, const float* src_poses, int NV,
+                          float focal, float cx, float cy, int n_coarse, int n_fine, int white_bkgd,
+                          const neo_tp_object_out* level0, const neo_tp_object_out* level1, int* hits_out, void* stream);
+
 /* ---- scene encoder: pillar stage -------------------------------------------------------- */
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).
  * weights/biases [host arrays of 9 device pointers], order: depth_fc.common_branch.0 (512x518), depth_fc.common_branch.2,
@@ -645,8 +667,8 @@ int neo_ctx_read_timing(neo_ctx* ctx, double* total_ms, int* launches, double* t
  * 1 k_tp_mlp_hp, 2 k_tp_mlp_hpp, 3 k_tp_mlp_h, 4 k_tp_mlp; Mip-NeRF 360: 5 proposal MLP (fused split evaluator), 6 NeRF MLP fused,
  * 7 NeRF MLP layer by layer - one span covers all batches of the call -, 8 exact fp32), points and algorithmic flops of each.  A NeO-360 frame is four
  * launches (inside / outside the sphere x coarse / fine) and, in pre-projection mode 3, two different kernels: the bench's
- * roofline object prices each kernel with ITS launches.  The two compact background launches of neo_tp_render_culled record
- * points = flops = 0: how many rows they evaluated is known on the device only.  Arrays may be NULL; *count = launches recorded (may exceed capacity). */
+ * roofline object prices each kernel with ITS launches.  The two compact background launches of neo_tp_render_culled and the two
+ * compact launches of neo_tp_render_objects record points = flops = 0: how many rows they evaluated is known on the device only.  Arrays may be NULL; *count = launches recorded (may exceed capacity). */
 int neo_ctx_read_spans(neo_ctx* ctx, int capacity, double* ms, int* kernel_id, double* points, double* flops, int* count);
 
 #ifdef __cplusplus

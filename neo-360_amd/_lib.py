@@ -30,6 +30,10 @@ class TpLevelOut(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth")]
 
 
+class TpObjectOut(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("rgb", "acc", "depth", "tvals")]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares
 SIGNATURES = {
     "neo_abi_version": (_i, []),
@@ -65,6 +69,8 @@ SIGNATURES = {
                            ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), _vp]),
     "neo_tp_render_culled": (_i, [_vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,
                                   ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), _f, _vp, _vp]),
+    "neo_tp_render_objects": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,
+                                   ctypes.POINTER(TpObjectOut), ctypes.POINTER(TpObjectOut), _vp, _vp]),
     "neo_enc_upload": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_enc_floorplans": (_i, [_vp, _vp, _i, _i, _i, _f, _f, c_float_p, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "neo_enc_train_tape_floats": (ctypes.c_long, [_i, _i, _i, _i]),

@@ -62,7 +62,7 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
     // neighbours of a ray are still in the XCD's 4 MB L2: 2 x 2 patches (59.8 -> 41.7 GB; 4 x 4: 45.3, 8 x 8: 51.5); outside, where
     // most taps are the zero-weight placeholder, 8 x 8 (11.6 -> 1.8 GB).  $NEO_TP_PATCH = "<log2 w>,<log2 h>" overrides both.
     neo::TpScene scp = sc;
-    if (cull_map) {       // compact launch (neo_tp_render_culled): rows are map[] entries, no pixel grid behind them
+    if (cull_map) {       // compact launch (neo_tp_render_culled, neo_tp_render_objects): rows are map[] entries, no pixel grid behind them
         scp.cull_map = cull_map;
         scp.cull_count = cull_count;
         scp.grid_w = 0;
@@ -430,6 +430,74 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     if (level1 && (level1->rgb || level1->depth || level1->bg_rgb))
         neo::launch_tp_merge_culled(L[1].fg_rgb, L[1].fg_depth, L[1].lam, c_bg_rgb, c_bg_depth, slot, R, level1->rgb, level1->depth,
                                     L[1].bg_rgb, s);
+    return check_launch();
+}
+
+// Object-level render: the two inside-sphere MLPs between a caller-given per-ray interval, on the rays that have one.
+// Hit rule (objects.hip): lo = max(near_obj, 1e-4), hi = far_obj; hit iff both are finite and hi > lo, written as the negation of
+// the failing comparisons (a NaN bound is a miss; the reference's 0 = "no hit" sentinel is one).
+int neo_tp_render_objects(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_obj,
+                          const float* far_obj, int R, int chunk, const float* src_poses, int NV, float focal, float cx, float cy,
+                          int n_coarse, int n_fine, int white_bkgd, const neo_tp_object_out* level0,
+                          const neo_tp_object_out* level1, int* hits_out, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
+    REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
+    if (R == 0) {
+        if (hits_out) HIP_TRY(hipMemsetAsync(hits_out, 0, sizeof(int), static_cast<hipStream_t>(stream)));
+        return NEO_OK;
+    }
+    REQUIRE(rays_o && rays_d && viewdirs && src_poses && near_obj && far_obj, "null pointer");
+    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
+    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
+    for (int i = 0; i < 2; ++i)          // the outside-sphere slots 2, 3 are not needed
+        if (!ctx->tp[i].ready) return fail(NEO_ERR_STATE, "NeRF_TP MLP slot %d has no weights", i);
+    REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3, "slots 0,1 must be fg (input_ch 3)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);      // no ray-grid hint: every launch is compact
+
+    const int N0 = n_coarse + 1, N1 = N0 + n_fine;
+    const float* edges = ctx->get_edges(n_coarse, 0.0f, 1.0f, s);
+    const float* u = ctx->get_quantiles(n_fine, s);
+    if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
+
+    // workspaces: this lane's set.  Everything but the map is COMPACT (row k belongs to ray map[k]) and sized for R rows.
+    ORDERED_LANE(ctx, s);
+    auto* W = ctx->ws;
+    const size_t r = static_cast<size_t>(R);
+    if (W[0].reserve(r * 4) || W[1].reserve(r * N0 * 4) || W[2].reserve(r * 3 * 4) || W[3].reserve(r * N1 * 16) ||
+        W[5].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) || W[9].reserve(r * 10 * 4) ||
+        W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)))
+        return NEO_ERR_NOMEM;
+    float* far_c = W[0].as<float>();
+    float* t0_c = W[1].as<float>();
+    float* rays_d_c = W[2].as<float>();
+    float* out = W[3].as<float>();
+    float* w0 = W[5].as<float>();
+    float* t1_c = W[7].as<float>();
+    float* res = W[9].as<float>();        // per level: rgb(3) acc depth = 5 floats a row
+    int* cws = W[10].as<int>();
+    const int* map = neo::cull_map_of(cws, R);
+    const int* slot = neo::cull_slot_of(cws, R);
+    const int* count = neo::cull_count_of(cws, R);
+    float* c_rgb[2] = {res, res + r * 5};
+    float* c_acc[2] = {res + r * 3, res + r * 8};
+    float* c_depth[2] = {res + r * 4, res + r * 9};
+
+    neo::launch_obj_compact(near_obj, far_obj, R, cws, hits_out, s);
+    neo::launch_obj_level0(near_obj, far_obj, rays_d, edges, map, count, R, N0, t0_c, far_c, rays_d_c, s);
+    // grids sized for R, every kernel takes its row count from the device word
+    if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, t0_c, nullptr, R, N0, chunk, out, s, map, count)) return rc;
+    neo::launch_composite(1, out, t0_c, N0, rays_d_c, far_c, R, N0, white_bkgd ? 1 : 0, c_rgb[0], c_acc[0], c_depth[0], w0, nullptr, s, count);
+    if (neo::launch_resample(t0_c, N0, w0, u, 0, R, N0, n_fine, 0, t1_c, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    if (int rc = tp_launch(ctx, ctx->tp[1], sc, views, rays_o, rays_d, viewdirs, t1_c, nullptr, R, N1, chunk, out, s, map, count)) return rc;
+    neo::launch_composite(1, out, t1_c, N1, rays_d_c, far_c, R, N1, white_bkgd ? 1 : 0, c_rgb[1], c_acc[1], c_depth[1], nullptr, nullptr, s, count);
+    if (level0)
+        neo::launch_obj_scatter(slot, R, N0, c_rgb[0], c_acc[0], c_depth[0], t0_c, white_bkgd, level0->rgb, level0->acc, level0->depth,
+                                level0->tvals, s);
+    if (level1)
+        neo::launch_obj_scatter(slot, R, N1, c_rgb[1], c_acc[1], c_depth[1], t1_c, white_bkgd, level1->rgb, level1->acc, level1->depth,
+                                level1->tvals, s);
     return check_launch();
 }
 

@@ -3,7 +3,7 @@
 // transmittance is below eps at BOTH levels skip the two background evaluations.  This file holds the stable compaction of the
 // surviving rays and the merge that puts compact background rows back behind their rays.
 //
-// Compaction, two launches over workgroups of 256 rays (4 waves):
+// Compaction (the scheme of compact.h, shared with objects.hip), two launches over workgroups of 256 rays (4 waves):
 //   k_cull_totals : keep mask -> wave ballot + popcount -> one total per workgroup
 //   k_cull_emit   : every workgroup sums the totals in front of it (fixed order), recomputes its ballots and writes
 //                   map[k] = ray, slot[ray] = k or -1; the last workgroup writes the count
@@ -11,27 +11,25 @@
 // results are bitwise repeatable and their quirk-Q1 direction index depends on ray identity, not on the slot).  The count
 // stays on the device: the launches that consume compact arrays are sized for all R rays and read it there.
 #include "common.h"
+#include "compact.h"
 #include "kernels.h"
 
 namespace neo {
 
 namespace {
 
-constexpr int CULL_BLOCK = 256;
+constexpr int CULL_BLOCK = compact::BLOCK;
 
 // the negation of `<`, so that a NaN transmittance survives (and reaches the caller through the un-culled arithmetic)
 __device__ __forceinline__ bool cull_keep(const float* __restrict__ lam0, const float* __restrict__ lam1, int ray, int R, float eps) {
     return ray < R && (!(lam0[ray] < eps) || !(lam1[ray] < eps));
 }
 
+// the two launches of compact.h with this file's predicate
 __global__ __launch_bounds__(CULL_BLOCK) void k_cull_totals(const float* __restrict__ lam0, const float* __restrict__ lam1, int R,
                                                             float eps, int* __restrict__ totals) {
     __shared__ int s_wave[CULL_BLOCK / 64];
-    const int ray = blockIdx.x * CULL_BLOCK + threadIdx.x;
-    const unsigned long long ballot = __ballot(cull_keep(lam0, lam1, ray, R, eps));
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(ballot);
-    __syncthreads();
-    if (threadIdx.x == 0) totals[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    compact::totals_body([&](int ray) { return cull_keep(lam0, lam1, ray, R, eps); }, s_wave, totals);
 }
 
 __global__ __launch_bounds__(CULL_BLOCK) void k_cull_emit(const float* __restrict__ lam0, const float* __restrict__ lam1, int R,
@@ -40,29 +38,8 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_cull_emit(const float* __restric
                                                           int* __restrict__ count_out) {
     __shared__ int s_part[CULL_BLOCK / 64];
     __shared__ int s_wave[CULL_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    // survivors in front of this workgroup: integer sums, any order gives the same value
-    int part = 0;
-    for (int b = threadIdx.x; b < (int)blockIdx.x; b += CULL_BLOCK) part += totals[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-    const int ray = blockIdx.x * CULL_BLOCK + threadIdx.x;
-    const bool keep = cull_keep(lam0, lam1, ray, R, eps);
-    const unsigned long long ballot = __ballot(keep);
-    if (lane == 0) { s_part[wv] = part; s_wave[wv] = __popcll(ballot); }
-    __syncthreads();
-    int base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    for (int w = 0; w < wv; ++w) base += s_wave[w];
-    if (ray < R) {
-        const int k = base + __popcll(ballot & ((1ull << lane) - 1ull));
-        if (keep) map[k] = ray;
-        slot[ray] = keep ? k : -1;
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        const int n = s_part[0] + s_part[1] + s_part[2] + s_part[3] + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        *count = n;
-        if (count_out) *count_out = n;
-    }
+    compact::emit_body([&](int ray) { return cull_keep(lam0, lam1, ray, R, eps); }, R, totals, s_part, s_wave, map, slot, count,
+                       count_out);
 }
 
 __global__ void k_tp_merge_culled(const float* __restrict__ fg_rgb, const float* __restrict__ fg_depth,
@@ -91,7 +68,7 @@ __global__ void k_tp_merge_culled(const float* __restrict__ fg_rgb, const float*
     }
 }
 
-inline int cull_blocks(int R) { return (R + CULL_BLOCK - 1) / CULL_BLOCK; }
+inline int cull_blocks(int R) { return compact::blocks(R); }
 
 }  // namespace
 

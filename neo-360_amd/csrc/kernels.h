@@ -121,7 +121,7 @@ struct TpScene {                     // channels-last feature maps owned by the 
     int grid_w = 0;
     long grid_first = 0;
     int grid_pw = 3, grid_ph = 3;   // log2 of the patch width / height in pixels (bands are 2^grid_ph image rows)
-    // Compact launch (neo_tp_render_culled, cull.hip): row g' of the launch stands for sample g' % N of ray cull_map[g' / N];
+    // Compact launch (neo_tp_render_culled, cull.hip; neo_tp_render_objects, objects.hip): row g' of the launch stands for sample g' % N of ray cull_map[g' / N];
     // tvals and the output are indexed by g', the rays' own arrays and the quirk-Q1 direction index by the ray and the
     // launch's R.  The launch holds *cull_count rays (device word, never read on the host): the grid is sized for R and the
     // surplus workgroups exit.  Null (every other caller): rows are the caller's rays.  grid_w must be 0 with a map.
@@ -311,5 +311,18 @@ inline int* cull_count_of(int* ws, int R) { return ws + 2 * (size_t)R; }
 // a culled ray gets rgb = fg_rgb, depth = fg_depth; bg_rgb (R,3, may be null) receives the survivor's background or exactly 0
 void launch_tp_merge_culled(const float* fg_rgb, const float* fg_depth, const float* lambda, const float* bg_rgb_c,
                             const float* bg_depth_c, const int* slot, int R, float* rgb, float* depth, float* bg_rgb, hipStream_t s);
+
+// objects.hip - object render of neo_tp_render_objects: the rays with a box interval, compacted as above (same workspace layout:
+// cull_ws_ints / cull_map_of / cull_slot_of / cull_count_of)
+// hit[ray] = near_obj, far_obj finite && far_obj > max(near_obj, 1e-4), written as the negation of the failing comparisons (a NaN
+// bound is a miss); *count = hit rays (also written to *count_out when not null)
+void launch_obj_compact(const float* near_obj, const float* far_obj, int R, int* ws, int* count_out, hipStream_t s);
+// compact level-0 rows: t0_c (count, N) = lo (1 - e) + hi e, far_c (count) = hi, rays_d_c (count, 3); grid sized for R rows
+void launch_obj_level0(const float* near_obj, const float* far_obj, const float* rays_d, const float* edges, const int* map,
+                       const int* count, int R, int N, float* t0_c, float* far_c, float* rays_d_c, hipStream_t s);
+// hit rays copy compact rgb / acc / depth (and the t rows, (count, N)) to their ray; missed rays get rgb = white_bkgd ? 1 : 0,
+// acc = depth = 0 and a zero t row.  Any output may be null.
+void launch_obj_scatter(const int* slot, int R, int N, const float* rgb_c, const float* acc_c, const float* depth_c,
+                        const float* t_c, int white_bkgd, float* rgb, float* acc, float* depth, float* tvals, hipStream_t s);
 
 }  // namespace neo

@@ -704,17 +704,21 @@ void launch_tp_mlp(int input_ch, const TpMlpDev& m, const TpScene& sc, const TpV
 #define NEO_TP_F32_LAUNCH(C, PR)                                                                                          \
     hipLaunchKernelGGL((k_tp_mlp<C, PR>), grid, dim3(256), lds, s, m, proj, planes, sc, views, rays_o, rays_d, viewdirs, \
                        tvals, far, R, N, chunk, flags, o4, dirsum)
-    if (input_ch == 3) {
-        if (mode == 0) NEO_TP_F32_LAUNCH(3, 0); else if (mode == 1) NEO_TP_F32_LAUNCH(3, 1); else NEO_TP_F32_LAUNCH(3, 2);
-    } else if (sc.cull_map) {      // compact launch of the culled render: its own instantiations
-#define NEO_TP_F32_LAUNCH_CULL(PR)                                                                                                \
-    hipLaunchKernelGGL((k_tp_mlp<4, PR, true>), grid, dim3(256), lds, s, m, proj, planes, sc, views, rays_o, rays_d, viewdirs, \
+#define NEO_TP_F32_LAUNCH_CULL(C, PR)                                                                                             \
+    hipLaunchKernelGGL((k_tp_mlp<C, PR, true>), grid, dim3(256), lds, s, m, proj, planes, sc, views, rays_o, rays_d, viewdirs, \
                        tvals, far, R, N, chunk, flags, o4, dirsum)
-        if (mode == 0) NEO_TP_F32_LAUNCH_CULL(0); else if (mode == 1) NEO_TP_F32_LAUNCH_CULL(1); else NEO_TP_F32_LAUNCH_CULL(2);
-#undef NEO_TP_F32_LAUNCH_CULL
-    } else {
+    // every branch tests cull_map: a compact launch (culled background, object render) can never reach a non-compact kernel
+    // (the existing instantiations stay in their source order: their machine code depends on it, profiles/objects_isa.txt)
+    if (!sc.cull_map && input_ch == 3) {
+        if (mode == 0) NEO_TP_F32_LAUNCH(3, 0); else if (mode == 1) NEO_TP_F32_LAUNCH(3, 1); else NEO_TP_F32_LAUNCH(3, 2);
+    } else if (sc.cull_map && input_ch != 3) {      // compact launch of the culled render: its own instantiations
+        if (mode == 0) NEO_TP_F32_LAUNCH_CULL(4, 0); else if (mode == 1) NEO_TP_F32_LAUNCH_CULL(4, 1); else NEO_TP_F32_LAUNCH_CULL(4, 2);
+    } else if (!sc.cull_map) {
         if (mode == 0) NEO_TP_F32_LAUNCH(4, 0); else if (mode == 1) NEO_TP_F32_LAUNCH(4, 1); else NEO_TP_F32_LAUNCH(4, 2);
+    } else {                                         // compact launch of the object render
+        if (mode == 0) NEO_TP_F32_LAUNCH_CULL(3, 0); else if (mode == 1) NEO_TP_F32_LAUNCH_CULL(3, 1); else NEO_TP_F32_LAUNCH_CULL(3, 2);
     }
+#undef NEO_TP_F32_LAUNCH_CULL
 #undef NEO_TP_F32_LAUNCH
 }
 

@@ -803,16 +803,22 @@ void launch_tp_mlp_hp(int input_ch, const TpMlpHDev& m, const float* proj, const
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     const long tiles = tp::xcd_grid((P + TM - 1) / TM);
-    if (input_ch == 3)
+    // every branch tests cull_map: a compact launch (culled background, object render) can never reach a non-compact kernel
+    // (the existing instantiations stay in their source order: their machine code depends on it, profiles/objects_isa.txt)
+    if (!sc.cull_map && input_ch == 3)
         hipLaunchKernelGGL(k_tp_mlp_hp<3>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
-    else if (sc.cull_map)      // compact launch of the culled render: its own instantiation
+    else if (sc.cull_map && input_ch != 3)      // compact launch of the culled render: its own instantiation
         hipLaunchKernelGGL((k_tp_mlp_hp<4, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
-    else
+    else if (!sc.cull_map)
         hipLaunchKernelGGL(k_tp_mlp_hp<4>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
+    else                                         // compact launch of the object render
+        hipLaunchKernelGGL((k_tp_mlp_hp<3, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
 }
 

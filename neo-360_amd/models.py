@@ -458,6 +458,7 @@ class NeRF_TP(_HipModule):
         # |depth change| < 1.001 bg_lambda); every other ray is bitwise the un-culled result.  The training calls do not read it.
         self.cull_background = None
         self.last_cull_survivors = None      # int32 device tensor: rays of the last culled call that kept their background
+        self.last_object_hits = None         # int32 device tensor: rays of the last render_objects call that had a box interval
 
     @property
     def cull_background(self):
@@ -743,6 +744,77 @@ class NeRF_TP(_HipModule):
         if eps is not None:
             self.last_cull_survivors = made[-1]
         return [(t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"]) for t in levels]
+
+    @staticmethod
+    def _object_bound(rays, given, key, B):
+        t = given if given is not None else (rays.get(key) if hasattr(rays, "get") else None)
+        if t is None:
+            raise ValueError("render_objects needs %s: pass it or put it into the batch as rays[%r]" % (key, key))
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise ValueError("%s must be a floating-point tensor, got %r" % (key, type(t).__name__ if not isinstance(t, torch.Tensor) else t.dtype))
+        if tuple(t.shape) not in ((B,), (B, 1)):
+            raise ValueError("%s must have shape (%d,) or (%d, 1) like the rays, got %s" % (key, B, B, tuple(t.shape)))
+        return t
+
+    @torch.no_grad()
+    def render_objects(self, rays, near_obj=None, far_obj=None, white_bkgd=True, chunk=None, return_samples=False):
+        """Object-level evaluation render (neo_tp_render_objects): the two foreground MLPs marched between a per-ray interval
+        [near_obj, far_obj] - what `ops.sample_rays_in_bbox` returns for all boxes of a scene, or for one of them - only for the
+        rays that have one.  Deterministic (randomized=False), no background, no unit-sphere intersection or assertion.
+
+        Bounds default to rays["near_obj"] / rays["far_obj"] (the reference's batch keys, datasets/nerds360_ae.py:869-872); shape
+        (B,) or (B, 1), any float dtype, on the rays' device.  Hit rule: lo = max(near_obj, 1e-4), hi = far_obj; a ray is a hit
+        iff both are finite and hi > lo (a NaN bound is a miss, and so is the reference's 0 = "no hit" sentinel).
+        Returns [(rgb (B,3), acc (B,), depth (B,))] for the two levels; with return_samples also (t0 (B, n_coarse+1),
+        t1 (B, n_coarse+1+n_fine)), the sample rows of the hit rays.  Missed rays: rgb = 1 if white_bkgd else 0, acc = depth = 0,
+        zero sample rows.  `chunk` as in forward (quirk Q1: a ray's direction index comes from its own index, B and chunk, never
+        from which other rays hit).  `last_object_hits` receives the number of hit rays as a device int32 scalar that this call
+        never reads.  Reads neither `cull_background` nor `ray_grid`."""
+        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
+        B = raw[0].shape[0]
+        raw_near = self._object_bound(rays, near_obj, "near_obj", B)
+        raw_far = self._object_bound(rays, far_obj, "far_obj", B)
+        rays_o = f32(raw[0], "rays_o")
+        rays_d = f32(raw[1], "rays_d")
+        viewdirs = f32(raw[2], "viewdirs")
+        near_c = f32(raw_near, "near_obj").reshape(B)
+        far_c = f32(raw_far, "far_obj").reshape(B)
+        dev = rays_o.device
+        if near_c.device != dev or far_c.device != dev:
+            raise ValueError("near_obj / far_obj must be on the rays' device (%s)" % (dev,))
+        ctx = self._context(dev)
+        self._ensure_scene(rays, dev)
+        if self._scene_ctx is not ctx:
+            raise _lib.NeoError("scene features were uploaded on a different device")
+        self._sync_weights(ctx)
+        self._before_call(ctx)
+        host_poses, NV, focal, cx, cy = self._camera_args(rays)
+        n0 = self.num_coarse_samples + 1
+        n1 = n0 + self.num_fine_samples
+        levels = []
+
+        def launch():
+            structs = []
+            for n in (n0, n1):
+                t = dict(rgb=torch.empty(B, 3, device=dev), acc=torch.empty(B, device=dev), depth=torch.empty(B, device=dev))
+                if return_samples:
+                    t["tvals"] = torch.empty(B, n, device=dev)
+                levels.append(t)
+                structs.append(_lib.TpObjectOut(t["rgb"].data_ptr(), t["acc"].data_ptr(), t["depth"].data_ptr(),
+                                                t["tvals"].data_ptr() if return_samples else None))
+            hits = torch.empty((), dtype=torch.int32, device=dev)     # written by the compaction, never read inside the call
+            _lib.check(ctx.lib.neo_tp_render_objects(
+                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(near_c), ptr(far_c), B, int(chunk or max(B, 1)), host_poses,
+                NV, focal, cx, cy, self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
+                ctypes.byref(structs[0]), ctypes.byref(structs[1]), hits.data_ptr(), ctx.stream()))
+            self._after_call(ctx)
+            return [v for t in levels for v in t.values()] + [hits]
+        made = self._launch_overlapped(ctx, dev, raw + (raw_near, raw_far), (rays_o, rays_d, viewdirs, near_c, far_c), launch)
+        self.last_object_hits = made[-1]
+        out = [(t["rgb"], t["acc"], t["depth"]) for t in levels]
+        if return_samples:
+            out.append((levels[0]["tvals"], levels[1]["tvals"]))
+        return out
 
 
 class PixelNeRFMLP(nn.Module):

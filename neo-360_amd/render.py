@@ -46,15 +46,55 @@ def _render_once(model, batch, chunk, white_bkgd, near, far, train_frac):
     raise TypeError("unsupported renderer %r" % type(model))
 
 
-def _render_exact(model, batch, chunk, white_bkgd, near, far, train_frac):
+def _render_exact(model, once):
     prev = model.precision
     model.precision = "f32"
     try:
-        out = _render_once(model, batch, chunk, white_bkgd, near, far, train_frac)
+        out = once()
         model.check_flags()
     finally:
         model.precision = prev
     out["precision_used"] = "f32"
+    return out
+
+
+def _render_guarded(model, batch, once, check, on_range):
+    """One frame through `once()` (a callable that renders it once in the module's current arithmetic and returns the output
+    dict) with the range-guard retry and latch of render_rays_test / render_object_rays (documented there); `target` /
+    `instance_mask` of the batch are passed through."""
+    if on_range not in ("retry_f32", "raise"):
+        raise ValueError("on_range must be 'retry_f32' or 'raise', got %r" % (on_range,))
+    latch = getattr(model, "_range_latch", None)
+    if latch is not None and on_range == "retry_f32" and check and (model.precision or model.default_precision) != "f32":
+        if latch == model.operands_key():
+            out = _render_exact(model, once)
+            model.last_precision_used = "f32"
+            for k in ("target", "instance_mask"):
+                if k in batch:
+                    out[k] = batch[k]
+            return out
+        model._range_latch = None          # weights or scene changed: the split arithmetic gets another chance
+    out = once()
+    model.last_precision_used = model.precision or model.default_precision
+    if check:
+        try:
+            model.check_flags()      # the deferred reads of the assertion word: raise before the frame is handed out
+        except _lib.NeoRangeError as err:
+            if on_range != "retry_f32":
+                raise
+            if not getattr(model, "_warned_range_downgrade", False):
+                model._warned_range_downgrade = True
+                warnings.warn("%s: an operand left the fp16 range of the split arithmetic (precision 'f16x3'); this frame "
+                              "(and any later one that trips the guard) is re-rendered on the exact fp32 kernels "
+                              "(~3-6x slower). Set model.precision = 'f32' to skip the failed attempt."
+                              % type(model).__name__, RuntimeWarning, stacklevel=3)
+            if getattr(err, "static_operand", False):
+                model._range_latch = model.operands_key()
+            out = _render_exact(model, once)
+            model.last_precision_used = "f32"
+    for k in ("target", "instance_mask"):
+        if k in batch:
+            out[k] = batch[k]
     return out
 
 
@@ -89,38 +129,23 @@ def render_rays_test(model, batch, chunk=1024, white_bkgd=False, near=0.2, far=3
             return render_rays_test(model, batch, chunk, white_bkgd, near, far, train_frac, check, on_range)
         finally:
             model.ray_grid = prev_grid
-    latch = getattr(model, "_range_latch", None)
-    if latch is not None and on_range == "retry_f32" and check and (model.precision or model.default_precision) != "f32":
-        if latch == model.operands_key():
-            out = _render_exact(model, batch, chunk, white_bkgd, near, far, train_frac)
-            model.last_precision_used = "f32"
-            for k in ("target", "instance_mask"):
-                if k in batch:
-                    out[k] = batch[k]
-            return out
-        model._range_latch = None          # weights or scene changed: the split arithmetic gets another chance
-    out = _render_once(model, batch, chunk, white_bkgd, near, far, train_frac)
-    model.last_precision_used = model.precision or model.default_precision
-    if check:
-        try:
-            model.check_flags()      # the deferred reads of the assertion word: raise before the frame is handed out
-        except _lib.NeoRangeError as err:
-            if on_range != "retry_f32":
-                raise
-            if not getattr(model, "_warned_range_downgrade", False):
-                model._warned_range_downgrade = True
-                warnings.warn("%s: an operand left the fp16 range of the split arithmetic (precision 'f16x3'); this frame "
-                              "(and any later one that trips the guard) is re-rendered on the exact fp32 kernels "
-                              "(~3-6x slower). Set model.precision = 'f32' to skip the failed attempt."
-                              % type(model).__name__, RuntimeWarning, stacklevel=2)
-            if getattr(err, "static_operand", False):
-                model._range_latch = model.operands_key()
-            out = _render_exact(model, batch, chunk, white_bkgd, near, far, train_frac)
-            model.last_precision_used = "f32"
-    for k in ("target", "instance_mask"):
-        if k in batch:
-            out[k] = batch[k]
-    return out
+    return _render_guarded(model, batch, lambda: _render_once(model, batch, chunk, white_bkgd, near, far, train_frac), check, on_range)
+
+
+@torch.no_grad()
+def render_object_rays(model, batch, chunk=1024, white_bkgd=True, check=True, on_range="retry_f32"):
+    """Object-level frame of a NeRF_TP module: the fine level of `model.render_objects` on every ray of `batch` (which carries
+    the reference's `near_obj` / `far_obj` keys, e.g. from ops.sample_rays_in_bbox) in one library call, with the reference
+    chunk size passed down.  Returns dict(rgb (R,3), depth (R,), acc (R,)) plus `target` / `instance_mask` passed through.
+    Rays without a box interval return the background colour (white_bkgd) and acc = depth = 0.  check / on_range: the flag
+    read, range-guard retry and latch of render_rays_test (the same code path)."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("render_object_rays renders NeRF_TP modules, got %r" % type(model))
+
+    def once():
+        res = model.render_objects(batch, white_bkgd=white_bkgd, chunk=chunk)
+        return dict(rgb=res[1][0], depth=res[1][2], acc=res[1][1])
+    return _render_guarded(model, batch, once, check, on_range)
 
 
 @torch.no_grad()
