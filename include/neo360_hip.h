@@ -242,7 +242,11 @@ int neo_tp_mlp(neo_ctx* ctx, int slot, const float* rays_o, const float* rays_d,
  * src_poses [host]: NV*16 floats (c2w 4x4 row-major); focal/cx/cy: source view
  * 0's intrinsics (neo360/model.py:242-244).  Outputs per level l (any may be
  * NULL): rgb_l (R,3), fg_rgb_l (R,3), bg_rgb_l (R,3), fg_acc_l (R),
- * bg_lambda_l (R), depth_l (R). */
+ * bg_lambda_l (R), depth_l (R).  A level struct may itself be NULL.  When
+ * level0 is NULL, or none of its rgb / fg_rgb / bg_rgb / depth is set, the
+ * coarse level is evaluated for its densities alone (they place the fine
+ * samples): the pre-projected split evaluators skip its colour branch.  Level 1
+ * is bitwise the same either way. */
 typedef struct {
     float* rgb; float* fg_rgb; float* bg_rgb; float* fg_acc; float* bg_lambda; float* depth;
 } neo_tp_level_out;

@@ -52,9 +52,13 @@ int ensure_projections(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, bool p
 }
 
 // one region's evaluator launch in the context's arithmetic mode
+// density_only: the caller reads sigma alone (a level-0 launch whose colour and depth nobody asked for).  The pre-projected split
+// evaluators then run their density-only instantiation and the per-ray direction sums are not built; the exact-fp32 and the
+// raw-latent split evaluators ignore it and compute everything.
 int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
               const float* rays_d, const float* viewdirs, const float* tvals, const float* far, int R, int N, int chunk,
-              float* out, hipStream_t s, const int* cull_map = nullptr, const int* cull_count = nullptr) {
+              float* out, hipStream_t s, const int* cull_map = nullptr, const int* cull_count = nullptr,
+              bool density_only = false) {
     ORDERED(ctx, s);      // context scratch (tp_dirsum, projected maps, ws[]) is shared by all streams
     const int slot_index = static_cast<int>(&sl - ctx->tp);
     // Patch shape of the ray-patch tile order (neo_ctx_set_ray_grid), per region - measured fabric-side bytes per full-frame launch
@@ -97,16 +101,18 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
             neo::TpMlpHDev mh{sl.wpack_hp.p, sl.bias_hp.as<float>(), sl.heads.as<float>(), ctx->flags};
             // the view-direction encodings enter the MLP only through their mean over the views, and they depend on the
             // ray alone: summed once per ray here instead of once per sample and view inside the evaluator
+            // (a compact inside-sphere launch has no density-only instantiation: it runs the full kernel and needs the sums)
+            const bool dens = density_only && !(cull_map && sl.input_ch == 3);
             if (ctx->tp_dirsum->reserve(static_cast<size_t>(R) * 32 * sizeof(float))) return NEO_ERR_NOMEM;
-            neo::launch_tp_dirsum(viewdirs, R, views, sc.nv, ctx->tp_dirsum->as<float>(), s);
+            if (!dens) neo::launch_tp_dirsum(viewdirs, R, views, sc.nv, ctx->tp_dirsum->as<float>(), s);
             ctx->span_kernel_next = planes ? 2 : 1;
             ctx->span_begin(s);
             if (planes)
                 neo::launch_tp_mlp_hpp(sl.input_ch, mh, sl.proj.as<float>(), plane_base, scp, views, rays_o, rays_d, viewdirs, tvals, far,
-                                       R, N, chunk, ctx->flags, out, ctx->tp_dirsum->as<float>(), s);
+                                       R, N, chunk, ctx->flags, out, ctx->tp_dirsum->as<float>(), s, dens);
             else
                 neo::launch_tp_mlp_hp(sl.input_ch, mh, sl.proj.as<float>(), scp, views, rays_o, rays_d, viewdirs, tvals, far, R, N,
-                                      chunk, ctx->flags, out, ctx->tp_dirsum->as<float>(), s);
+                                      chunk, ctx->flags, out, ctx->tp_dirsum->as<float>(), s, dens);
         } else {
             guard_split_weights(sl, sl.wpack_h.p, neo::tp_wpack_h_bytes(sl.input_ch), ctx->flags, s);
             if (ctx->latent_checked != ctx->scene_epoch) {
@@ -142,6 +148,12 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
     // real), so nothing derived from the spans prices rows that were never evaluated
     ctx->span_end(s, cull_map ? 0.0 : static_cast<double>(R) * N, tp_flop_per_point(sl.input_ch, sc.nv));
     return NEO_OK;
+}
+
+// may the level-0 launches of a frame render be density-only?  Yes when the caller takes none of the level's colours or depth
+// (fg_acc and bg_lambda are functions of sigma and stay available)
+bool level0_sigma_only(const neo_tp_level_out* level0) {
+    return !level0 || !(level0->rgb || level0->fg_rgb || level0->bg_rgb || level0->depth);
 }
 
 }  // namespace
@@ -310,22 +322,26 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const 
     neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);
     neo::launch_tp_level0(far, edges, R, N0, near, fg_t0, bg_s0, s);
 
+    // the coarse level feeds the fine one through its weights (sigma) alone: when nobody reads its colour or depth, its
+    // launches are density-only and its composites write neither
+    const bool sigma0 = level0_sigma_only(level0);
     const float* fg_t = fg_t0;
     const float* bg_s = bg_s0;
     for (int level = 0; level < 2; ++level) {
         const int N = level == 0 ? N0 : N1;
         const neo_tp_level_out* lo = level == 0 ? level0 : level1;
+        const bool dens = level == 0 && sigma0;
         MlpSlot& fg = ctx->tp[level];
         MlpSlot& bg = ctx->tp[2 + level];
-        if (int rc = tp_launch(ctx, fg, sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s)) return rc;
-        if (int rc = tp_launch(ctx, bg, sc, views, rays_o, rays_d, viewdirs, bg_s, far, R, N, chunk, bg_out, s)) return rc;
-        float* fg_rgb = (lo && lo->fg_rgb) ? lo->fg_rgb : s_fg_rgb;
-        float* bg_rgb = (lo && lo->bg_rgb) ? lo->bg_rgb : s_bg_rgb;
+        if (int rc = tp_launch(ctx, fg, sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
+        if (int rc = tp_launch(ctx, bg, sc, views, rays_o, rays_d, viewdirs, bg_s, far, R, N, chunk, bg_out, s, nullptr, nullptr, dens)) return rc;
+        float* fg_rgb = dens ? nullptr : (lo && lo->fg_rgb) ? lo->fg_rgb : s_fg_rgb;
+        float* bg_rgb = dens ? nullptr : (lo && lo->bg_rgb) ? lo->bg_rgb : s_bg_rgb;
         float* fg_acc = (lo && lo->fg_acc) ? lo->fg_acc : s_fg_acc;
         float* lam = (lo && lo->bg_lambda) ? lo->bg_lambda : s_lambda;
-        neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, fg_rgb, fg_acc, s_fg_depth,
+        neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, fg_rgb, fg_acc, dens ? nullptr : s_fg_depth,
                               level == 0 ? fg_w0 : nullptr, lam, s);
-        neo::launch_composite(2, bg_out, bg_s, N, nullptr, nullptr, R, N, 0, bg_rgb, nullptr, s_bg_depth,
+        neo::launch_composite(2, bg_out, bg_s, N, nullptr, nullptr, R, N, 0, bg_rgb, nullptr, dens ? nullptr : s_bg_depth,
                               level == 0 ? bg_w0 : nullptr, nullptr, s);
         if (lo && (lo->rgb || lo->depth))
             neo::launch_tp_merge(fg_rgb, s_fg_depth, lam, bg_rgb, s_bg_depth, R, lo->rgb, lo->depth, s);
@@ -402,6 +418,7 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);       // sphere-miss assertions: every ray, culled or not
     neo::launch_tp_level0(far, edges, R, N0, near, fg_t0, bg_s0, s);
 
+    const bool sigma0 = level0_sigma_only(level0);     // as neo_tp_render: density-only level-0 launches, no level-0 colour / depth
     struct LevelFg { float* fg_rgb; float* fg_depth; float* fg_acc; float* lam; float* bg_rgb; } L[2];
     for (int level = 0; level < 2; ++level) {
         const neo_tp_level_out* lo = level == 0 ? level0 : level1;
@@ -410,8 +427,9 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
                     (lo && lo->bg_lambda) ? lo->bg_lambda : b + r * 5, lo ? lo->bg_rgb : nullptr};
     }
     // foreground of both levels first: nothing in a ray's background half feeds its foreground half
-    if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, fg_t0, nullptr, R, N0, chunk, fg_out, s)) return rc;
-    neo::launch_composite(1, fg_out, fg_t0, N0, rays_d, far, R, N0, 0, L[0].fg_rgb, L[0].fg_acc, L[0].fg_depth, fg_w0, L[0].lam, s);
+    if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, fg_t0, nullptr, R, N0, chunk, fg_out, s, nullptr, nullptr, sigma0)) return rc;
+    neo::launch_composite(1, fg_out, fg_t0, N0, rays_d, far, R, N0, 0, sigma0 ? nullptr : L[0].fg_rgb, L[0].fg_acc,
+                          sigma0 ? nullptr : L[0].fg_depth, fg_w0, L[0].lam, s);
     if (neo::launch_resample(fg_t0, N0, fg_w0, u, 0, R, N0, n_fine, 0, fg_t1, s)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
     if (int rc = tp_launch(ctx, ctx->tp[1], sc, views, rays_o, rays_d, viewdirs, fg_t1, nullptr, R, N1, chunk, fg_out, s)) return rc;
     neo::launch_composite(1, fg_out, fg_t1, N1, rays_d, far, R, N1, 0, L[1].fg_rgb, L[1].fg_acc, L[1].fg_depth, nullptr, L[1].lam, s);
@@ -419,8 +437,9 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     neo::launch_cull_compact(L[0].lam, L[1].lam, R, eps, cws, survivors_out, s);
 
     // background on the survivors: grids sized for R, every kernel takes its row count from the device word
-    if (int rc = tp_launch(ctx, ctx->tp[2], sc, views, rays_o, rays_d, viewdirs, bg_s0, far, R, N0, chunk, bg_out, s, map, count)) return rc;
-    neo::launch_composite(2, bg_out, bg_s0, N0, nullptr, nullptr, R, N0, 0, c_bg_rgb, nullptr, c_bg_depth, bg_w0, nullptr, s, count);
+    if (int rc = tp_launch(ctx, ctx->tp[2], sc, views, rays_o, rays_d, viewdirs, bg_s0, far, R, N0, chunk, bg_out, s, map, count, sigma0)) return rc;
+    neo::launch_composite(2, bg_out, bg_s0, N0, nullptr, nullptr, R, N0, 0, sigma0 ? nullptr : c_bg_rgb, nullptr,
+                          sigma0 ? nullptr : c_bg_depth, bg_w0, nullptr, s, count);
     if (neo::launch_resample(bg_s0, N0, bg_w0, u, 0, R, N0, n_fine, 1, bg_s1, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
     if (level0 && (level0->rgb || level0->depth || level0->bg_rgb))
         neo::launch_tp_merge_culled(L[0].fg_rgb, L[0].fg_depth, L[0].lam, c_bg_rgb, c_bg_depth, slot, R, level0->rgb, level0->depth,

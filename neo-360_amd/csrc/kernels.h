@@ -237,12 +237,15 @@ void launch_tp_pack_hp(int input_ch, const float* const* w, const float* const* 
 void launch_tp_preproject(const float* latent_cl, long texels, const float* wpack_f32_stage_x, int kc_x, float* proj,
                           hipStream_t s, int channels = 256, int in_ch = 512, int first_chunk = 0);
 // dirsum (R, 32): per ray the SUM over the source views of its view-direction encoding in each view's camera frame
-// (27 features + 5 zeros), built by launch_tp_dirsum before every evaluator launch
+// (27 features + 5 zeros), built by launch_tp_dirsum before every evaluator launch.
+// density_only (both launchers below): the caller reads the launch's sigma only - the kernel may skip the colour branch (direction
+// staging, view layers, rgb head), writes rgb = 0 and does not read `dirsum` (may be null).  A permission, not a contract: a launch
+// without a density-only instantiation (the object render's compact one) computes everything.
 void launch_tp_dirsum(const float* viewdirs, int R, const TpViews& views, int nv, float* dirsum, hipStream_t s);
 void launch_tp_mlp_hp(int input_ch, const TpMlpHDev& m, const float* proj, const TpScene& sc, const TpViews& views,
                       const float* rays_o, const float* rays_d, const float* viewdirs, const float* tvals,
                       const float* far, int R, int N, int chunk, uint32_t* flags, float* out, const float* dirsum,
-                      hipStream_t s);
+                      hipStream_t s, bool density_only = false);
 
 // mlp_tp_hpp.hip — the same evaluator with the three TRI-PLANES pre-projected as well (through [W0_world | W3_world]):
 // no world GEMM stage per point-view; 4 maps x 1 KB taps are blended and added to the L0 / L3-skip accumulators
@@ -253,7 +256,7 @@ size_t tp_proj_pad_bytes();
 void launch_tp_mlp_hpp(int input_ch, const TpMlpHDev& m, const float* proj_all, const long plane_base_texels[3],
                        const TpScene& sc, const TpViews& views, const float* rays_o, const float* rays_d, const float* viewdirs,
                        const float* tvals, const float* far, int R, int N, int chunk, uint32_t* flags, float* out,
-                       const float* dirsum, hipStream_t s);
+                       const float* dirsum, hipStream_t s, bool density_only = false);
 
 // (train_mlp.hip's launchers are declared in train_kernels.h)
 

@@ -63,7 +63,10 @@ namespace {
 using namespace hp;
 constexpr int RING = NEO_TP_RING;
 
-template <int PE_C, bool CULL = false>
+// DENS: density-only variant (level-0 launches of a frame whose coarse colour nobody reads): everything up to the view-mean trunk
+// and the density head is the full kernel's; the direction-encoding staging, the 14 tail k-steps and the rgb head are not run,
+// the point gets (0, 0, 0, density_act(raw_sigma)) and `dirsum` is not read (may be null).
+template <int PE_C, bool CULL = false, bool DENS = false>
 __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, const float* __restrict__ proj, TpScene sc,
                                                              TpViews views, const float* __restrict__ rays_o,
                                                              const float* __restrict__ rays_d,
@@ -116,7 +119,7 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
     const float* lheads = lbias_w + 768;
     float* dsum = smem + tp::OFF_DIR;          // [64][32] fp32: sum over the views of each point's direction encoding (same 8 KB as dsm)
     TP_SYNC();                                 // point_setup has recorded which ray's direction every row carries
-    {
+    if constexpr (!DENS) {
         // the sums come ready-made from the per-ray table of this launch (k_tp_dirsum): 8 features per thread
         const int p = tid >> 2, f0 = (tid & 3) << 3;
         const int dray = __float_as_int(S.vdir_world[p * 4 + 3]);
@@ -124,8 +127,8 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
         const f32x4 s1 = *reinterpret_cast<const f32x4*>(dirsum + (long)dray * 32 + f0 + 4);
 #pragma unroll
         for (int j = 0; j < 8; ++j) dsum[p * 32 + ((f0 + j) ^ (p & 31))] = j < 4 ? s0[j] : s1[j - 4];
+        TP_SYNC();
     }
-    TP_SYNC();
     TP_MARK(0);
 
     // view means by linearity (see mlp_tp_h.hip): only sum_v relu(L3_v) and sum_v dir_enc_v are accumulated per view
@@ -496,11 +499,13 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
     store_tile_h<false>(hsum[0], act, L.wv, 0, L);
     store_tile_h<false>(hsum[1], act, L.wv, 1, L);
     // view mean of the direction encoding: fp32 sums -> hi/lo planes in place (read all, barrier, write)
-    float dmean[8];
+    [[maybe_unused]] float dmean[8];
+    if constexpr (!DENS) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) dmean[j] = dsum[(tid >> 2) * 32 + ((((tid & 3) << 3) + j) ^ ((tid >> 2) & 31))] * inv_nv;
+        for (int j = 0; j < 8; ++j) dmean[j] = dsum[(tid >> 2) * 32 + ((((tid & 3) << 3) + j) ^ ((tid >> 2) & 31))] * inv_nv;
+    }
     TP_SYNC();
-    {
+    if constexpr (!DENS) {
         h8 vh, vl;
 #pragma unroll
         for (int j = 0; j < 8; j += 2) {
@@ -522,7 +527,7 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
     }
     // ---- tail GEMMs as one weight stream of 14 k-steps, TD ahead across the stage boundary: view layer 0 WITH THE BOTTLENECK FOLDED
     //      IN (tp_hp_layout.h) on [mean trunk | mean dir enc] (N-tile vnt, M-tile vmt, 8 + 2 k-steps), then 64 x 64 (4 k-steps) ----
-    {
+    if constexpr (!DENS) {
         const char* twb = reinterpret_cast<const char*>(wp);
         constexpr int TD = 6, TS = TD + 1;
         h8 twh[TS], twl[TS];
@@ -570,35 +575,40 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
             }
             __builtin_amdgcn_sched_barrier(0);
         });
+        TP_SYNC();
     }
-    TP_SYNC();
     {
         const int pt = L.wv * 16 + (L.lane >> 2), part = L.lane & 3;
-        const float* wr = lheads + HD_RW;
-        float r = 0.f, g = 0.f, b = 0.f;
+        [[maybe_unused]] float r = 0.f, g = 0.f, b = 0.f;
+        if constexpr (!DENS) {
+            const float* wr = lheads + HD_RW;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int chunk_i = part * 2 + ((c + part) & 1);
-            const int o = chunk_off<128>(pt, chunk_i);
-            const h8 vh = *reinterpret_cast<const h8*>(act.hi + o);
-            const h8 vl = *reinterpret_cast<const h8*>(act.lo + o);
+            for (int c = 0; c < 2; ++c) {
+                const int chunk_i = part * 2 + ((c + part) & 1);
+                const int o = chunk_off<128>(pt, chunk_i);
+                const h8 vh = *reinterpret_cast<const h8*>(act.hi + o);
+                const h8 vl = *reinterpret_cast<const h8*>(act.lo + o);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float h = (float)vh[e] + (float)vl[e];
-                r += h * wr[chunk_i * 8 + e];
-                g += h * wr[64 + chunk_i * 8 + e];
-                b += h * wr[128 + chunk_i * 8 + e];
+                for (int e = 0; e < 8; ++e) {
+                    const float h = (float)vh[e] + (float)vl[e];
+                    r += h * wr[chunk_i * 8 + e];
+                    g += h * wr[64 + chunk_i * 8 + e];
+                    b += h * wr[128 + chunk_i * 8 + e];
+                }
             }
+            r += __shfl_xor(r, 1, 64); r += __shfl_xor(r, 2, 64);
+            g += __shfl_xor(g, 1, 64); g += __shfl_xor(g, 2, 64);
+            b += __shfl_xor(b, 1, 64); b += __shfl_xor(b, 2, 64);
         }
-        r += __shfl_xor(r, 1, 64); r += __shfl_xor(r, 2, 64);
-        g += __shfl_xor(g, 1, 64); g += __shfl_xor(g, 2, 64);
-        b += __shfl_xor(b, 1, 64); b += __shfl_xor(b, 2, 64);
         range_commit(L, m.flags);
         const long gv = tile0 + pt;
         const long gi = tp::patch_point(gv, N, R, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
         if (part == 0 && gv < P) {
-            out[gi] = make_float4(colour_act(r + lheads[HD_RB]), colour_act(g + lheads[HD_RB + 1]),
-                                  colour_act(b + lheads[HD_RB + 2]), density_act(raw_sigma));
+            if constexpr (DENS)
+                out[gi] = make_float4(0.0f, 0.0f, 0.0f, density_act(raw_sigma));
+            else
+                out[gi] = make_float4(colour_act(r + lheads[HD_RB]), colour_act(g + lheads[HD_RB + 1]),
+                                      colour_act(b + lheads[HD_RB + 2]), density_act(raw_sigma));
         }
     }
 #if NEO_TP_TRACE
@@ -785,7 +795,7 @@ void launch_tp_dirsum(const float* viewdirs, int R, const TpViews& views, int nv
 void launch_tp_mlp_hp(int input_ch, const TpMlpHDev& m, const float* proj, const TpScene& sc, const TpViews& views,
                       const float* rays_o, const float* rays_d, const float* viewdirs, const float* tvals,
                       const float* far, int R, int N, int chunk, uint32_t* flags, float* out, const float* dirsum,
-                      hipStream_t s) {
+                      hipStream_t s, bool density_only) {
     const long P = (long)R * N;
     if (P <= 0) return;
     static int stagger = -1;
@@ -804,11 +814,17 @@ void launch_tp_mlp_hp(int input_ch, const TpMlpHDev& m, const float* proj, const
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<3, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     const long tiles = tp::xcd_grid((P + TM - 1) / TM);
     // every branch tests cull_map: a compact launch (culled background, object render) can never reach a non-compact kernel
-    // (the existing instantiations stay in their source order: their machine code depends on it, profiles/objects_isa.txt)
-    if (!sc.cull_map && input_ch == 3)
+    // (the existing instantiations stay in their source order: their machine code depends on it, profiles/objects_isa.txt; the
+    // density-only ones come after all of them.  The object render's compact inside-sphere launch has none: it runs the full kernel.)
+    const bool dens = density_only && !(sc.cull_map && input_ch == 3);
+    if (dens) {        // launched below, from the instantiations that come last
+    } else if (!sc.cull_map && input_ch == 3)
         hipLaunchKernelGGL(k_tp_mlp_hp<3>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
     else if (sc.cull_map && input_ch != 3)      // compact launch of the culled render: its own instantiation
@@ -819,6 +835,16 @@ void launch_tp_mlp_hp(int input_ch, const TpMlpHDev& m, const float* proj, const
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
     else                                         // compact launch of the object render
         hipLaunchKernelGGL((k_tp_mlp_hp<3, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
+    if (!dens) return;
+    if (!sc.cull_map && input_ch == 3)
+        hipLaunchKernelGGL((k_tp_mlp_hp<3, false, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
+    else if (!sc.cull_map)
+        hipLaunchKernelGGL((k_tp_mlp_hp<4, false, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
+    else
+        hipLaunchKernelGGL((k_tp_mlp_hp<4, true, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), stagger, dirsum);
 }
 

@@ -81,7 +81,9 @@ static_assert(PP_LDS_WORDS * 4 <= 81920, "two workgroups per CU");
 
 struct TpPlaneBase { int texels[3]; };      // first texel of each projected tri-plane inside the one projected-maps buffer
 
-template <int PE_C, bool CULL = false>
+// DENS: density-only variant, as k_tp_mlp_hp's: no direction-encoding staging, no tail k-steps, no rgb head; the point gets
+// (0, 0, 0, density_act(raw_sigma)) and `dirsum` is not read (may be null).
+template <int PE_C, bool CULL = false, bool DENS = false>
 __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, const float* __restrict__ proj, TpPlaneBase plb,
                                                                TpScene sc, TpViews views, const float* __restrict__ rays_o,
                                                                const float* __restrict__ rays_d,
@@ -494,7 +496,7 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
     for (int r = 0; r < 16; ++r) { hsum[0][r] = hsum[0][r] * inv_nv; hsum[1][r] = hsum[1][r] * inv_nv; }
     store_tile_h<false>(hsum[0], act, L.wv, 0, L);
     store_tile_h<false>(hsum[1], act, L.wv, 1, L);
-    {
+    if constexpr (!DENS) {
         // view mean of the direction encoding straight from the per-ray table of this launch (k_tp_dirsum: the sum over
         // the views of the ray whose direction this point carries, quirk Q1) -> hi/lo planes; 8 features per thread
         const int p = tid >> 2, f0 = (tid & 3) << 3;
@@ -524,7 +526,7 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
     }
     // ---- tail GEMMs as one weight stream of 14 k-steps, TD ahead across the stage boundary: view layer 0 WITH THE BOTTLENECK FOLDED
     //      IN (tp_hp_layout.h) on [mean trunk | mean dir enc] (N-tile vnt, M-tile vmt, 8 + 2 k-steps), then 64 x 64 (4 k-steps) ----
-    {
+    if constexpr (!DENS) {
         const char* twb = reinterpret_cast<const char*>(wp);
         constexpr int TD = NEO_TPP_TD, TS = TD + 1;
         h8 twh[TS], twl[TS];
@@ -572,35 +574,40 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
             }
             __builtin_amdgcn_sched_barrier(0);
         });
+        TPP_SYNC();
     }
-    TPP_SYNC();
     {
         const int pt = L.wv * 16 + (L.lane >> 2), part = L.lane & 3;
-        const float* wr = lheads + HD_RW;
-        float r = 0.f, g = 0.f, b = 0.f;
+        [[maybe_unused]] float r = 0.f, g = 0.f, b = 0.f;
+        if constexpr (!DENS) {
+            const float* wr = lheads + HD_RW;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int chunk_i = part * 2 + ((c + part) & 1);
-            const int o = chunk_off<128>(pt, chunk_i);
-            const h8 vh = *reinterpret_cast<const h8*>(act.hi + o);
-            const h8 vl = *reinterpret_cast<const h8*>(act.lo + o);
+            for (int c = 0; c < 2; ++c) {
+                const int chunk_i = part * 2 + ((c + part) & 1);
+                const int o = chunk_off<128>(pt, chunk_i);
+                const h8 vh = *reinterpret_cast<const h8*>(act.hi + o);
+                const h8 vl = *reinterpret_cast<const h8*>(act.lo + o);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float h = (float)vh[e] + (float)vl[e];
-                r += h * wr[chunk_i * 8 + e];
-                g += h * wr[64 + chunk_i * 8 + e];
-                b += h * wr[128 + chunk_i * 8 + e];
+                for (int e = 0; e < 8; ++e) {
+                    const float h = (float)vh[e] + (float)vl[e];
+                    r += h * wr[chunk_i * 8 + e];
+                    g += h * wr[64 + chunk_i * 8 + e];
+                    b += h * wr[128 + chunk_i * 8 + e];
+                }
             }
+            r += __shfl_xor(r, 1, 64); r += __shfl_xor(r, 2, 64);
+            g += __shfl_xor(g, 1, 64); g += __shfl_xor(g, 2, 64);
+            b += __shfl_xor(b, 1, 64); b += __shfl_xor(b, 2, 64);
         }
-        r += __shfl_xor(r, 1, 64); r += __shfl_xor(r, 2, 64);
-        g += __shfl_xor(g, 1, 64); g += __shfl_xor(g, 2, 64);
-        b += __shfl_xor(b, 1, 64); b += __shfl_xor(b, 2, 64);
         range_commit(L, m.flags);
         const long gv = tile0 + pt;
         const long gi = tp::patch_point(gv, N, R, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
         if (part == 0 && gv < P) {
-            out[gi] = make_float4(colour_act(r + lheads[HD_RB]), colour_act(g + lheads[HD_RB + 1]),
-                                  colour_act(b + lheads[HD_RB + 2]), density_act(raw_sigma));
+            if constexpr (DENS)
+                out[gi] = make_float4(0.0f, 0.0f, 0.0f, density_act(raw_sigma));
+            else
+                out[gi] = make_float4(colour_act(r + lheads[HD_RB]), colour_act(g + lheads[HD_RB + 1]),
+                                      colour_act(b + lheads[HD_RB + 2]), density_act(raw_sigma));
         }
     }
 #if NEO_TP_TRACE
@@ -629,7 +636,7 @@ extern "C" void neo_debug_tpp_trace(unsigned long long* host16, int reset) {
 void launch_tp_mlp_hpp(int input_ch, const TpMlpHDev& m, const float* proj_all, const long plane_base_texels[3],
                        const TpScene& sc, const TpViews& views, const float* rays_o, const float* rays_d, const float* viewdirs,
                        const float* tvals, const float* far, int R, int N, int chunk, uint32_t* flags, float* out,
-                       const float* dirsum, hipStream_t s) {
+                       const float* dirsum, hipStream_t s, bool density_only) {
     const long P = (long)R * N;
     if (P <= 0) return;
     const float* proj = proj_all;
@@ -645,12 +652,18 @@ void launch_tp_mlp_hpp(int input_ch, const TpMlpHDev& m, const float* proj_all, 
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<3, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hpp<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
     const long tiles = tp::xcd_grid((P + TM - 1) / TM);
     // every branch tests cull_map: a compact launch (culled background, object render) can never reach a non-compact kernel
-    // (the existing instantiations stay in their source order: their machine code depends on it, profiles/objects_isa.txt)
-    if (!sc.cull_map && input_ch == 3)
+    // (the existing instantiations stay in their source order: their machine code depends on it, profiles/objects_isa.txt; the
+    // density-only ones come after all of them.  The object render's compact inside-sphere launch has none: it runs the full kernel.)
+    const bool dens = density_only && !(sc.cull_map && input_ch == 3);
+    if (dens) {        // launched below, from the instantiations that come last
+    } else if (!sc.cull_map && input_ch == 3)
         hipLaunchKernelGGL(k_tp_mlp_hpp<3>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, pp, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), dirsum);
     else if (sc.cull_map && input_ch != 3)      // compact launch of the culled render: its own instantiation
@@ -661,6 +674,16 @@ void launch_tp_mlp_hpp(int input_ch, const TpMlpHDev& m, const float* proj_all, 
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), dirsum);
     else                                         // compact launch of the object render
         hipLaunchKernelGGL((k_tp_mlp_hpp<3, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, pp, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), dirsum);
+    if (!dens) return;
+    if (!sc.cull_map && input_ch == 3)
+        hipLaunchKernelGGL((k_tp_mlp_hpp<3, false, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, pp, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), dirsum);
+    else if (!sc.cull_map)
+        hipLaunchKernelGGL((k_tp_mlp_hpp<4, false, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, pp, sc, views, rays_o, rays_d,
+                           viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), dirsum);
+    else
+        hipLaunchKernelGGL((k_tp_mlp_hpp<4, true, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, pp, sc, views, rays_o, rays_d,
                            viewdirs, tvals, far, R, N, chunk, flags, reinterpret_cast<float4*>(out), dirsum);
 }
 

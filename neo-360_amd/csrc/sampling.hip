@@ -4,6 +4,8 @@
 // running carry across 64-sample rounds (samples of a ray are contiguous in
 // HBM, so every round is one coalesced load per array).  These kernels are
 // HBM-bound: 24 B/point for compositing, ~12 B/point for resampling.
+#include <cstdlib>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -147,42 +149,81 @@ void launch_composite(int mode, const float* rgbsigma, const float* t, int t_row
 //    bin0 = max(bins_0..bins_J)        bin1 = min(bins_{J+1}..bins_last) (bins_last if J is last)
 // which is evaluated here with a prefix-max / suffix-min of the bins — valid for
 // ascending AND descending bins (the background branch), no monotonicity of the
-// bins assumed.  The merged set is sorted with an in-LDS bitonic network
-// (a real sort: background samples are not monotone).
+// bins assumed.
+//
+// The merged row is sort(cat(t_prev, samples)).  t_prev is normally monotone
+// already (ascending inside the sphere, descending outside) and so are the new
+// samples of an ascending row; a descending row's samples are a sawtooth (pmax /
+// smin collapse to the first and last bin, as in the reference).  So per ray:
+//   1. t_prev monotone in the row's direction (checked while the bins are made;
+//      a NaN fails the comparison) and no NaN among the new samples: MERGE,
+//      otherwise the full bitonic network over the whole row;
+//   2. the new samples are sorted alone if they are not non-decreasing (bitonic
+//      over the next power of two of n_new);
+//   3. merge by rank: a previous sample goes to its index + #(new samples
+//      strictly below it), a new sample to its index + #(previous samples at or
+//      below it), both counts by binary search in LDS.
+// The output of a sort is fixed by the multiset of its values, so both paths give
+// the same bits (equal floats are identical bits; the one exception, -0.0 next to
+// +0.0, cannot arise from non-negative t rows).  $NEO_RESAMPLE_FULL_SORT=1 (read
+// once per process) forces the full network for every ray.
+// A ray and all its LDS buffers belong to ONE wave: the stages are ordered with
+// wave_sync(), there is no workgroup barrier, and surplus waves leave at once.
 // ---------------------------------------------------------------------------
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// bitonic sort of a wave-private LDS buffer of n (a power of two) floats, ascending (+inf padding stays at the end)
+__device__ __forceinline__ void wave_bitonic(float* srt, int n, int lane) {
+    for (int k = 2; k <= n; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = lane; i < n; i += 64) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const float a = srt[i], b = srt[p];
+                    const bool up = (i & k) == 0;
+                    if ((a > b) == up) { srt[i] = b; srt[p] = a; }
+                }
+            }
+            wave_sync();
+        }
+    }
+}
+
 template <int MAXB, int SORT_N>
 __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ t_prev, int t_prev_stride,
                                                   const float* __restrict__ weights,
                                                   const float* __restrict__ u_arr, int u_row_stride, int R, int n_prev,
                                                   int n_new, int descending, float* __restrict__ t_out,
-                                                  const int* __restrict__ r_dev) {
-    if (r_dev) {                 // compact arrays (cull.hip): row count on the device; whole surplus workgroups leave before any barrier
-        R = *r_dev;
-        if ((int)(blockIdx.x * RAYS_PER_BLOCK) >= R) return;
-    }
-    __shared__ float s_bins[RAYS_PER_BLOCK][MAXB];
-    __shared__ float s_pmax[RAYS_PER_BLOCK][MAXB];
-    __shared__ float s_smin[RAYS_PER_BLOCK][MAXB];
-    __shared__ float s_cdf[RAYS_PER_BLOCK][MAXB];
-    __shared__ float s_sort[RAYS_PER_BLOCK][SORT_N];
+                                                  const int* __restrict__ r_dev, int full_sort) {
+    if (r_dev) R = *r_dev;       // compact arrays (cull.hip): the row count lives on the device, the grid covers the caller's rays
+    // per wave: bins | pmax | smin | cdf (MAXB each), then the sort buffer
+    __shared__ float s_buf[RAYS_PER_BLOCK][4 * MAXB + SORT_N];
     const int wv = threadIdx.x >> 6, lane = lane_id();
-    const int ray_raw = blockIdx.x * RAYS_PER_BLOCK + wv;
-    const bool live = ray_raw < R;
-    const int ray = live ? ray_raw : R - 1;  // surplus waves redo the last ray so every barrier is uniform
+    const int ray = blockIdx.x * RAYS_PER_BLOCK + wv;
+    if (ray >= R) return;        // wave-uniform; no workgroup barrier below
     const int nb = n_prev - 1;   // bins = midpoints
     const int nw = n_prev - 2;   // pdf weights = weights[1:-1]
     const int n_out = n_prev + n_new;
-    float* bins = s_bins[wv]; float* pmax = s_pmax[wv]; float* smin = s_smin[wv];
-    float* cdf = s_cdf[wv]; float* srt = s_sort[wv];
+    float* bins = s_buf[wv]; float* pmax = bins + MAXB; float* smin = bins + 2 * MAXB;
+    float* cdf = bins + 3 * MAXB; float* srt = bins + 4 * MAXB;
+    const float* tp = t_prev + (long)ray * t_prev_stride;
+    bool merge;
     {
-        const float* tp = t_prev + (long)ray * t_prev_stride;
         const float* wp = weights + (long)ray * n_prev + 1;
-        // bins + total weight
+        // bins + total weight; is t_prev monotone in the row's direction?
         float part = 0.f;
+        bool mono = true;
         for (int k = lane; k < nb; k += 64) {
-            bins[k] = 0.5f * (tp[k + 1] + tp[k]);
+            const float t0 = tp[k], t1 = tp[k + 1];
+            bins[k] = 0.5f * (t1 + t0);
+            mono = mono && (descending ? t0 >= t1 : t0 <= t1);
             if (k < nw) part += wp[k];
         }
+        merge = !full_sort && __ballot(!mono) == 0ull;
         float total = wave_sum(part);
         const float pad = fmaxf(0.0f, 1e-5f - total);
         const float add = pad / (float)nw;
@@ -203,7 +244,7 @@ __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ t_pr
             carry += __shfl(incl, 63, 64);
         }
         if (lane == 0) { cdf[0] = 0.0f; cdf[nb - 1] = 1.0f; }
-        __syncthreads();
+        wave_sync();
         // prefix max / suffix min of the bins
         float cmax = -__builtin_inff(), cmin = __builtin_inff();
         for (int base = 0; base < nb; base += 64) {
@@ -218,10 +259,9 @@ __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ t_pr
             if (k < nb) smin[kr] = mr;
             cmin = __shfl(mr, 63, 64);
         }
-        __syncthreads();
-        // previous samples into the sort buffer
-        for (int i = lane; i < SORT_N; i += 64) srt[i] = i < n_prev ? tp[i] : __builtin_inff();
-        // new samples
+        wave_sync();
+        // new samples: srt[0 .. n_new)
+        bool nan_new = false;
         for (int m = lane; m < n_new; m += 64) {
             const float u = u_arr[(long)ray * u_row_stride + m];     // stride 0: one shared row of quantiles
             int lo = 0, hi = nb;  // first index with cdf > u
@@ -235,27 +275,58 @@ __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ t_pr
             const float b0 = pmax[J], b1 = last ? bins[nb - 1] : smin[J + 1];
             float frac = nan_to_num((u - c0) / (c1 - c0), 0.0f);
             frac = fminf(fmaxf(frac, 0.0f), 1.0f);
-            srt[n_prev + m] = b0 + frac * (b1 - b0);
+            const float v = b0 + frac * (b1 - b0);
+            nan_new = nan_new || v != v;
+            srt[m] = v;
         }
+        if (__ballot(nan_new) != 0ull) merge = false;
     }
-    __syncthreads();
-    // bitonic sort, ascending (padding = +inf stays at the end)
-    for (int k = 2; k <= SORT_N; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = lane; i < SORT_N; i += 64) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const float a = srt[i], b = srt[p];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) { srt[i] = b; srt[p] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (live) {
-        float* out = t_out + (long)ray * n_out;
+    wave_sync();                 // bins / pmax / smin / cdf are dead from here on
+    float* out = t_out + (long)ray * n_out;
+    if (!merge) {
+        // the whole row through the network: previous samples behind the new ones, +inf padding behind both
+        for (int i = n_new + lane; i < SORT_N; i += 64) srt[i] = i < n_out ? tp[i - n_new] : __builtin_inff();
+        wave_sync();
+        wave_bitonic(srt, SORT_N, lane);
         for (int i = lane; i < n_out; i += 64) out[i] = srt[descending ? n_out - 1 - i : i];
+        return;
+    }
+    // previous samples, ascending, into the dead bins | pmax part
+    float* pv = bins;
+    for (int i = lane; i < n_prev; i += 64) pv[i] = tp[descending ? n_prev - 1 - i : i];
+    // the new samples sorted alone where they are not in order already
+    bool sorted = true;
+    for (int m = lane; m < n_new - 1; m += 64) sorted = sorted && srt[m] <= srt[m + 1];
+    if (__ballot(!sorted) != 0ull) {
+        int p2 = 1;
+        while (p2 < n_new) p2 <<= 1;       // <= SORT_N: n_new < n_out <= SORT_N, a power of two
+        wave_sync();                       // the order check has read what the padding and the network overwrite
+        for (int i = n_new + lane; i < p2; i += 64) srt[i] = __builtin_inff();
+        wave_sync();
+        wave_bitonic(srt, p2, lane);
+    } else {
+        wave_sync();
+    }
+    // merge by rank (ties: previous samples first - equal values are equal bits, the order among them is immaterial)
+    for (int i = lane; i < n_prev; i += 64) {
+        const float x = pv[i];
+        int lo = 0, hi = n_new;            // number of new samples < x
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (srt[mid] < x) lo = mid + 1; else hi = mid;
+        }
+        const int pos = i + lo;
+        out[descending ? n_out - 1 - pos : pos] = x;
+    }
+    for (int m = lane; m < n_new; m += 64) {
+        const float x = srt[m];
+        int lo = 0, hi = n_prev;           // number of previous samples <= x
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (pv[mid] <= x) lo = mid + 1; else hi = mid;
+        }
+        const int pos = m + lo;
+        out[descending ? n_out - 1 - pos : pos] = x;
     }
 }
 
@@ -264,12 +335,17 @@ int launch_resample(const float* t_prev, int t_prev_stride, const float* weights
     const int n_out = n_prev + n_new;
     const dim3 grid((R + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK), block(256);
     if (n_prev < 4 || n_prev - 1 > 256) return -1;
+    static int full_sort = -1;   // $NEO_RESAMPLE_FULL_SORT (read once): every ray through the full network, for comparisons
+    if (full_sort < 0) {
+        const char* e = getenv("NEO_RESAMPLE_FULL_SORT");
+        full_sort = e && atoi(e) != 0 ? 1 : 0;
+    }
     if (n_out <= 256)
-        hipLaunchKernelGGL((k_resample<256, 256>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev);
+        hipLaunchKernelGGL((k_resample<256, 256>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev, full_sort);
     else if (n_out <= 512)
-        hipLaunchKernelGGL((k_resample<256, 512>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev);
+        hipLaunchKernelGGL((k_resample<256, 512>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev, full_sort);
     else if (n_out <= 1024)
-        hipLaunchKernelGGL((k_resample<256, 1024>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev);
+        hipLaunchKernelGGL((k_resample<256, 1024>), grid, block, 0, s, t_prev, t_prev_stride, weights, u, u_row_stride, R, n_prev, n_new, descending, t_out, r_dev, full_sort);
     else
         return -1;
     return 0;

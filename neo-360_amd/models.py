@@ -666,9 +666,11 @@ class NeRF_TP(_HipModule):
         held = getattr(self, "_scene_src", None)
         return tuple(r() for r in held[0]) if held is not None else ()
 
-    def forward(self, rays, randomized, white_bkgd, near, far, out_depth=False, chunk=None, seed=None):
+    def forward(self, rays, randomized, white_bkgd, near, far, out_depth=False, chunk=None, seed=None, fine_only=False):
         """out_depth=True (evaluation, neo360/model.py:521-527): per level (comp_rgb, fg_rgb, bg_rgb, fg_acc, bg_lambda,
-        comp_depth), randomized=False.  out_depth=False (the training call, :531-579): per level (comp_rgb, fg_weights,
+        comp_depth), randomized=False.  With `fine_only=True` that call returns [None, level-1 tuple]: the coarse level then
+        only delivers the densities the fine samples are drawn from (no level-0 tensors, density-only coarse launches where the
+        evaluator has them); the level-1 tuple is bitwise the default call's.  out_depth=False (the training call, :531-579): per level (comp_rgb, fg_weights,
         bg_weights, fg_sdist, bg_sdist, bg_acc), randomized as asked.  `near`/`far` are ignored
         exactly as in the reference (:277-278).  All rays of the call form ONE reference chunk unless `chunk` is given
         (whole-frame rendering, see render.py).
@@ -693,9 +695,9 @@ class NeRF_TP(_HipModule):
             with torch.no_grad():
                 return self._forward_train(rays, randomized, white_bkgd, chunk, seed)
         with torch.no_grad():
-            return self._forward_eval(rays, randomized, white_bkgd, chunk)
+            return self._forward_eval(rays, randomized, white_bkgd, chunk, fine_only)
 
-    def _forward_eval(self, rays, randomized, white_bkgd, chunk=None):
+    def _forward_eval(self, rays, randomized, white_bkgd, chunk=None, fine_only=False):
         self._check_mode(randomized)
         raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
         rays_o = f32(raw[0], "rays_o")
@@ -719,7 +721,11 @@ class NeRF_TP(_HipModule):
 
         def launch():
             structs = []
-            for _ in range(2):
+            for level in range(2):
+                if level == 0 and fine_only:       # NULL level 0: the library runs the coarse launches for their densities alone
+                    levels.append(None)
+                    structs.append(None)
+                    continue
                 t = dict(rgb=torch.empty(B, 3, device=dev), fg_rgb=torch.empty(B, 3, device=dev),
                          bg_rgb=torch.empty(B, 3, device=dev), fg_acc=torch.empty(B, device=dev),
                          bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
@@ -727,7 +733,7 @@ class NeRF_TP(_HipModule):
                 structs.append(_lib.TpLevelOut(*(t[k].data_ptr() for k in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth"))))
             args = (ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), B, int(chunk or max(B, 1)), host_poses, NV, focal, cx, cy,
                     self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
-                    ctypes.byref(structs[0]), ctypes.byref(structs[1]))
+                    ctypes.byref(structs[0]) if structs[0] is not None else None, ctypes.byref(structs[1]))
             extra = []
             if eps is None:
                 _lib.check(ctx.lib.neo_tp_render(*args, ctx.stream()))
@@ -736,14 +742,15 @@ class NeRF_TP(_HipModule):
                 extra.append(torch.empty((), dtype=torch.int32, device=dev))
                 _lib.check(ctx.lib.neo_tp_render_culled(*args, eps, extra[0].data_ptr(), ctx.stream()))
             self._after_call(ctx)
-            return [v for t in levels for v in t.values()] + extra
+            return [v for t in levels if t is not None for v in t.values()] + extra
         try:
             made = self._launch_overlapped(ctx, dev, raw, (rays_o, rays_d, viewdirs), launch)
         finally:
             ctx.set_ray_grid(0)
         if eps is not None:
             self.last_cull_survivors = made[-1]
-        return [(t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"]) for t in levels]
+        return [None if t is None else (t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"])
+                for t in levels]
 
     @staticmethod
     def _object_bound(rays, given, key, B):

@@ -30,7 +30,7 @@ def _slice(batch, lo, hi):
 
 def _render_once(model, batch, chunk, white_bkgd, near, far, train_frac):
     if isinstance(model, models.NeRF_TP):
-        res = model(batch, False, white_bkgd, near, far, out_depth=True, chunk=chunk)
+        res = model(batch, False, white_bkgd, near, far, out_depth=True, chunk=chunk, fine_only=True)      # only res[1] is read
         return dict(rgb=res[1][0], depth=res[1][5], fg_rgb=res[1][1], bg_rgb=res[1][2], acc=res[1][3])
     if isinstance(model, models.PixelNeRF):
         res = model(batch, False, white_bkgd, near, far, chunk=chunk)      # vanilla_nerf/model_pixel.py:356-383
