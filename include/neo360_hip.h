@@ -648,6 +648,27 @@ int neo_mip_lossfun_outer_backward(neo_ctx* ctx, const float* t, const float* w,
 int neo_mip_lossfun_distortion(neo_ctx* ctx, const float* t, const float* w, int R, int N, float* loss_rays, float* grad_w,
                                void* stream);
 
+/* The per-ray extras of an interval histogram - the slot volumetric_rendering leaves open behind `compute_extras`
+ * (mipnerf360/helper.py:264-274), built from integrate_weights (:196-203) and sorted_interp (:207-222).  edges (R, n+1) do not
+ * decrease along a row, weights (R, n) are non-negative, 1 <= n <= 1024.  near == far == 0: edges are metric distances t already (any
+ * histogram); otherwise edges are sdist and t = s_to_t(edges) = 1 / (s / far + (1 - s) / near) (helper.py:168-172) inside the kernel,
+ * no (R, n+1) temporary; exactly one of near / far being 0 is an error.  Inputs and outputs are fp32, every prefix sum, difference
+ * and quotient in between (s_to_t included) is fp64 and each output entry is rounded once; no atomics, results repeat bit for bit.
+ *
+ * neo_mip_extras: u (n_u) DEVICE pointer, ascending quantiles in [0, 1], 0 <= n_u <= 8.  Outputs, any of which may be NULL:
+ * acc (R) = sum_i w_i;  dist_mean (R) = clip(nan_to_num(sum_i w_i (t_i + t_{i+1}) / 2 / acc, nan=inf), t_0, t_n) - a row without
+ * weight returns t_n;  dist_pct (R, n_u) = sorted_interp(u, integrate_weights(w), t) as the reference's two functions compute it:
+ * knots [0, min(cumsum(w[:-1]), 1), 1] without renormalisation, the bracket selected by u >= knot, offset =
+ * clip(nan_to_num(., 0), 0, 1).  The percentile jumps where u meets a knot at a zero-weight interval. */
+int neo_mip_extras(neo_ctx* ctx, const float* edges, const float* weights, int R, int n, float near, float far, const float* u, int n_u,
+                   float* acc, float* dist_mean, float* dist_pct /* (R, n_u) */, void* stream);
+/* Backward of (acc, dist_mean) with respect to the weights: upstream g_acc (R), g_mean (R), either may be NULL (= zeros) ->
+ * g_w (R, n) = g_acc + g_mean ((t_i + t_{i+1}) / 2 - mean) / acc.  On a row with acc == 0 the second term is DEFINED as 0 (autograd
+ * of the forward's expression yields NaN there).  Edges and percentiles carry no gradient: the percentile is piecewise linear in w
+ * with jumps at zero-weight intervals, and nothing in the reference differentiates it. */
+int neo_mip_extras_backward(neo_ctx* ctx, const float* edges, const float* weights, int R, int n, float near, float far,
+                            const float* g_acc, const float* g_mean, float* g_w, void* stream);
+
 /* MipNeRF360.forward(batch, train_frac, randomized=False, is_train=False, near, far)
  * (model.py:236-365), 3 levels (n_prop, n_prop, n_nerf samples).  Per level l (any pointer may be
  * NULL): rgb_l (R,3), sdist_l (R,n_l+1), weights_l (R,n_l), rgbdens_l (R,n_l,4) = per-interval

@@ -139,6 +139,8 @@ SIGNATURES = {
     "neo_mip_lossfun_outer": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "neo_mip_lossfun_outer_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "neo_mip_lossfun_distortion": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "neo_mip_extras": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp]),
+    "neo_mip_extras_backward": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
     "neo_mip_render": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _i, ctypes.POINTER(MipLevelOut), _vp]),
     "neo_ctx_set_timing": (_i, [_vp, _i]),
     "neo_ctx_read_timing": (_i, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i),

@@ -174,6 +174,32 @@ int neo_mip_lossfun_distortion(neo_ctx* ctx, const float* t, const float* w, int
     return check_launch();
 }
 
+// neither entry touches context-owned memory: no ordering scope, so a call on a lane's side stream stays a lane call's neighbour
+int neo_mip_extras(neo_ctx* ctx, const float* edges, const float* weights, int R, int n, float near, float far, const float* u, int n_u,
+                   float* acc, float* dist_mean, float* dist_pct, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && n >= 1 && n <= 1024, "bad shape (1 <= n <= 1024)");
+    REQUIRE(n_u >= 0 && n_u <= 8, "bad quantile count (0 <= n_u <= 8)");
+    REQUIRE((near == 0.0f && far == 0.0f) || (near > 0.0f && far > 0.0f), "near and far must both be positive, or both 0 for metric edges");
+    if (R == 0) return NEO_OK;
+    REQUIRE(edges && weights && (u || n_u == 0 || !dist_pct), "null pointer");
+    if (neo::launch_mip_extras(edges, weights, R, n, near, far, u, n_u, acc, dist_mean, dist_pct, static_cast<hipStream_t>(stream)))
+        return fail(NEO_ERR_INVALID, "unsupported interval or quantile count");
+    return check_launch();
+}
+
+int neo_mip_extras_backward(neo_ctx* ctx, const float* edges, const float* weights, int R, int n, float near, float far,
+                            const float* g_acc, const float* g_mean, float* g_w, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && n >= 1 && n <= 1024, "bad shape (1 <= n <= 1024)");
+    REQUIRE((near == 0.0f && far == 0.0f) || (near > 0.0f && far > 0.0f), "near and far must both be positive, or both 0 for metric edges");
+    if (R == 0) return NEO_OK;
+    REQUIRE(edges && weights && g_w, "null pointer");
+    if (neo::launch_mip_extras_bwd(edges, weights, R, n, near, far, g_acc, g_mean, g_w, static_cast<hipStream_t>(stream)))
+        return fail(NEO_ERR_INVALID, "unsupported interval count");
+    return check_launch();
+}
+
 int neo_mip_mlp(neo_ctx* ctx, int slot, const float* rays_o, const float* rays_d, const float* viewdirs,
                 const float* radii, const float* tdist, int R, int n, float* out, void* stream) {
     ENTER(ctx);

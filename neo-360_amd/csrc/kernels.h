@@ -206,6 +206,15 @@ int launch_mip_lossfun_outer_bwd(const float* t, const float* w, const float* t_
 // loss_rays (R) and, when not null, d loss_ray / d w (R,N)
 int launch_mip_lossfun_distortion(const float* t, const float* w, int R, int N, float* loss_rays, float* grad_w, hipStream_t s);
 
+// mip_extras.hip — opacity, expected distance and distance percentiles of an interval histogram, one wave per ray, fp64 between fp32
+// ends.  edges (R,n+1) non-decreasing: metric distances when near == far == 0, else sdist mapped with s_to_t; w (R,n); u (n_u) device
+// quantiles -> acc (R), dist_mean (R), dist_pct (R,n_u), each may be null.  Backward: g_acc (R), g_mean (R), either may be null
+// -> g_w (R,n).  Return -1 outside 1 <= n <= 1024, 0 <= n_u <= 8, or when exactly one of near / far is zero.
+int launch_mip_extras(const float* edges, const float* w, int R, int n, float near, float far, const float* u, int n_u, float* acc,
+                      float* dist_mean, float* dist_pct, hipStream_t s);
+int launch_mip_extras_bwd(const float* edges, const float* w, int R, int n, float near, float far, const float* g_acc,
+                          const float* g_mean, float* g_w, hipStream_t s);
+
 // mlp_tp_h.hip — the NeO-360 evaluator on the fp16 matrix cores (hi/lo-split operands, fp32-equivalent)
 struct TpMlpHDev {
     const void* wpack;    // fp16 hi/lo fragments

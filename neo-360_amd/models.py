@@ -1085,6 +1085,19 @@ class MipNeRF360(_HipModule):
 
     _upload = ("mip", "neo_mip_upload_mlp")
 
+    # The slot the reference's volumetric_rendering leaves open (helper.py:264-274 takes `compute_extras` and ignores it).  True: every
+    # level's rendering dict gains acc, distance_mean, distance_median, distance_percentile_5 and distance_percentile_95
+    # (ops.mip_extras on the level's own sdist / weights: one more launch per level); on the operator chain acc and distance_mean
+    # carry gradients to the weights (training.mip_expected_distance), the percentiles come detached.  False (default): no launch is
+    # added and forward returns what it always returned.
+    compute_extras = False
+    EXTRA_QUANTILES = (0.05, 0.5, 0.95)
+
+    @staticmethod
+    def _extras_dict(acc, mean, pct):
+        return dict(acc=acc, distance_mean=mean, distance_median=pct[..., 1], distance_percentile_5=pct[..., 0],
+                    distance_percentile_95=pct[..., 2])
+
     def _mlps(self):
         return self.mlps
 
@@ -1114,7 +1127,7 @@ class MipNeRF360(_HipModule):
         self._before_call(ctx)
         B = rays_o.shape[0]
         counts = (self.num_prop_samples, self.num_prop_samples, self.num_nerf_samples)
-        bufs = []
+        bufs, extras = [], []
 
         def launch():
             bufs.extend(dict(rgb=torch.empty(B, 3, device=dev), sdist=torch.empty(B, n + 1, device=dev),
@@ -1125,9 +1138,15 @@ class MipNeRF360(_HipModule):
                                               float(train_frac), float(near), float(far), self.num_prop_samples,
                                               self.num_nerf_samples, arr, ctx.stream()))
             self._after_call(ctx)
-            return [t for b in bufs for t in b.values()]
+            if self.compute_extras:            # on this call's stream, behind the render; the outputs join the tracked ones
+                from . import ops
+                for b in bufs:
+                    extras.append(ops.mip_extras(b["sdist"], b["weights"], self.EXTRA_QUANTILES, near, far, ctx=ctx))
+            return [t for b in bufs for t in b.values()] + [t for e in extras for t in e]
         self._launch_overlapped(ctx, dev, raw, (rays_o, rays_d, viewdirs, radii), launch)
         renderings = [{"rgb": b["rgb"]} for b in bufs]
+        for r, e in zip(renderings, extras):
+            r.update(self._extras_dict(*e))
         history = [dict(density=b["rgbdens"][..., 3], rgb=b["rgbdens"][..., :3], sdist=b["sdist"], weights=b["weights"])
                    for b in bufs]
         return renderings, history

@@ -173,3 +173,40 @@ def mip_composite(rgbdens, tdist, rays_d, bg=1.0, ctx=None):
     _lib.check(ctx.lib.neo_mip_composite(ctx.handle, ptr(rgbdens), ptr(tdist), ptr(rays_d), R, n1 - 1, float(bg), ptr(w),
                                          ptr(rgb), ctx.stream()))
     return w, rgb
+
+
+_QUANTILES = {}     # (device, quantiles) -> the fp32 device table neo_mip_extras reads
+
+
+def _quantile_table(u, dev):
+    if isinstance(u, torch.Tensor):
+        return f32(u.reshape(-1), "u")
+    key = (dev, tuple(float(x) for x in u))
+    tab = _QUANTILES.get(key)
+    if tab is None:
+        tab = _QUANTILES[key] = torch.tensor(key[1], dtype=torch.float32, device=dev).reshape(-1)
+    return tab
+
+
+@torch.no_grad()
+def mip_extras(edges, w, u=(0.05, 0.5, 0.95), near=0.0, far=0.0, ctx=None):
+    """The extras volumetric_rendering leaves behind `compute_extras` (mipnerf360/helper.py:264-274) for an interval histogram:
+    edges (..., n+1) non-decreasing, w (..., n) non-negative -> acc (...,) = sum w, distance_mean (...,) = the expected distance
+    clipped to [t_0, t_n] (t_n on a row without weight) and percentiles (..., len(u)) = sorted_interp(u, integrate_weights(w), t)
+    (helper.py:196-222).  near == far == 0: edges are metric distances; otherwise edges are sdist and t = s_to_t(edges) for that near /
+    far, formed inside the kernel.  u: up to 8 ascending quantiles in [0, 1], a sequence (its device table is kept) or an fp32 device
+    tensor.  No gradients: training.mip_expected_distance is the differentiable (acc, distance_mean)."""
+    edges, w = f32(edges, "edges"), f32(w, "w")
+    n = w.shape[-1]
+    if edges.shape[-1] != n + 1 or edges.shape[:-1] != w.shape[:-1]:
+        raise ValueError("edges must hold one more entry per row than w, got %s %s" % (tuple(edges.shape), tuple(w.shape)))
+    ctx = _ctx(w, ctx)
+    e2, w2 = edges.reshape(-1, n + 1), w.reshape(-1, n)
+    R, dev = w2.shape[0], w.device
+    tab = _quantile_table(u, dev)
+    n_u = tab.numel()
+    acc, mean, pct = torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, n_u, device=dev)
+    _lib.check(ctx.lib.neo_mip_extras(ctx.handle, ptr(e2), ptr(w2), R, n, float(near), float(far), ptr(tab), n_u, ptr(acc), ptr(mean),
+                                      ptr(pct), ctx.stream()))
+    lead = w.shape[:-1]
+    return acc.reshape(lead), mean.reshape(lead), pct.reshape(*lead, n_u)

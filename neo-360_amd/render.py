@@ -38,8 +38,12 @@ def _render_once(model, batch, chunk, white_bkgd, near, far, train_frac):
     if isinstance(model, models.MipNeRF360):
         # mipnerf360/model.py:471-505: train_frac = global_step / max_steps of the trainer; near/far as given
         rend, hist = model(batch, train_frac, False, False, near, far)
+        last = rend[-1]
+        if model.compute_extras:            # depth = the expected distance of the final level, acc the kernel's own sum
+            return dict(rgb=last["rgb"], acc=last["acc"], depth=last["distance_mean"], distance_median=last["distance_median"],
+                        distance_percentile_5=last["distance_percentile_5"], distance_percentile_95=last["distance_percentile_95"])
         w = hist[-1]["weights"]
-        return dict(rgb=rend[-1]["rgb"], acc=w.sum(-1), depth=torch.zeros_like(w[:, 0]))   # the reference returns rgb only
+        return dict(rgb=last["rgb"], acc=w.sum(-1), depth=torch.zeros_like(w[:, 0]))   # the reference returns rgb only
     if isinstance(model, models.NeRF):
         res = model(batch, False, white_bkgd, near, far)     # chunking does not change vanilla results
         return dict(rgb=res[1][0], depth=res[1][2], acc=res[1][1])
@@ -103,7 +107,9 @@ def render_rays_test(model, batch, chunk=1024, white_bkgd=False, near=0.2, far=3
                      on_range="retry_f32", image_width=None, first_ray=0):
     """Fine-level rgb / depth of every ray in `batch` (one image), as the reference's
     render_rays_test returns them: dict(rgb (R,3), depth (R,)) plus `target` /
-    `instance_mask` passed through when present.  check=True waits for the frame and raises what the device-side
+    `instance_mask` passed through when present.  A MipNeRF360 returns depth = 0 (the reference renders rgb only) unless
+    `model.compute_extras` is set: then depth = the final level's expected distance (`distance_mean`), acc the kernel's own
+    sum, and `distance_median` / `distance_percentile_5` / `distance_percentile_95` ride along.  check=True waits for the frame and raises what the device-side
     assertions reported (a ray that missed the unit sphere); check=False leaves that to
     a later `model.check_flags()` (a loop over frames that never wants to block).
 

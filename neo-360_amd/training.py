@@ -1259,6 +1259,10 @@ def mip_render_train(module, batch, train_frac, randomized, near, far, seed=None
         density, rgb = (mip_mlp_fused if getattr(module, "train_fused", True) else mip_mlp)(mlp, x0, d_enc, n, ctx=c)
         weights, colour = mip_composite(rgb, density, tdist, rays_d, 1.0, ctx=c)
         renderings.append({"rgb": colour})
+        if module.compute_extras:
+            acc, mean = mip_expected_distance(sdist, weights, near, far, ctx=c)
+            pct = ops.mip_extras(sdist, weights.detach(), module.EXTRA_QUANTILES, near, far, ctx=c)[2]
+            renderings[-1].update(module._extras_dict(acc, mean, pct))
         history.append(dict(density=density, rgb=rgb, sdist=sdist, weights=weights))
     module._raise_flags(c.poll_flags())
     return renderings, history
@@ -1353,6 +1357,46 @@ def lossfun_distortion(t, w, ctx=None):
     implemented - mip_render_train returns a detached sdist - and a t that requires grad raises ValueError."""
     _no_edge_grad(t, "t", "lossfun_distortion")
     return _LossfunDistortion.apply(t, w, ctx)
+
+
+class _MipExpectedDistance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx_, edges, w, near, far, lib_ctx):
+        n = w.shape[-1]
+        if edges.shape[-1] != n + 1 or edges.shape[:-1] != w.shape[:-1]:
+            raise ValueError("edges must hold one more entry per row than w, got %s %s" % (tuple(edges.shape), tuple(w.shape)))
+        e2, w2 = f32(edges, "edges").reshape(-1, n + 1), f32(w, "w").reshape(-1, n)
+        R = w2.shape[0]
+        c = _ctx(w2, lib_ctx)
+        acc, mean = torch.empty(R, device=w2.device), torch.empty(R, device=w2.device)
+        _lib.check(c.lib.neo_mip_extras(c.handle, ptr(e2), ptr(w2), R, n, float(near), float(far), None, 0, ptr(acc), ptr(mean), None,
+                                        c.stream()))
+        ctx_.save_for_backward(e2, w2)
+        ctx_.meta = (c, float(near), float(far), tuple(w.shape))
+        return acc.reshape(w.shape[:-1]), mean.reshape(w.shape[:-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx_, g_acc, g_mean):
+        e2, w2 = ctx_.saved_tensors
+        c, near, far, w_shape = ctx_.meta
+        if not ctx_.needs_input_grad[1]:
+            return (None,) * 5
+        R, n = w2.shape
+        ga, gm = f32(g_acc.reshape(R).contiguous(), "g_acc"), f32(g_mean.reshape(R).contiguous(), "g_mean")
+        g_w = torch.empty(R, n, device=w2.device)
+        _lib.check(c.lib.neo_mip_extras_backward(c.handle, ptr(e2), ptr(w2), R, n, near, far, ptr(ga), ptr(gm), ptr(g_w), c.stream()))
+        return None, g_w.reshape(w_shape), None, None, None
+
+
+def mip_expected_distance(edges, w, near=0.0, far=0.0, ctx=None):
+    """(acc, distance_mean) of ops.mip_extras under autograd (neo_mip_extras / neo_mip_extras_backward): edges (..., n+1), w (..., n)
+    -> acc (...,) = sum w and distance_mean (...,) = clip(sum w_i (t_i + t_{i+1}) / 2 / acc, t_0, t_n), t = edges when
+    near == far == 0 and s_to_t(edges) otherwise.  Gradient to w: g_acc + g_mean (midpoint - mean) / acc; on a row with acc == 0 the
+    second term is defined as 0 and distance_mean is t_n.  Edges carry no gradient (a t that requires grad raises ValueError), and the
+    percentiles of ops.mip_extras are not differentiable."""
+    _no_edge_grad(edges, "edges", "mip_expected_distance")
+    return _MipExpectedDistance.apply(edges, w, near, far, ctx)
 
 
 def mip_interlevel_loss(ray_history):
