@@ -137,6 +137,14 @@ int neo_aabb_multi(neo_ctx* ctx, int n_boxes, const double* world_to_box, const 
                    const double* rays_o, const double* rays_d, int R, uint8_t* hit_per_box, float* near,
                    float* far, uint8_t* mask, void* stream);
 
+/* models/neo360/helper.py:375-394 sample_rays_in_bbox_list: the same box-frame transform and slab test as neo_aabb_multi, with the
+ * interval of EVERY box kept instead of the merged one.  Outputs (any may be NULL): near (n_boxes,R) / far (n_boxes,R) float32 =
+ * tmin / tmax rounded to float32, 0 where the ray misses the box (the reference's "no hit" sentinel); hit (n_boxes,R) uint8
+ * (bit-exact contract; the hit_per_box of neo_aabb_multi). */
+int neo_aabb_per_box(neo_ctx* ctx, int n_boxes, const double* world_to_box, const double* bounds,
+                     const double* rays_o, const double* rays_d, int R, float* near, float* far, uint8_t* hit,
+                     void* stream);
+
 /* models/neo360/helper.py:253-273 intersect_sphere.  far (R); ok (R) uint8 =
  * (1-|p|^2 >= 0), may be NULL; a miss also raises flag bit0. */
 int neo_intersect_sphere(neo_ctx* ctx, const float* rays_o, const float* rays_d, int R,
@@ -296,6 +304,36 @@ int neo_tp_render_objects(neo_ctx* ctx, const float* rays_o, const float* rays_d
                           const float* near_obj, const float* far_obj, int R, int chunk, const float* src_poses, int NV,
                           float focal, float cx, float cy, int n_coarse, int n_fine, int white_bkgd,
                           const neo_tp_object_out* level0, const neo_tp_object_out* level1, int* hits_out, void* stream);
+
+/* EVERY INSTANCE of a scene in one call: K per-instance intervals near_inst / far_inst (K,R floats each, device; e.g. the output of
+ * neo_aabb_per_box), 0 <= K <= 32.  Pair (i, ray) is rendered exactly as neo_tp_render_objects renders `ray` between near_inst[i],
+ * far_inst[i] - same evaluators, same quirk-Q1 direction index from the ray's own index, R and `chunk` - and the instances of a
+ * ray are then composited in depth order.  No background, no sphere intersection and no sphere assertion.
+ * HIT RULE (per pair, that of neo_tp_render_objects): lo = max(near_inst, 1e-4), hi = far_inst; a pair is a hit iff both bounds
+ * are finite and hi > lo; the test is the negation of the failing comparisons, so a NaN bound makes the pair a miss.
+ * The hit pairs are compacted in ascending (instance, ray) order (deterministic, no atomics; the count stays on the device) and
+ * consumed in K WINDOWS of at most R rows: window p is rows [p R, p R + min(max(count - p R, 0), R)) of the pair list, one compact
+ * launch chain of neo_tp_render_objects each (a compact launch holds at most R rows); an empty window's kernels leave at once.
+ * PER-INSTANCE outputs rgb (K,R,3), acc (K,R), depth (K,R): row i is bitwise neo_tp_render_objects(near_inst[i], far_inst[i],
+ * white_bkgd), missed pairs included (rgb = white_bkgd ? 1 : 0, acc = depth = 0).
+ * COMPOSITE outputs comp_rgb (R,3), comp_acc (R), comp_depth (R), instance_id (R) int32: one thread per ray, plain fp32, in
+ * exactly this order.  The ray's hit instances are taken in ascending lo, ties to the lower instance index; p_i = the instance's
+ * premultiplied colour (its white_bkgd = 0 rgb), a_i = its acc, d_i = its depth.  COMPOSITE RECURRENCE: T = 1, rgb = depth = acc
+ * = 0, best = 0, id = -1; for each instance in order: v = T * a_i; rgb += T * p_i; depth += T * d_i; acc += v; if v > best then
+ * best = v, id = i; T = T * (1 - a_i).  Afterwards, if white_bkgd: rgb += 1 - acc.  A ray without hits gets rgb = white_bkgd ? 1 : 0,
+ * acc = depth = 0, id = -1.  instance_id is the instance that contributes the largest visibility v to the ray (the counterpart
+ * of the dataset's instance_mask).  Intervals of overlapping boxes are marched independently: density inside an overlap counts
+ * twice.
+ * Any output, and either level struct, may be NULL.  pairs_out [device, may be NULL]: receives the number of hit pairs; the call
+ * never reads it on the host and synchronises nothing.  K == 0 writes the no-hit composite; R == 0 zeroes pairs_out and returns. */
+typedef struct {
+    float* rgb; float* acc; float* depth;                                  /* per instance: (K,R,3), (K,R), (K,R) */
+    float* comp_rgb; float* comp_acc; float* comp_depth; int* instance_id; /* composite: (R,3), (R), (R), (R) */
+} neo_tp_instance_out;
+int neo_tp_render_instances(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs,
+                            const float* near_inst, const float* far_inst, int K, int R, int chunk, const float* src_poses, int NV,
+                            float focal, float cx, float cy, int n_coarse, int n_fine, int white_bkgd,
+                            const neo_tp_instance_out* level0, const neo_tp_instance_out* level1, int* pairs_out, void* stream);
 
 /* ---- scene encoder: pillar stage -------------------------------------------------------- */
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).
@@ -693,7 +731,7 @@ int neo_ctx_read_timing(neo_ctx* ctx, double* total_ms, int* launches, double* t
  * 7 NeRF MLP layer by layer - one span covers all batches of the call -, 8 exact fp32), points and algorithmic flops of each.  A NeO-360 frame is four
  * launches (inside / outside the sphere x coarse / fine) and, in pre-projection mode 3, two different kernels: the bench's
  * roofline object prices each kernel with ITS launches.  The two compact background launches of neo_tp_render_culled and the two
- * compact launches of neo_tp_render_objects record points = flops = 0: how many rows they evaluated is known on the device only.  Arrays may be NULL; *count = launches recorded (may exceed capacity). */
+ * compact launches of neo_tp_render_objects (and the 2 K of neo_tp_render_instances) record points = flops = 0: how many rows they evaluated is known on the device only.  Arrays may be NULL; *count = launches recorded (may exceed capacity). */
 int neo_ctx_read_spans(neo_ctx* ctx, int capacity, double* ms, int* kernel_id, double* points, double* flops, int* count);
 
 #ifdef __cplusplus

@@ -34,6 +34,10 @@ class TpObjectOut(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("rgb", "acc", "depth", "tvals")]
 
 
+class TpInstanceOut(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("rgb", "acc", "depth", "comp_rgb", "comp_acc", "comp_depth", "instance_id")]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares
 SIGNATURES = {
     "neo_abi_version": (_i, []),
@@ -53,6 +57,8 @@ SIGNATURES = {
     "neo_raygen_range": (_i, [_vp, _i, _i, _f, c_float_p, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "neo_aabb_multi": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp, _vp, _i,
                             _vp, _vp, _vp, _vp, _vp]),
+    "neo_aabb_per_box": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp, _vp, _i,
+                              _vp, _vp, _vp, _vp]),
     "neo_aabb_intersect": (_i, [_vp, ctypes.POINTER(ctypes.c_double), _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "neo_intersect_sphere": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "neo_pos_enc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
@@ -71,6 +77,8 @@ SIGNATURES = {
                                   ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), _f, _vp, _vp]),
     "neo_tp_render_objects": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,
                                    ctypes.POINTER(TpObjectOut), ctypes.POINTER(TpObjectOut), _vp, _vp]),
+    "neo_tp_render_instances": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,
+                                     ctypes.POINTER(TpInstanceOut), ctypes.POINTER(TpInstanceOut), _vp, _vp]),
     "neo_enc_upload": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_enc_floorplans": (_i, [_vp, _vp, _i, _i, _i, _f, _f, c_float_p, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "neo_enc_train_tape_floats": (ctypes.c_long, [_i, _i, _i, _i]),

@@ -416,14 +416,8 @@ int neo_raygen_range(neo_ctx* ctx, int H, int W, float focal, const float* c2w, 
     return check_launch();
 }
 
-int neo_aabb_multi(neo_ctx* ctx, int n_boxes, const double* world_to_box, const double* bounds, const double* rays_o,
-                   const double* rays_d, int R, uint8_t* hit_per_box, float* near, float* far, uint8_t* mask,
-                   void* stream) {
-    ENTER(ctx);
-    REQUIRE(R >= 0 && n_boxes >= 1 && n_boxes <= 4096, "bad ray / box count");
-    if (R == 0) return NEO_OK;
-    REQUIRE(world_to_box && bounds && rays_o && rays_d, "null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// box frames + bounds of n_boxes oriented boxes into the context's buffer (synchronises the stream: the staging copy is pageable)
+static int upload_boxes(neo_ctx* ctx, int n_boxes, const double* world_to_box, const double* bounds, hipStream_t s) {
     std::vector<neo::BoxFrame> h(n_boxes);
     for (int b = 0; b < n_boxes; ++b) {
         for (int i = 0; i < 12; ++i) h[b].m[i] = world_to_box[b * 16 + i];
@@ -432,7 +426,31 @@ int neo_aabb_multi(neo_ctx* ctx, int n_boxes, const double* world_to_box, const 
     if (ctx->boxes.reserve(h.size() * sizeof(neo::BoxFrame))) return NEO_ERR_NOMEM;
     HIP_TRY(hipMemcpyAsync(ctx->boxes.p, h.data(), h.size() * sizeof(neo::BoxFrame), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));          // `h` is pageable host memory about to go out of scope
+    return NEO_OK;
+}
+
+int neo_aabb_multi(neo_ctx* ctx, int n_boxes, const double* world_to_box, const double* bounds, const double* rays_o,
+                   const double* rays_d, int R, uint8_t* hit_per_box, float* near, float* far, uint8_t* mask,
+                   void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && n_boxes >= 1 && n_boxes <= 4096, "bad ray / box count");
+    if (R == 0) return NEO_OK;
+    REQUIRE(world_to_box && bounds && rays_o && rays_d, "null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = upload_boxes(ctx, n_boxes, world_to_box, bounds, s)) return rc;
     neo::launch_aabb_multi(ctx->boxes.as<neo::BoxFrame>(), n_boxes, rays_o, rays_d, R, hit_per_box, near, far, mask, s);
+    return check_launch();
+}
+
+int neo_aabb_per_box(neo_ctx* ctx, int n_boxes, const double* world_to_box, const double* bounds, const double* rays_o,
+                     const double* rays_d, int R, float* near, float* far, uint8_t* hit, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && n_boxes >= 1 && n_boxes <= 4096, "bad ray / box count");
+    if (R == 0) return NEO_OK;
+    REQUIRE(world_to_box && bounds && rays_o && rays_d, "null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = upload_boxes(ctx, n_boxes, world_to_box, bounds, s)) return rc;
+    neo::launch_aabb_per_box(ctx->boxes.as<neo::BoxFrame>(), n_boxes, rays_o, rays_d, R, near, far, hit, s);
     return check_launch();
 }
 

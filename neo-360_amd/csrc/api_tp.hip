@@ -167,6 +167,13 @@ int neo_tp_eval_region(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo
     return tp_launch(ctx, sl, sc, views, rays_o, rays_d, viewdirs, tvals, far, R, N, chunk, out, s);
 }
 
+// one COMPACT inside-sphere evaluator launch (rows are map[] entries, *count of them) for other translation units (instances.hip)
+int neo_tp_eval_compact(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
+                        const float* rays_d, const float* viewdirs, const float* tvals, int R, int N, int chunk, float* out,
+                        const int* map, const int* count, hipStream_t s) {
+    return tp_launch(ctx, ctx->tp[slot], sc, views, rays_o, rays_d, viewdirs, tvals, nullptr, R, N, chunk, out, s, map, count);
+}
+
 extern "C" {
 
 int neo_tp_upload_mlp(neo_ctx* ctx, int slot, int input_ch, const float* const* weights,

@@ -15,6 +15,9 @@ struct BoxFrame {        // one oriented box: world -> box frame (row-major 3x4 
 };
 void launch_aabb_multi(const BoxFrame* boxes_dev, int n_boxes, const double* rays_o, const double* rays_d, int R,
                        uint8_t* hit_per_box, float* near, float* far, uint8_t* mask, hipStream_t s);
+// the same transform and slab test, every box's own interval: near / far (n_boxes, R) float32 with 0 = no hit, hit (n_boxes, R)
+void launch_aabb_per_box(const BoxFrame* boxes_dev, int n_boxes, const double* rays_o, const double* rays_d, int R, float* near,
+                         float* far, uint8_t* hit, hipStream_t s);
 void launch_aabb(const double* bounds, const double* rays_o, const double* rays_d, int R, uint8_t* hit,
                  double* tmin, double* tmax, hipStream_t s);
 void launch_sphere(const float* rays_o, const float* rays_d, int R, float* far, uint8_t* ok, uint32_t* flags,
@@ -336,5 +339,28 @@ void launch_obj_level0(const float* near_obj, const float* far_obj, const float*
 // acc = depth = 0 and a zero t row.  Any output may be null.
 void launch_obj_scatter(const int* slot, int R, int N, const float* rgb_c, const float* acc_c, const float* depth_c,
                         const float* t_c, int white_bkgd, float* rgb, float* acc, float* depth, float* tvals, hipStream_t s);
+
+// instances.hip - instance render of neo_tp_render_instances: the hit (instance, ray) PAIRS of K x R intervals, pair = i R + ray,
+// compacted as above over K R elements (the hit rule of objects.hip per pair) and consumed in K windows of at most R rows
+size_t inst_ws_ints(int K, int R);      // [cull_ws_ints(K R) | ray map of the current window R | window counts K]
+inline int* inst_raymap_of(int* ws, int K, int R) { return ws + cull_ws_ints(K * R); }
+inline int* inst_wcount_of(int* ws, int K, int R) { return inst_raymap_of(ws, K, R) + R; }
+// pair map / count at cull_map_of / cull_count_of (ws, K R); wcount[p] = min(max(count - p R, 0), R); *count_out = count
+void launch_inst_compact(const float* near_inst, const float* far_inst, int K, int R, int* ws, int* count_out, hipStream_t s);
+// one window's compact level-0 rows as launch_obj_level0, from the pair's own interval; raymap[k] = pair_map[k] % R
+void launch_inst_level0(const float* near_inst, const float* far_inst, const float* rays_d, const float* edges, const int* pair_map,
+                        const int* count, int R, int N, float* t0_c, float* far_c, float* rays_d_c, int* raymap, hipStream_t s);
+// missed pairs of the per-instance outputs (any may be null): rgb = white_bkgd ? 1 : 0, acc = depth = 0
+void launch_inst_fill_misses(const float* near_inst, const float* far_inst, long pairs, int white_bkgd, float* rgb, float* acc,
+                             float* depth, hipStream_t s);
+// one window's compact results (composited WITHOUT white) to their pairs: prem_* (K R) keep them as they are, the per-instance
+// outputs (any may be null) get rgb + (1 - acc) when white_bkgd - the arithmetic of k_composite's white background
+void launch_inst_scatter(const int* pair_map, const int* count, int R, const float* rgb_c, const float* acc_c, const float* depth_c,
+                         int white_bkgd, float* prem_rgb, float* prem_acc, float* prem_depth, float* rgb, float* acc, float* depth,
+                         hipStream_t s);
+// depth-ordered composite of a ray's hit instances (include/neo360_hip.h: COMPOSITE RECURRENCE); any output may be null
+void launch_inst_composite(const float* near_inst, const float* far_inst, int K, int R, const float* prem_rgb, const float* prem_acc,
+                           const float* prem_depth, int white_bkgd, float* rgb, float* acc, float* depth, int* instance_id,
+                           hipStream_t s);
 
 }  // namespace neo

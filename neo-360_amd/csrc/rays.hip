@@ -152,6 +152,32 @@ __global__ void k_aabb_multi(const BoxFrame* __restrict__ boxes, int n_boxes, co
     if (mask) mask[r] = (all_near != 0.0f && all_far != 0.0f) ? 1 : 0;
 }
 
+// models/neo360/helper.py:375-394: sample_rays_in_bbox_list keeps every box's own interval.  One lane per (box, ray): the
+// transform and slab test of k_aabb_multi, tmin / tmax rounded to float32 with 0 as "no hit".
+__global__ void k_aabb_per_box(const BoxFrame* __restrict__ boxes, int n_boxes, const double* __restrict__ rays_o,
+                               const double* __restrict__ rays_d, int R, float* __restrict__ near_out,
+                               float* __restrict__ far_out, uint8_t* __restrict__ hit) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (r >= R) return;
+    const double o[3] = {rays_o[r * 3], rays_o[r * 3 + 1], rays_o[r * 3 + 2]};
+    const double d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
+    const BoxFrame& B = boxes[b];
+    double ob[3], db[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double* row = B.m + a * 4;
+        ob[a] = __builtin_fma(row[2], o[2], __builtin_fma(row[1], o[1], row[0] * o[0])) + row[3];
+        db[a] = __builtin_fma(row[2], d[2], __builtin_fma(row[1], d[1], row[0] * d[0]));
+    }
+    double tmin, tmax;
+    const bool ok = slab_test(B.lo, B.hi, ob, db, tmin, tmax);
+    const long idx = (long)b * R + r;
+    if (near_out) near_out[idx] = ok ? (float)tmin : 0.0f;       // torch.Tensor(float64 array)
+    if (far_out) far_out[idx] = ok ? (float)tmax : 0.0f;
+    if (hit) hit[idx] = ok ? 1 : 0;
+}
+
 // models/neo360/helper.py:253-273.
 __global__ void k_sphere(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int R,
                          float* __restrict__ far, uint8_t* __restrict__ ok_out, uint32_t* flags) {
@@ -177,6 +203,12 @@ void launch_aabb_multi(const BoxFrame* boxes, int n_boxes, const double* rays_o,
                        uint8_t* hit_per_box, float* near, float* far, uint8_t* mask, hipStream_t s) {
     hipLaunchKernelGGL(k_aabb_multi, dim3((R + 255) / 256), dim3(256), 0, s, boxes, n_boxes, rays_o, rays_d, R,
                        hit_per_box, near, far, mask);
+}
+
+void launch_aabb_per_box(const BoxFrame* boxes, int n_boxes, const double* rays_o, const double* rays_d, int R, float* near,
+                         float* far, uint8_t* hit, hipStream_t s) {
+    hipLaunchKernelGGL(k_aabb_per_box, dim3((R + 255) / 256, n_boxes), dim3(256), 0, s, boxes, n_boxes, rays_o, rays_d, R, near,
+                       far, hit);
 }
 
 void launch_aabb(const double* bounds, const double* rays_o, const double* rays_d, int R, uint8_t* hit,

@@ -459,6 +459,7 @@ class NeRF_TP(_HipModule):
         self.cull_background = None
         self.last_cull_survivors = None      # int32 device tensor: rays of the last culled call that kept their background
         self.last_object_hits = None         # int32 device tensor: rays of the last render_objects call that had a box interval
+        self.last_instance_pairs = None      # int32 device tensor: hit (instance, ray) pairs of the last render_instances call
 
     @property
     def cull_background(self):
@@ -822,6 +823,86 @@ class NeRF_TP(_HipModule):
         if return_samples:
             out.append((levels[0]["tvals"], levels[1]["tvals"]))
         return out
+
+
+    MAX_INSTANCES = 32
+
+    @classmethod
+    def _instance_bound(cls, t, key, B, dev):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise ValueError("%s must be a floating-point tensor, got %r" % (key, type(t).__name__ if not isinstance(t, torch.Tensor) else t.dtype))
+        if not (t.dim() in (2, 3) and t.shape[1] == B and (t.dim() == 2 or t.shape[2] == 1)):
+            raise ValueError("%s must have shape (K, %d) or (K, %d, 1): one row per instance, like the rays, got %s" % (key, B, B, tuple(t.shape)))
+        if t.shape[0] > cls.MAX_INSTANCES:
+            raise ValueError("%s holds %d instances, at most %d are supported" % (key, t.shape[0], cls.MAX_INSTANCES))
+        if t.device != dev:
+            raise ValueError("%s must be on the rays' device (%s), got %s" % (key, dev, t.device))
+        return t
+
+    @torch.no_grad()
+    def render_instances(self, rays, near_inst, far_inst, white_bkgd=True, chunk=None, per_instance=True):
+        """Every instance of a scene in ONE call (neo_tp_render_instances), with the depth-ordered composite of the instances and
+        the visible-instance id of every ray.  near_inst / far_inst: (K,B) or (K,B,1), any float dtype, on the rays' device,
+        0 <= K <= 32 - what `ops.sample_rays_in_bbox_list` returns.  Deterministic (randomized=False), no background, no
+        unit-sphere intersection or assertion, exactly as `render_objects`; reads neither `cull_background` nor `ray_grid`;
+        `chunk` as in forward.
+
+        Pair (i, ray) is a hit by the rule of `render_objects` on near_inst[i, ray], far_inst[i, ray]: lo = max(near, 1e-4),
+        hi = far, hit iff both are finite and hi > lo (a NaN bound is a miss).  The hit pairs are compacted on the device and
+        evaluated in K windows of at most B rows on the kernels of `render_objects`.
+
+        Returns dict(instances=..., composite=...), two levels each:
+          instances  [(rgb (K,B,3), acc (K,B), depth (K,B))] - row i is BITWISE `render_objects(rays, near_inst[i], far_inst[i],
+                     white_bkgd, chunk)`, missed rays included (rgb = 1 or 0, acc = depth = 0); None when per_instance=False;
+          composite  [(rgb (B,3), acc (B,), depth (B,), instance_id (B,) int32)] - the ray's hit instances in ascending lo (ties
+                     to the lower index), each with its premultiplied colour p_i (its white_bkgd=False rgb), a_i = acc, d_i =
+                     depth; from T = 1, rgb = depth = acc = 0, best = 0, id = -1: v = T a_i; rgb += T p_i; depth += T d_i;
+                     acc += v; if v > best: best = v, id = i; T = T (1 - a_i); then rgb += 1 - acc if white_bkgd.  Plain fp32
+                     in that order.  A ray without hits: rgb = 1 or 0, acc = depth = 0, id = -1.
+        Intervals of overlapping boxes are marched independently, so density inside an overlap counts twice.
+        `last_instance_pairs` receives the number of hit pairs as a device int32 scalar that this call never reads."""
+        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
+        B = raw[0].shape[0]
+        raw_near = self._instance_bound(near_inst, "near_inst", B, raw[0].device)
+        raw_far = self._instance_bound(far_inst, "far_inst", B, raw[0].device)
+        K = raw_near.shape[0]
+        if raw_far.shape[0] != K:
+            raise ValueError("near_inst holds %d instances, far_inst %d" % (K, raw_far.shape[0]))
+        rays_o = f32(raw[0], "rays_o")
+        rays_d = f32(raw[1], "rays_d")
+        viewdirs = f32(raw[2], "viewdirs")
+        near_c = f32(raw_near, "near_inst").reshape(K, B)
+        far_c = f32(raw_far, "far_inst").reshape(K, B)
+        dev = rays_o.device
+        ctx = self._context(dev)
+        self._ensure_scene(rays, dev)
+        if self._scene_ctx is not ctx:
+            raise _lib.NeoError("scene features were uploaded on a different device")
+        self._sync_weights(ctx)
+        self._before_call(ctx)
+        host_poses, NV, focal, cx, cy = self._camera_args(rays)
+        levels = []
+
+        def launch():
+            structs = []
+            for _ in range(2):
+                t = dict(comp_rgb=torch.empty(B, 3, device=dev), comp_acc=torch.empty(B, device=dev),
+                         comp_depth=torch.empty(B, device=dev), instance_id=torch.empty(B, dtype=torch.int32, device=dev))
+                if per_instance:
+                    t.update(rgb=torch.empty(K, B, 3, device=dev), acc=torch.empty(K, B, device=dev), depth=torch.empty(K, B, device=dev))
+                levels.append(t)
+                structs.append(_lib.TpInstanceOut(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpInstanceOut._fields_)))
+            pairs = torch.empty((), dtype=torch.int32, device=dev)    # written by the compaction, never read inside the call
+            _lib.check(ctx.lib.neo_tp_render_instances(
+                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(near_c), ptr(far_c), K, B, int(chunk or max(B, 1)), host_poses,
+                NV, focal, cx, cy, self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
+                ctypes.byref(structs[0]), ctypes.byref(structs[1]), pairs.data_ptr(), ctx.stream()))
+            self._after_call(ctx)
+            return [v for t in levels for v in t.values()] + [pairs]
+        made = self._launch_overlapped(ctx, dev, raw + (raw_near, raw_far), (rays_o, rays_d, viewdirs, near_c, far_c), launch)
+        self.last_instance_pairs = made[-1]
+        return dict(instances=[(t["rgb"], t["acc"], t["depth"]) for t in levels] if per_instance else None,
+                    composite=[(t["comp_rgb"], t["comp_acc"], t["comp_depth"], t["instance_id"]) for t in levels])
 
 
 class PixelNeRFMLP(nn.Module):

@@ -53,16 +53,9 @@ def bbox_intersection_batch(bounds, rays_o, rays_d, ctx=None):
     return hit, tmin, tmax
 
 
-def sample_rays_in_bbox(RTs, rays_o, view_dirs, ctx=None, return_per_box=False):
-    """models/neo360/helper.py:359-373 (with get_object_rays_in_bbox :348-357 and get_rays_in_bbox :333-346 inside):
-    RTs = dict(R=[3x3 or 9], T=[3], s=[(2,3) bounds]) per object; rays are moved into every box frame in float64,
-    slab-tested, and merged with 0 as the "no hit" sentinel.  rays_o / view_dirs: (R,3) device tensors (any float
-    dtype; the reference's NumPy arrays are promoted to float64 the same way).  Returns all_near (R,1), all_far (R,1)
-    float32 and bbox_mask (R,1) bool, as the reference; with return_per_box also the per-box hit masks (n,R)."""
+def _box_tables(RTs):
+    """Host tables of the boxes of an `RTs` dict: (n, 16 n doubles of world -> box frames, 6 n doubles of bounds)."""
     import numpy as np
-    rays_o, view_dirs = f64(rays_o, "rays_o"), f64(view_dirs, "view_dirs")
-    ctx = _ctx(rays_o, ctx)
-    R = rays_o.shape[0]
     mats, bounds = [], []
     for rot, tran, sca in zip(RTs["R"], RTs["T"], RTs["s"]):
         box = np.eye(4)                                         # helper.py:352-356, verbatim order of operations
@@ -71,6 +64,23 @@ def sample_rays_in_bbox(RTs, rays_o, view_dirs, ctx=None, return_per_box=False):
         mats.append(np.linalg.inv(box))
         bounds.append(np.asarray(sca, dtype=np.float64).reshape(6))
     n = len(mats)
+    if n == 0:
+        return 0, None, None
+    hm = (ctypes.c_double * (16 * n))(*np.stack(mats).astype(np.float64).reshape(-1).tolist())
+    hb = (ctypes.c_double * (6 * n))(*np.stack(bounds).reshape(-1).tolist())
+    return n, hm, hb
+
+
+def sample_rays_in_bbox(RTs, rays_o, view_dirs, ctx=None, return_per_box=False):
+    """models/neo360/helper.py:359-373 (with get_object_rays_in_bbox :348-357 and get_rays_in_bbox :333-346 inside):
+    RTs = dict(R=[3x3 or 9], T=[3], s=[(2,3) bounds]) per object; rays are moved into every box frame in float64,
+    slab-tested, and merged with 0 as the "no hit" sentinel.  rays_o / view_dirs: (R,3) device tensors (any float
+    dtype; the reference's NumPy arrays are promoted to float64 the same way).  Returns all_near (R,1), all_far (R,1)
+    float32 and bbox_mask (R,1) bool, as the reference; with return_per_box also the per-box hit masks (n,R)."""
+    rays_o, view_dirs = f64(rays_o, "rays_o"), f64(view_dirs, "view_dirs")
+    ctx = _ctx(rays_o, ctx)
+    R = rays_o.shape[0]
+    n, hm, hb = _box_tables(RTs)
     dev = rays_o.device
     if n == 0:
         # a scene without objects: the reference's loops never run and its zero-initialised outputs come back
@@ -80,8 +90,6 @@ def sample_rays_in_bbox(RTs, rays_o, view_dirs, ctx=None, return_per_box=False):
         if return_per_box:
             return zero, zero.clone(), mask, torch.empty(0, R, dtype=torch.uint8, device=dev)
         return zero, zero.clone(), mask
-    hm = (ctypes.c_double * (16 * n))(*np.stack(mats).astype(np.float64).reshape(-1).tolist())
-    hb = (ctypes.c_double * (6 * n))(*np.stack(bounds).reshape(-1).tolist())
     near = torch.empty(R, 1, device=dev)
     far = torch.empty(R, 1, device=dev)
     mask = torch.empty(R, 1, dtype=torch.uint8, device=dev)
@@ -91,6 +99,26 @@ def sample_rays_in_bbox(RTs, rays_o, view_dirs, ctx=None, return_per_box=False):
     if return_per_box:
         return near, far, mask.bool(), per_box
     return near, far, mask.bool()
+
+
+def sample_rays_in_bbox_list(RTs, rays_o, view_dirs, ctx=None):
+    """models/neo360/helper.py:375-394: the interval of EVERY box instead of the merged one (which keeps the smallest near and
+    the smallest far over the boxes a ray meets, so a ray that clips a front box never reaches the object behind it).  Inputs as
+    sample_rays_in_bbox, the same float64 transform and slab test.  Returns all_near (K,R,1), all_far (K,R,1) float32 with the
+    reference's 0 = "no hit" sentinel (its stacked shape) and hit (K,R) bool - the reference's third value is a leftover of its
+    loop, ours is the mask.  K = 0 returns empty tensors.  What `NeRF_TP.render_instances` takes as near_inst / far_inst."""
+    rays_o, view_dirs = f64(rays_o, "rays_o"), f64(view_dirs, "view_dirs")
+    ctx = _ctx(rays_o, ctx)
+    R = rays_o.shape[0]
+    n, hm, hb = _box_tables(RTs)
+    dev = rays_o.device
+    near = torch.empty(n, R, 1, device=dev)
+    far = torch.empty(n, R, 1, device=dev)
+    hit = torch.empty(n, R, dtype=torch.uint8, device=dev)
+    if n:
+        _lib.check(ctx.lib.neo_aabb_per_box(ctx.handle, n, hm, hb, ptr(rays_o), ptr(view_dirs), R, ptr(near), ptr(far), ptr(hit),
+                                            ctx.stream()))
+    return near, far, hit.bool()
 
 
 def intersect_sphere(rays_o, rays_d, ctx=None, check=True):

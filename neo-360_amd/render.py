@@ -155,6 +155,32 @@ def render_object_rays(model, batch, chunk=1024, white_bkgd=True, check=True, on
 
 
 @torch.no_grad()
+def render_instance_rays(model, batch, RTs=None, chunk=1024, white_bkgd=True, check=True, on_range="retry_f32"):
+    """Instance-level frame of a NeRF_TP module: the fine level of `model.render_instances` on every ray of `batch` in one
+    library call, with the reference chunk size passed down.  The per-instance intervals are batch["near_inst"] /
+    batch["far_inst"] ((K,R) or (K,R,1)) when present, else they are computed from `RTs` (the reference's dict of boxes) with
+    ops.sample_rays_in_bbox_list.  Returns dict(rgb (R,3), depth (R,), acc (R,), instance_id (R,) int32) - the depth-ordered
+    composite of the instances and the visible instance of every ray (-1: none) - plus `instances` = (rgb (K,R,3), acc (K,R),
+    depth (K,R)), row i bitwise render_object_rays on instance i's interval, and `target` / `instance_mask` passed through.
+    check / on_range: the flag read, range-guard retry and latch of render_rays_test (the same code path)."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("render_instance_rays renders NeRF_TP modules, got %r" % type(model))
+    if "near_inst" in batch and "far_inst" in batch:
+        near, far = batch["near_inst"], batch["far_inst"]
+    elif RTs is not None:
+        from . import ops
+        near, far, _ = ops.sample_rays_in_bbox_list(RTs, batch["rays_o"], batch["viewdirs"])
+    else:
+        raise ValueError("render_instance_rays needs the per-instance intervals: batch['near_inst'] / batch['far_inst'], or RTs")
+
+    def once():
+        res = model.render_instances(batch, near, far, white_bkgd=white_bkgd, chunk=chunk)
+        rgb, acc, depth, ids = res["composite"][1]
+        return dict(rgb=rgb, depth=depth, acc=acc, instance_id=ids, instances=res["instances"][1])
+    return _render_guarded(model, batch, once, check, on_range)
+
+
+@torch.no_grad()
 def render_frame_sharded(model, batch, world, rank, chunk=1024, white_bkgd=False, near=0.2, far=3.0, group=None,
                          gather=True, train_frac=1.0, n_rays=None, out=None, reuse=False, check=True, always_gather=False,
                          info=None, image_width=None):
