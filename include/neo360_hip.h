@@ -90,6 +90,15 @@ int neo_ctx_set_lane(neo_ctx* ctx, int lane);
  * (default) removes it; width must be a multiple of 8.  The reference has no counterpart (its chunk loop renders 1024 consecutive
  * rays at a time; datasets/ray_utils.py:96-104 defines the row-major order). */
 int neo_ctx_set_ray_grid(neo_ctx* ctx, int width, long first_ray);
+/* Quad order of the NeO-360 pre-projected split evaluators.  A 64-point tile normally holds 64 consecutive samples of one ray; in
+ * quad order it holds 64 / G samples of G consecutive rays of the launch (G = 4, a quad: with the pixel-grid hint a 2 x 2 pixel patch
+ * inside the unit sphere, four adjacent pixels of a patch row outside; without it four consecutive rays of the caller; G = 8 / 16:
+ * two / four such quads), so that the four rows behind one gather instruction are neighbouring rays at one sample index and fall
+ * on almost the same texels.  Pure scheduling: every output value is bitwise the one of the ray-major order.  mode -1 (default): the
+ * library's per-launch choice (api_tp.hip:tp_launch; $NEO_TP_QUAD, read once, replaces that choice: 0, 1 or a group size); 0:
+ * ray-major everywhere; 1: quads of four in every launch that can take them (compact launches - culled background, objects,
+ * instances - never do); 4 / 8 / 16: that many rays per group everywhere (4 is 1).  The setter wins over the environment variable. */
+int neo_ctx_set_tp_quad(neo_ctx* ctx, int mode);
 
 /* Arithmetic of the per-point MLP GEMMs of every renderer (vanilla, NeRF_TP, Mip-NeRF 360, PixelNeRF).
  * 1 (the context default, and the default of the Python modules, "f16x3"): fp16 MFMA with every fp32

@@ -117,6 +117,15 @@ class Context:
             _lib.check(self.lib.neo_ctx_set_ray_grid(self.handle, key[0], key[1]))
             self._ray_grid = key
 
+    def set_tp_quad(self, mode):
+        """Quad order of the NeO-360 pre-projected split evaluators (neo_ctx_set_tp_quad): None / -1 = the library's per-launch
+        default, False / 0 = ray-major everywhere, True / 1 = quads of four rays everywhere, 4 / 8 / 16 = that many rays per group
+        everywhere.  Bitwise-neutral."""
+        code = -1 if mode is None else int(mode)
+        if getattr(self, "_tp_quad", -1) != code:
+            _lib.check(self.lib.neo_ctx_set_tp_quad(self.handle, code))
+            self._tp_quad = code
+
     def set_precision(self, mode):
         """'f32' (exact fp32 MFMA) or 'f16x3' (fp16 MFMA, hi/lo-split operands, fp32-equivalent)."""
         code = {"f32": 0, "f16x3": 1, 0: 0, 1: 1}[mode]

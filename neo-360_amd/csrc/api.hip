@@ -324,6 +324,14 @@ int neo_ctx_set_ray_grid(neo_ctx* ctx, int width, long first_ray) {
     return NEO_OK;
 }
 
+int neo_ctx_set_tp_quad(neo_ctx* ctx, int mode) {
+    ENTER(ctx);
+    REQUIRE(mode == -1 || mode == 0 || mode == 1 || mode == 4 || mode == 8 || mode == 16,
+            "mode must be -1 (per-launch default), 0 (ray-major everywhere), 1 (quads of four rays everywhere) or 4 / 8 / 16 (rays per group, everywhere)");
+    ctx->tp_quad = mode == 1 ? 4 : mode;
+    return NEO_OK;
+}
+
 int neo_ctx_stream_waits(neo_ctx* ctx, uint64_t* cross_stream_waits) {
     ENTER(ctx);
     REQUIRE(cross_stream_waits != nullptr, "null out pointer");

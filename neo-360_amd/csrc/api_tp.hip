@@ -81,6 +81,28 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
         scp.grid_ph = eph >= 0 ? eph : (slot_index < 2 ? 1 : 3);
         if (scp.grid_w % (1 << scp.grid_pw) != 0) scp.grid_w = 0;
     }
+    // Quad order (point_order.h:quad_point), per slot = per region and level: the samples of G consecutive launch-order rays are
+    // interleaved, so that the four rows behind one gather instruction are four neighbouring rays at one sample index instead of
+    // four samples of one ray, and a tile holds 64 / G samples of G rays.  Under the patch order above a group of four (a quad) is a
+    // 2 x 2 pixel patch inside the sphere and four adjacent pixels of a patch row outside, a group of 16 four such patches in a
+    // row / two patch rows; without the hint, consecutive rays of the caller.  The defaults are what profiles/quad_order.log
+    // measured per launch of the 640 x 480 frame against the ray-major order (its section 3d, G = 4 / 8 / 16: inside coarse
+    // -4.6 / -4.9 / -5.4 %, inside fine -2.6 / -3.3 / -4.4 %, outside coarse -3.1 / -4.3 / -5.5 %, outside fine -0.8 / -1.3 / -1.9 %;
+    // section 3e, the shipped table: -6.5 / -4.8 / -6.8 / -2.1 %, every slowest launch below the parent's fastest).  The table
+    // below is the one place the defaults are stated (DESIGN.md 4.1 repeats it; tests/test_point_order_cpu.py compares the two).
+    // neo_ctx_set_tp_quad, then $NEO_TP_QUAD (read once: 0 = ray-major, 1 = quads of four, 4 / 8 / 16 = rays per group), replace
+    // them for every slot; a compact launch never takes the order.
+    {
+        static const int quad_default[4] = {16, 16, 16, 16};      // fg_coarse, fg_fine, bg_coarse, bg_fine
+        static int equad = -2;
+        if (equad == -2) {
+            const char* e = getenv("NEO_TP_QUAD");
+            const int v = e ? atoi(e) : -1;
+            equad = v == 1 ? 4 : (v == 0 || v == 4 || v == 8 || v == 16) ? v : -1;
+        }
+        const int forced = ctx->tp_quad >= 0 ? ctx->tp_quad : equad;
+        scp.quad = cull_map ? 0 : forced >= 0 ? forced : quad_default[slot_index];
+    }
     long plane_base[3] = {0, 0, 0};          // first texel of each projected tri-plane inside sl.proj
     if (ctx->precision == 1) {
         // range guard of the split arithmetic: tri-planes are summed over three maps before they are split

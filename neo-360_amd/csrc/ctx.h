@@ -187,6 +187,7 @@ struct neo_ctx {
     neo_host::DevBuf* tp_dirsum = &tp_dirsum_sets[0];   // (rays, 32): view-summed direction encodings of the current launch (k_tp_mlp_hp)
     int ray_grid_w = 0;                // neo_ctx_set_ray_grid: the next renders' rays are row-major pixels of an image this wide ...
     long ray_grid_first = 0;           // ... ray 0 of a render = pixel ray_grid_first of the frame (0 = no hint: caller's ray order)
+    int tp_quad = -1;                  // neo_ctx_set_tp_quad: quad order of the pre-projected split evaluators (-1: the per-launch default of tp_launch, 0: off everywhere, 4 / 8 / 16: rays per group everywhere)
     int preproject = 3;                // 0 off; 1 gather the latent pre-projected through the first-layer weights; 2 the tri-planes too; 3 (default): planes for the outside-sphere slots only
     // PixelNeRF scene latent: its own buffer / descriptor / ready flag (a context may hold both decoders)
     neo_host::DevBuf pix_latent;

@@ -124,6 +124,11 @@ struct TpScene {                     // channels-last feature maps owned by the 
     int grid_w = 0;
     long grid_first = 0;
     int grid_pw = 3, grid_ph = 3;   // log2 of the patch width / height in pixels (bands are 2^grid_ph image rows)
+    // Quad order (point_order.h:quad_point; policy in api_tp.hip:tp_launch): the pre-projected split evaluators interleave the
+    // samples of `quad` consecutive launch-order rays (4 = a quad, 8, 16: a multiple of 4), so that the four rows of one gather
+    // instruction are four neighbouring rays at one sample index.  0 (default): ray-major.  Compact launches never use it.
+    // Results do not depend on it.
+    int quad = 0;
     // Compact launch (neo_tp_render_culled, cull.hip; neo_tp_render_objects, objects.hip): row g' of the launch stands for sample g' % N of ray cull_map[g' / N];
     // tvals and the output are indexed by g', the rays' own arrays and the quirk-Q1 direction index by the ray and the
     // launch's R.  The launch holds *cull_count rays (device word, never read on the host): the grid is sized for R and the

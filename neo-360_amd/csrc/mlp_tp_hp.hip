@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
 #if NEO_TP_TRACE
     unsigned long long tr_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #endif
-    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr);
+    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr, CULL ? 0 : sc.quad);
     float* dens_w = smem + tp::OFF_DENSW;
     if (tid < 128) dens_w[tid] = m.heads[HD_DW + tid];
     // biases and head weights are read from LDS: an accumulator initialisation is on the critical path of every layer
@@ -602,7 +602,7 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
         }
         range_commit(L, m.flags);
         const long gv = tile0 + pt;
-        const long gi = tp::patch_point(gv, N, R, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
+        const long gi = tp::launch_point(gv, N, R, CULL ? 0 : sc.quad, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
         if (part == 0 && gv < P) {
             if constexpr (DENS)
                 out[gi] = make_float4(0.0f, 0.0f, 0.0f, density_act(raw_sigma));

@@ -5,6 +5,7 @@
 #pragma once
 #include "kernels.h"
 #include "mfma_tile.h"
+#include "point_order.h"
 
 namespace neo {
 namespace tp {
@@ -142,22 +143,7 @@ __device__ __forceinline__ float pe_feature(const float* x, int f) {
 }
 
 
-// Virtual point index (tile order) -> the point it stands for: identity unless the launch carries a pixel-grid hint
-// (TpScene::grid_w), then the rays of every WHOLE band of 2^ph image rows inside the launch are visited patch by patch
-// (2^pw x 2^ph pixels, row-major inside a patch, patches left to right).  A bijection on the launch's points; rays outside whole
-// bands (a shard's ragged ends) keep their place.
-__device__ __forceinline__ long patch_point(long gv, int N, int R, int grid_w, long grid_first, int pw = 3, int ph = 3) {
-    if (grid_w <= 0) return gv;
-    const long rayv = gv / N;
-    const int s = (int)(gv - rayv * N);
-    const long band = (long)grid_w << ph;
-    const long G = grid_first + rayv;
-    const long b = G / band;
-    if (b * band < grid_first || (b + 1) * band > grid_first + R) return gv;
-    const int k = (int)(G - b * band), r = k & ((1 << (pw + ph)) - 1);
-    const long Gt = b * band + (long)(r >> pw) * grid_w + ((long)(k >> (pw + ph)) << pw) + (r & ((1 << pw) - 1));
-    return (Gt - grid_first) * N + s;
-}
+// (the point order of a launch - tp::patch_point, tp::quad_point, tp::launch_point - lives in point_order.h)
 
 // ---- per-point world-space quantities (once per tile; threads 0..63) ---------------------------
 // row `tid` of the tile (any thread may compute any row)
@@ -167,14 +153,14 @@ __device__ __forceinline__ void point_setup_row(const Scratch& S, int tid, long 
                                                 const float* __restrict__ viewdirs, const float* __restrict__ tvals,
                                                 const float* __restrict__ far_arr, uint32_t* __restrict__ flags,
                                                 bool t_shared = false, int grid_w = 0, long grid_first = 0, int pw = 3, int ph = 3,
-                                                const int* __restrict__ cull_map = nullptr) {
+                                                const int* __restrict__ cull_map = nullptr, int quad = 0) {
     float* pe_world = S.pe_world;
     float* feat_world = S.feat_world;
     float* vdir_world = S.vdir_world;
     {
         long g = tile0 + tid;
         if (g >= P) g = P - 1;
-        g = patch_point(g, N, R, grid_w, grid_first, pw, ph);
+        g = launch_point(g, N, R, quad, grid_w, grid_first, pw, ph);   // quad order (TpScene::quad), then the ray-patch order
         const int row = (int)(g / N);                            // ray of the launch: the row of tvals and of the output
         const int s = (int)(g - (long)row * N);
         const int ray = cull_map ? cull_map[row] : row;          // compact launch: the caller's ray behind that row
@@ -243,9 +229,9 @@ __device__ __forceinline__ void point_setup(const Scratch& S, int tid, long tile
                                             const float* __restrict__ viewdirs, const float* __restrict__ tvals,
                                             const float* __restrict__ far_arr, uint32_t* __restrict__ flags,
                                             bool t_shared = false, int grid_w = 0, long grid_first = 0, int pw = 3, int ph = 3,
-                                            const int* __restrict__ cull_map = nullptr) {
+                                            const int* __restrict__ cull_map = nullptr, int quad = 0) {
     if (tid < TM)
-        point_setup_row<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, t_shared, grid_w, grid_first, pw, ph, cull_map);
+        point_setup_row<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, t_shared, grid_w, grid_first, pw, ph, cull_map, quad);
 }
 
 // ---- per-view descriptors (all 4 waves; lane = row) ---------------------------------------------------

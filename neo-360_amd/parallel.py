@@ -119,7 +119,7 @@ def alter_gather_cat(outputs, key, image_sizes, group=None):
 
 
 def ray_patch_order(n_rays, width, first_ray=0, pw_log2=1, ph_log2=1):
-    """Host mirror of csrc/tp_common.h:patch_point at ray granularity (documentation + CPU test; the device function is what runs):
+    """Host mirror of csrc/point_order.h:patch_point at ray granularity (documentation + CPU test; the device function is what runs):
     the order in which the NeO-360 evaluators visit the rays of a launch that carries the pixel-grid hint (neo_ctx_set_ray_grid).
     Returns a LongTensor `order` with order[k] = the ray (0 .. n_rays-1) visited k-th: inside every WHOLE band of 2^ph image rows
     that lies inside [first_ray, first_ray + n_rays) the rays go patch by patch (2^pw x 2^ph pixels, row-major inside a patch,
