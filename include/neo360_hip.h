@@ -50,7 +50,9 @@ int neo_ctx_destroy(neo_ctx* ctx);
  * sphere — the reference's AssertionError at models/neo360/helper.py:271,:426.  bit1 (NEO_FLAG_SPLIT_RANGE): an
  * operand of a split-fp16 kernel left the fp16 range (results of that call invalid; select precision 0).  bit2
  * (NEO_FLAG_SPLIT_STATIC, always together with bit1): the offending operand is a static one - packed weights or an
- * uploaded feature map - so every call on this (weights, scene) pair trips again.
+ * uploaded feature map - so every call on this (weights, scene) pair trips again.  The range has a low end for the
+ * weights of the vanilla and Mip-NeRF 360 MLPs: a linear layer whose largest |w| is non-zero and below 2^-13 raises
+ * bits 1 and 2 on the first split-fp16 launch after its upload (the hi/lo planes keep too few bits of such weights).
  * Synchronises `stream`.  [flags: host out] */
 #define NEO_FLAG_SPHERE_MISS 1u
 #define NEO_FLAG_SPLIT_RANGE 2u

@@ -540,6 +540,11 @@ int neo_vanilla_upload_mlp(neo_ctx* ctx, int slot, const float* const* weights, 
         return NEO_ERR_NOMEM;
     neo::launch_vanilla_pack_h(weights, biases, sl.wpack_h.p, sl.fold_ws.as<float>(), sl.bias.as<float>(), sl.bias_hp.as<float>(),
                                static_cast<hipStream_t>(stream));
+    {   // element counts in upload order: pts_linears.0..7 (the skip concatenation feeds 5), views_linear.0, bottleneck, density, rgb
+        const size_t counts[12] = {256 * 63, 256 * 256, 256 * 256, 256 * 256, 256 * 256, 256 * (256 + 63), 256 * 256, 256 * 256,
+                                   128 * (256 + 27), 256 * 256, 256, 3 * 128};
+        if (int rc = record_weight_maxima(sl, weights, counts, 12, static_cast<hipStream_t>(stream))) return rc;
+    }
     sl.weights_epoch += 1;
     sl.ready = true;
     return check_launch();

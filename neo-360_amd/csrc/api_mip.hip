@@ -76,6 +76,14 @@ int neo_mip_upload_mlp(neo_ctx* ctx, int slot, int width, int depth, int rgb, co
                          sl.heads.as<float>(), s);
     if (rgb && (sl.fold_ws.reserve(neo::mip_fold_floats() * sizeof(float)) || sl.bias_hp.reserve(128 * sizeof(float)))) return NEO_ERR_NOMEM;
     neo::launch_mip_pack_h(width, depth, rgb, weights, biases, sl.wpack_h.p, sl.fold_ws.as<float>(), sl.bias_hp.as<float>(), s);
+    {   // element counts in upload order: trunk (the skip concatenation feeds layer 5), density, bottleneck, view layer, rgb
+        size_t counts[12];
+        const size_t w = static_cast<size_t>(width);
+        for (int i = 0; i < depth; ++i) counts[i] = w * (i == 0 ? 504 : i == 5 ? w + 504 : w);
+        counts[depth] = w;
+        if (rgb) { counts[depth + 1] = 256 * w; counts[depth + 2] = 128 * (256 + 27); counts[depth + 3] = 3 * 128; }
+        if (int rc = record_weight_maxima(sl, weights, counts, nl, s)) return rc;
+    }
     ctx->mip_shape[slot][0] = width;
     ctx->mip_shape[slot][1] = depth;
     ctx->mip_shape[slot][2] = rgb;

@@ -59,6 +59,8 @@ struct MlpSlot {
     DevBuf wpack, bias, heads;
     DevBuf wpack_h;      // fp16 hi/lo split fragments (precision mode 1)
     DevBuf wpack_hp;     // NeRF_TP: split fragments of the pre-projected evaluator (no local-latent k-steps)
+    DevBuf wmax;         // max |w| of every linear layer of the last upload, from the fp32 source (bits of a float per layer)
+    int wmax_layers = 0; // 0: the slot's upload does not record them (no low-end check)
     DevBuf bias_hp, fold_ws;   // NeRF_TP pre-projected evaluators: their bias block (view layer 0 with the bottleneck folded in) + pack scratch
     DevBuf proj;         // NeRF_TP: ONE buffer [latent through this slot's [W0_loc | W3_loc] | the three tri-planes through
                          // [W0_world | W3_world] (preproject modes 2, 3) | padding], 256 fp32 channels = 1 KB per texel
@@ -70,7 +72,8 @@ struct MlpSlot {
     bool ready = false;
     void release() {
         wpack.release(); bias.release(); heads.release(); wpack_h.release(); wpack_hp.release(); proj.release();
-        bias_hp.release(); fold_ws.release();
+        bias_hp.release(); fold_ws.release(); wmax.release();
+        wmax_layers = 0;
         proj_weights = proj_scene = projpl_weights = projpl_scene = 0;
         ready = false;
     }
@@ -96,10 +99,25 @@ struct DeviceGuard {
 
 // Split-fp16 range guard, weight side: the first split launch after an upload scans the packed hi/lo fragments for
 // fp16 inf / NaN (|w| >= 65520 or a non-finite weight) and raises FLAG_SPLIT_RANGE in the context's flag word.
+// Slots whose upload recorded the layers' largest |w| (record_weight_maxima: vanilla and Mip-NeRF 360) are held to the low end
+// of the range as well (kernels.h SPLIT_WEIGHT_LOW), on the same launch and once per upload.
 inline void guard_split_weights(MlpSlot& sl, const void* halves, size_t bytes, uint32_t* flags, hipStream_t s) {
     if (sl.range_checked == sl.weights_epoch) return;
     neo::launch_half_range_check(halves, bytes / 2, flags, s);
+    if (sl.wmax_layers) neo::launch_weight_low_end_check(sl.wmax.as<uint32_t>(), sl.wmax_layers, neo::SPLIT_WEIGHT_LOW, flags, s);
     sl.range_checked = sl.weights_epoch;
+}
+
+// Upload side of the low-end check: max |w| of each of the nl linear layers (counts[i] floats at weights[i], the caller's fp32
+// source) into the slot, read by guard_split_weights before the first split launch on these weights.
+inline int record_weight_maxima(MlpSlot& sl, const float* const* weights, const size_t* counts, int nl, hipStream_t s) {
+    sl.wmax_layers = 0;
+    if (sl.wmax.reserve(static_cast<size_t>(nl) * sizeof(uint32_t))) return NEO_ERR_NOMEM;
+    if (hipMemsetAsync(sl.wmax.p, 0, static_cast<size_t>(nl) * sizeof(uint32_t), s) != hipSuccess)
+        return fail(NEO_ERR_HIP, "hipMemsetAsync failed");
+    for (int i = 0; i < nl; ++i) neo::launch_abs_max(weights[i], counts[i], sl.wmax.as<uint32_t>() + i, s);
+    sl.wmax_layers = nl;
+    return 0;
 }
 
 inline int check_launch() {

@@ -234,6 +234,16 @@ struct TpMlpHDev {
 // >= 65520 in magnitude, or non-finite), any fp32 value with |x| >= limit or non-finite -> flags |= 2.
 void launch_half_range_check(const void* halves, size_t n, uint32_t* flags, hipStream_t s);
 void launch_f32_range_check(const float* x, size_t n, float limit, uint32_t* flags, hipStream_t s);
+// The low end of the guard.  hi = fp16(w) keeps 11 bits and lo = fp16(w - hi) the next 11 only while lo is an fp16 normal; below
+// |w| ~ 2^-3 the lo plane runs into the subnormals and below 2^-13 it holds nothing, so the error of a product stays at about
+// 2^-25 per operand however small the operand: a layer whose weights are ALL small loses relative accuracy in proportion.
+// Rule: a linear layer with 0 < max |w| < SPLIT_WEIGHT_LOW trips the guard as a static operand (an all-zero layer splits
+// exactly).  2^-13 is taken from the measured error-against-scale curve of the dense evaluators (docs/dense_mlp_sweep.md).
+// launch_abs_max folds max |x| over n floats into *out (bits of a non-negative float, zeroed by the caller);
+// launch_weight_low_end_check reads nl such maxima and raises flag bits 1 and 2 when one of them is inside (0, low).
+constexpr float SPLIT_WEIGHT_LOW = 0x1p-13f;
+void launch_abs_max(const float* x, size_t n, uint32_t* out, hipStream_t s);
+void launch_weight_low_end_check(const uint32_t* wmax, int nl, float low, uint32_t* flags, hipStream_t s);
 size_t tp_wpack_h_bytes(int input_ch);
 void launch_tp_pack_h(int input_ch, const float* const* w, void* wpack_h, hipStream_t s);
 void launch_tp_mlp_h(int input_ch, const TpMlpHDev& m, const TpScene& sc, const TpViews& views, const float* rays_o,

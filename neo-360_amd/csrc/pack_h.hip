@@ -66,6 +66,27 @@ __global__ void k_f32_range_check(const float* __restrict__ x, size_t n4, size_t
     if (bad) atomicOr(flags, bits);
 }
 
+// max |x| over n floats, as the bits of a non-negative float (their unsigned order is the order of the values; a NaN sorts above
+// every number and is left to the high end of the guard)
+__global__ void k_abs_max(const float* __restrict__ x, size_t n, uint32_t* __restrict__ out) {
+    uint32_t m = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t b = __float_as_uint(fabsf(x[i]));
+        m = b > m ? b : m;
+    }
+    if (m) atomicMax(out, m);
+}
+
+__global__ void k_weight_low_end_check(const uint32_t* __restrict__ wmax, int nl, float low, uint32_t* __restrict__ flags) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    bool bad = false;
+    for (int i = 0; i < nl; ++i) {
+        const float m = __uint_as_float(wmax[i]);
+        bad |= m > 0.0f && m < low;
+    }
+    if (bad) atomicOr(flags, FLAG_SPLIT_RANGE | FLAG_SPLIT_STATIC);
+}
+
 // Bottleneck folded into the layer that consumes it (tp_hp_layout.h NEO_TP_FOLDB; the same algebra for the vanilla NeRFMLP,
 // vanilla_nerf/model.py:113-121: bottleneck_layer has no activation and feeds views_linear.0 only):
 //   wfold (n_out, nin + extra) = [W_v[:, :nb] . W_b (nb, nin) | W_v[:, nb:nb + extra]],   bfold (n_out) = b_v + W_v[:, :nb] . b_b
@@ -106,6 +127,17 @@ void launch_half_range_check(const void* halves, size_t n, uint32_t* flags, hipS
     const size_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(k_half_range_check, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, s,
                        reinterpret_cast<const uint16_t*>(halves), n, flags);
+}
+
+void launch_abs_max(const float* x, size_t n, uint32_t* out, hipStream_t s) {
+    if (n == 0) return;
+    const size_t blocks = (n + 1023) / 1024;
+    hipLaunchKernelGGL(k_abs_max, dim3((unsigned)(blocks > 256 ? 256 : blocks)), dim3(256), 0, s, x, n, out);
+}
+
+void launch_weight_low_end_check(const uint32_t* wmax, int nl, float low, uint32_t* flags, hipStream_t s) {
+    if (nl <= 0) return;
+    hipLaunchKernelGGL(k_weight_low_end_check, dim3(1), dim3(64), 0, s, wmax, nl, low, flags);
 }
 
 static void f32_range_check(const float* x, size_t n, float limit, uint32_t* flags, hipStream_t s, bool static_operand) {

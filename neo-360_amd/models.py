@@ -101,7 +101,7 @@ class _HipModule(nn.Module):
     precision = None
     default_precision = "f16x3"
     # The device assertion word (bit 0: the unit-sphere assertion of NeRF_TP, bit 1: the range guard of the split-fp16
-    # arithmetic) is read WITHOUT synchronising by default (no sync inside the call):
+    # arithmetic, bit 2 beside it: the operand was a static one - a packed weight beyond either end of the range, a feature map) is read WITHOUT synchronising by default (no sync inside the call):
     #   "deferred"  (default) every call enqueues a read-and-clear of the word behind its kernels; reads that have
     #               completed are looked at when the NEXT call on this module starts, and all of them in
     #               `check_flags()` (which waits) - render.render_rays_test calls it before returning a frame, and a
@@ -215,10 +215,11 @@ class _HipModule(nn.Module):
             raise _lib.NeoError("internal error reported by a kernel (flag bit 3: a bounded in-kernel wait ran out); results of that "
                                 "call are invalid" + where)
         if flags & 2:
-            err = _lib.NeoRangeError(
-                "split-fp16 arithmetic (precision 'f16x3') met an operand outside the fp16 range (|x| >= 65504 or "
-                "non-finite %s): results of that call are invalid; use precision 'f32'"
-                % ("weights / feature maps" if flags & 4 else "activations / gathered features") + where)
+            what = ("weights / feature maps outside the range the split arithmetic keeps fp32 accuracy in (beyond the fp16 range: "
+                    "|x| >= 65504 or non-finite; or, for a vanilla / Mip-NeRF 360 MLP, a linear layer whose largest |w| is below 2^-13)"
+                    if flags & 4 else "an operand outside the fp16 range (|x| >= 65504 or non-finite activations / gathered features)")
+            err = _lib.NeoRangeError("split-fp16 arithmetic (precision 'f16x3') met %s: results of that call are invalid; use "
+                                     "precision 'f32'" % what + where)
             err.static_operand = bool(flags & 4)
             raise err
 

@@ -64,7 +64,7 @@ def conical_frustum_gaussians(tdist, origins, directions, radii):
     mean = d[..., None, :] * t_mean[..., None]
     d_mag_sq = torch.sum(d ** 2, dim=-1, keepdim=True).clip(min=1e-10)
     d_outer = d[..., :, None] * d[..., None, :]
-    null_outer = torch.eye(3) - d[..., :, None] * (d / d_mag_sq)[..., None, :]
+    null_outer = torch.eye(3).type_as(d) - d[..., :, None] * (d / d_mag_sq)[..., None, :]
     cov = t_var[..., None, None] * d_outer[..., None, :, :] + r_var[..., None, None] * null_outer[..., None, :, :]
     return mean + origins[..., None, :], cov
 
@@ -79,8 +79,9 @@ def contract(mean, cov):
     z = torch.where(inside, mean, a * mean)
     outer = mean[..., :, None] * mean[..., None, :]
     coef = 2 / (m * torch.sqrt(m)) - 2 * a / m
-    J = a[..., None] * torch.eye(3) + coef[..., None] * outer
-    J = torch.where(inside[..., None], torch.eye(3).expand_as(J), J)
+    eye = torch.eye(3).type_as(mean)
+    J = a[..., None] * eye + coef[..., None] * outer
+    J = torch.where(inside[..., None], eye.expand_as(J), J)
     return z, J @ cov @ J.transpose(-1, -2)
 
 

@@ -54,7 +54,7 @@ def test_mlp_stages_vs_oracle(layered):
     (layered: 1600 intervals = one padded batch of 2048)."""
     net = _net(layered=layered)
     params = synth.mip360_state(0, weight_gain=0.5)
-    rays = cases.mip_rays(50)          # ragged: 50*64 = 3200 = 100 tiles; 50*32 = 1600 = 50 tiles
+    rays = cases.mip_rays(50)          # whole tiles: 50*64 = 3200 = 100 tiles; 50*32 = 1600 = 50 tiles
     basis = mip360.icosahedron_basis()
     for slot, n, depth, rgb in ((0, 64, 4, False), (2, 32, 8, True)):
         s = torch.sort(synth.uniform(71, "mip_s%d" % slot, (50, n + 1), 0.0, 1.0), dim=-1).values
@@ -96,8 +96,9 @@ def test_end_to_end_vs_golden(golden, tag, tf, gain, counts, layered):
 @pytest.mark.parametrize("rays,n", [(77, 32), (600, 32), (130, 128)])
 def test_layered_schedule_equals_fused_evaluator(rays, n):
     """The layer-by-layer NeRF MLP (encodings -> 8 GEMM launches -> heads) runs the SAME products in the same k order as
-    the fused evaluator: bitwise equal outputs.  77 x 32 = 2464 intervals (a padded batch, ragged last tile), 600 x 32 =
-    19200 (two batches, the second short), 130 x 128 = 16640 (one full batch + 256 intervals)."""
+    the fused evaluator: bitwise equal outputs.  77 x 32 = 2464 intervals (77 whole tiles in one padded batch of 4096), 600 x 32 =
+    19200 (two batches, the second short), 130 x 128 = 16640 (one full batch + 256 intervals).  Every count here is a multiple of
+    the 32-interval tile; partial last tiles are in test_gpu_dense_mlp_sweep.py::test_mip_layered_equals_fused."""
     batch = _to(cases.mip_rays(rays))
     s = torch.sort(synth.uniform(79, "mip_eq_%d_%d" % (rays, n), (rays, n + 1), 0.0, 1.0), dim=-1).values
     tdist = (1 / (s * (1 / 3.0) + (1 - s) * (1 / 0.2))).to(DEV)
