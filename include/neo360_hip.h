@@ -50,9 +50,15 @@ int neo_ctx_destroy(neo_ctx* ctx);
  * sphere — the reference's AssertionError at models/neo360/helper.py:271,:426.  bit1 (NEO_FLAG_SPLIT_RANGE): an
  * operand of a split-fp16 kernel left the fp16 range (results of that call invalid; select precision 0).  bit2
  * (NEO_FLAG_SPLIT_STATIC, always together with bit1): the offending operand is a static one - packed weights or an
- * uploaded feature map - so every call on this (weights, scene) pair trips again.  The range has a low end for the
- * weights of the vanilla and Mip-NeRF 360 MLPs: a linear layer whose largest |w| is non-zero and below 2^-13 raises
- * bits 1 and 2 on the first split-fp16 launch after its upload (the hi/lo planes keep too few bits of such weights).
+ * uploaded feature map - so every call on this (weights, scene) pair trips again: a read that returns bit1 re-arms the
+ * one-time checks of static operands, here and in neo_ctx_take_flags.  The range has a low end: a linear layer whose
+ * largest |w| is non-zero and below 2^-13 (vanilla, Mip-NeRF 360), 2^-11 (neo_tp_upload_mlp), 2^-9 (neo_pix_upload_mlp)
+ * or 2^-6 (neo_enc_upload) raises bits 1 and 2 on the first split-fp16 launch after its upload (the hi/lo planes keep
+ * too few bits of such weights; a layer folded into another one in fp64 at pack time is exempt), and so does an uploaded
+ * feature map that a split kernel reads without the fp32 pre-projection when its largest |x| is non-zero and below 2^-8
+ * (neo_tp_set_scene: the summed tri-planes in modes 0, 1 and in slots 0, 1 of mode 3, the latent in mode 0;
+ * neo_pix_set_scene: the latent with pre-projection off).  The latent of neo_enc_floorplans is a per-call operand: below
+ * 2^-6 it raises bit 1 alone.
  * Synchronises `stream`.  [flags: host out] */
 #define NEO_FLAG_SPHERE_MISS 1u
 #define NEO_FLAG_SPLIT_RANGE 2u
@@ -360,8 +366,8 @@ int neo_enc_upload(neo_ctx* ctx, const float* const* weights, const float* const
  * SpatialEncoder's output; src_poses [host] NV*16; focal / cx / cy = view 0's intrinsics (:491-493).  Outputs
  * channels-last: fp_yz (NV,G1,G2,512), fp_xz (NV,G0,G2,512), fp_xy (NV,G0,G1,512) (the reference permutes them to NCHW
  * for its conv nets, :580-592).  Runs in the context's arithmetic (neo_ctx_set_precision): mode 1 = fp16 MFMA on hi/lo-split
- * operands behind the range guard (a latent texel or a weight at or beyond 65504 raises flag bit 1; bit 2 as well when it
- * is a weight); mode 0 = exact fp32 MFMA, no range check, no flag bit - what a caller whose guard tripped runs again. */
+ * operands behind the range guard (a latent texel or a weight at or beyond 65504, a latent whose largest |x| or a layer
+ * whose largest |w| is non-zero and below 2^-6 raises flag bit 1; bit 2 as well when it is a weight); mode 0 = exact fp32 MFMA, no range check, no flag bit - what a caller whose guard tripped runs again. */
 int neo_enc_floorplans(neo_ctx* ctx, const float* latent, int NV, int Hf, int Wf, float image_w, float image_h,
                        const float* src_poses, float focal, float cx, float cy, int G0, int G1, int G2,
                        float* fp_yz, float* fp_xz, float* fp_xy, void* stream);

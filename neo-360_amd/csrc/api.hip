@@ -198,6 +198,7 @@ int neo_ctx_destroy(neo_ctx* ctx) {
     ctx->enc_axes.release();
     for (auto& b : ctx->enc_ws) b.release();
     ctx->latent.release();
+    ctx->map_max.release();
     for (auto& b : ctx->tp_dirsum_sets) b.release();
     ctx->train_scratch.release();
     for (auto& b : ctx->plane) b.release();
@@ -239,6 +240,7 @@ int neo_ctx_poll_flags(neo_ctx* ctx, uint32_t* flags, void* stream) {
     HIP_TRY(take_flags_async(ctx, neo_ctx::FLAG_RING, flags, s));
     HIP_TRY(hipStreamSynchronize(s));
     ctx->blocking_waits += 1;
+    if (*flags & NEO_FLAG_SPLIT_RANGE) ctx->rearm_split_checks();      // the word is clear now: a static operand must trip again
     return NEO_OK;
 }
 
@@ -295,6 +297,7 @@ int neo_ctx_take_flags(neo_ctx* ctx, int wait, void* stream, uint32_t* flags, in
         acc |= now;
     }
     *flags = acc;
+    if (acc & NEO_FLAG_SPLIT_RANGE) ctx->rearm_split_checks();         // as neo_ctx_poll_flags
     if (pending) *pending = static_cast<int>(ctx->flag_posted - ctx->flag_taken);
     return NEO_OK;
 }
@@ -346,13 +349,7 @@ int neo_ctx_set_precision(neo_ctx* ctx, int mode) {
         // entering the split arithmetic: the one-time range checks of packed weights and feature maps run again at the
         // next split launch (a frame that tripped the guard and was re-rendered exactly must trip it again, not pass
         // because "already checked")
-        for (auto& sl : ctx->vanilla) sl.range_checked = 0;
-        for (auto& sl : ctx->tp) sl.range_checked = 0;
-        for (auto& sl : ctx->mip) sl.range_checked = 0;
-        for (auto& sl : ctx->pix) sl.range_checked = 0;
-        ctx->enc.range_checked = 0;
-        ctx->planes_checked = ctx->latent_checked = 0;
-        ctx->pix_latent_checked = false;
+        ctx->rearm_split_checks();
     }
     ctx->precision = mode;
     return NEO_OK;

@@ -60,8 +60,13 @@ int enc_forward(neo_ctx* ctx, const neo::PillarGeom& gm, float* h1, float* h2, f
     MlpSlot& sl = ctx->enc;
     int rc;
     if (ctx->precision == 1) {
-        guard_split_weights(sl, sl.wpack_h.p, neo::pillar_wpack_bytes(), ctx->flags, s);
+        guard_split_weights(sl, sl.wpack_h.p, neo::pillar_wpack_bytes(), ctx->flags, s, neo::SPLIT_WEIGHT_LOW_ENC);
         neo::launch_f32_input_range_check(ctx->enc_latent.as<float>(), static_cast<size_t>(gm.nv) * 512 * gm.Hf * gm.Wf, 65504.0f, ctx->flags, s);
+        {   // low end of the same per-call operand: a latent that is small everywhere (kernels.h SPLIT_LATENT_LOW_ENC)
+            const float* lat = ctx->enc_latent.as<float>();
+            if (int rc = guard_map_low(ctx, MAP_MAX_ENC_LATENT, &lat, 1, static_cast<size_t>(gm.nv) * 512 * gm.Hf * gm.Wf,
+                                       neo::SPLIT_LATENT_LOW_ENC, false, s)) return rc;
+        }
         ctx->span_begin(s);
         rc = neo::launch_pillar(gm, ctx->enc_latent.as<float>(), sl.wpack_h.p, sl.bias.as<float>(), sl.heads.as<float>(),
                                 ctx->enc_head_b, h1, h2, Lf, score, ctx->flags, fp_yz, fp_xz, fp_xy, s);
@@ -102,6 +107,10 @@ int neo_enc_upload(neo_ctx* ctx, const float* const* weights, const float* const
         HIP_TRY(hipMemcpyAsync(&ctx->enc_head_b[a], biases[4 + 2 * a], sizeof(float), hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));        // the three scalar head biases are kernel arguments
+    {   // element counts in upload order: common_branch.0, .2, depth_encoder, then per axis the aggregator's layer and its scorer head
+        const size_t counts[9] = {512 * 518, 512 * 512, 512 * 512, 512 * 513, 512, 512 * 513, 512, 512 * 513, 512};
+        if (int rc = record_weight_maxima(sl, weights, counts, 9, s)) return rc;
+    }
     sl.weights_epoch += 1;
     sl.ready = true;
     return check_launch();

@@ -24,10 +24,17 @@ int pix_launch(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpView
         ctx->span_end(s, static_cast<double>(R) * N, pix_flop_per_point(sc.nv));
         return NEO_OK;
     }
-    guard_split_weights(sl, sl.wpack_h.p, neo::pix_wpack_h_bytes(), ctx->flags, s);
+    // low end: the bottleneck (upload index 6) is folded into view layer 0 in fp64 at pack time (launch_pix_pack_h)
+    guard_split_weights(sl, sl.wpack_h.p, neo::pix_wpack_h_bytes(), ctx->flags, s, neo::SPLIT_WEIGHT_LOW_PIX, 1u << 6);
     if (!ctx->pix_latent_checked) {
         neo::launch_f32_range_check(sc.latent, static_cast<size_t>(sc.nv) * sc.Hf * sc.Wf * 512, 65504.0f, ctx->flags, s);
         ctx->pix_latent_checked = true;
+    }
+    if (!ctx->pix_preproject && !ctx->pix_latent_low_checked) {      // the raw latent is split only without the fp32 pre-projection
+        if (int rc = ctx->touch_shared(s)) return rc;
+        if (int rc = guard_map_low(ctx, MAP_MAX_PIX_LATENT, &sc.latent, 1, static_cast<size_t>(sc.nv) * sc.Hf * sc.Wf * 512,
+                                   neo::SPLIT_MAP_LOW, true, s)) return rc;
+        ctx->pix_latent_low_checked = true;
     }
     const float* proj = nullptr;
     if (ctx->pix_preproject) {
@@ -74,6 +81,10 @@ int neo_pix_upload_mlp(neo_ctx* ctx, int slot, const float* const* weights, cons
     // pts_linears.0 that k_tp_preproject multiplies the scene latent with (pre-projection of the split evaluator)
     neo::launch_pix_pack(weights, biases, sl.fold_ws.as<float>(), sl.bias.as<float>(), sl.bias_hp.as<float>(), sl.wpack.as<float>(),
                          static_cast<hipStream_t>(stream));
+    {   // element counts in upload order: pts_linears.0..3, views_linear.0, .1, bottleneck, density, rgb
+        const size_t counts[9] = {128 * (63 + 512), 128 * 128, 128 * 128, 128 * 128, 128 * (128 + 27), 128 * 128, 128 * 128, 128, 3 * 128};
+        if (int rc = record_weight_maxima(sl, weights, counts, 9, static_cast<hipStream_t>(stream))) return rc;
+    }
     sl.input_ch = 3;
     sl.weights_epoch += 1;
     sl.ready = true;
@@ -102,7 +113,7 @@ int neo_pix_set_scene(neo_ctx* ctx, const float* latent, int NV, int Cl, int Hf,
     ctx->pix_scene.sy = ((hf / (hf - 1.0f)) * 2.0f) / image_h;
     ctx->pix_scene.fy_sign = 1.0f;                                     // model_pixel.py:203 passes (f, f)
     ctx->pix_scene_ready = true;
-    ctx->pix_latent_checked = false;
+    ctx->pix_latent_checked = ctx->pix_latent_low_checked = false;
     ctx->pix_scene_epoch += 1;
     return check_launch();
 }

@@ -51,6 +51,17 @@ int ensure_projections(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, bool p
     return NEO_OK;
 }
 
+// Low end of the range guard for the tri-planes on the paths that split them raw (summed over the three maps first, so their
+// common maximum counts): once per scene, a static operand (kernels.h SPLIT_MAP_LOW).
+int guard_planes_low(neo_ctx* ctx, const neo::TpScene& sc, hipStream_t s) {
+    if (ctx->planes_low_checked == ctx->scene_epoch) return NEO_OK;
+    if (int rc = ctx->touch_shared(s)) return rc;      // writes the context's map maxima: this call ends as an exclusive one
+    if (int rc = guard_map_low(ctx, MAP_MAX_PLANES, sc.plane, 3, static_cast<size_t>(sc.nv) * sc.Hp * sc.Wp * 128, neo::SPLIT_MAP_LOW,
+                               true, s)) return rc;
+    ctx->planes_low_checked = ctx->scene_epoch;
+    return NEO_OK;
+}
+
 // one region's evaluator launch in the context's arithmetic mode
 // density_only: the caller reads sigma alone (a level-0 launch whose colour and depth nobody asked for).  The pre-projected split
 // evaluators then run their density-only instantiation and the per-ray direction sums are not built; the exact-fp32 and the
@@ -119,7 +130,11 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
             // more than the GEMM stage they replace (+1..7 %): profiles/r04_tp_hp_experiments.log.
             const bool planes = ctx->preproject == 2 || (ctx->preproject == 3 && slot_index >= 2);
             if (int rc = ensure_projections(ctx, sl, sc, planes, s, plane_base, true)) return rc;
-            guard_split_weights(sl, sl.wpack_hp.p, neo::tp_wpack_hp_bytes(sl.input_ch), ctx->flags, s);
+            // low end: the bottleneck (upload index 6) is folded into view layer 0 in fp64 at pack time and is no operand of
+            // these fragments; the latent is projected in fp32, the tri-planes are split raw unless this slot projects them too
+            guard_split_weights(sl, sl.wpack_hp.p, neo::tp_wpack_hp_bytes(sl.input_ch), ctx->flags, s, neo::SPLIT_WEIGHT_LOW_TP, 1u << 6);
+            if (!planes)
+                if (int rc = guard_planes_low(ctx, sc, s)) return rc;
             neo::TpMlpHDev mh{sl.wpack_hp.p, sl.bias_hp.as<float>(), sl.heads.as<float>(), ctx->flags};
             // the view-direction encodings enter the MLP only through their mean over the views, and they depend on the
             // ray alone: summed once per ray here instead of once per sample and view inside the evaluator
@@ -136,10 +151,18 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
                 neo::launch_tp_mlp_hp(sl.input_ch, mh, sl.proj.as<float>(), scp, views, rays_o, rays_d, viewdirs, tvals, far, R, N,
                                       chunk, ctx->flags, out, ctx->tp_dirsum->as<float>(), s, dens);
         } else {
-            guard_split_weights(sl, sl.wpack_h.p, neo::tp_wpack_h_bytes(sl.input_ch), ctx->flags, s);
+            guard_split_weights(sl, sl.wpack_h.p, neo::tp_wpack_h_bytes(sl.input_ch), ctx->flags, s, neo::SPLIT_WEIGHT_LOW_TP);
             if (ctx->latent_checked != ctx->scene_epoch) {
                 neo::launch_f32_range_check(sc.latent, static_cast<size_t>(sc.nv) * sc.Hf * sc.Wf * 512, 65504.0f, ctx->flags, s);
                 ctx->latent_checked = ctx->scene_epoch;
+            }
+            // k_tp_mlp_h splits the raw latent and the raw summed tri-planes: both are held to the low end as well
+            if (int rc = guard_planes_low(ctx, sc, s)) return rc;
+            if (ctx->latent_low_checked != ctx->scene_epoch) {
+                if (int rc = ctx->touch_shared(s)) return rc;
+                if (int rc = guard_map_low(ctx, MAP_MAX_LATENT, &sc.latent, 1, static_cast<size_t>(sc.nv) * sc.Hf * sc.Wf * 512,
+                                           neo::SPLIT_MAP_LOW, true, s)) return rc;
+                ctx->latent_low_checked = ctx->scene_epoch;
             }
             neo::TpMlpHDev mh{sl.wpack_h.p, sl.bias.as<float>(), sl.heads.as<float>(), ctx->flags};
             ctx->span_kernel_next = 3;
@@ -220,6 +243,11 @@ int neo_tp_upload_mlp(neo_ctx* ctx, int slot, int input_ch, const float* const* 
         return NEO_ERR_NOMEM;
     neo::launch_tp_pack_hp(input_ch, weights, biases, sl.wpack_hp.p, sl.fold_ws.as<float>(), sl.bias.as<float>(),
                            sl.bias_hp.as<float>(), static_cast<hipStream_t>(stream));
+    {   // element counts in upload order: pts_linears.0..3 (the skip concatenation feeds 3), views_linear.0, .1, bottleneck, density, rgb
+        const size_t x = static_cast<size_t>(21 * input_ch + 512 + 128);
+        const size_t counts[9] = {128 * x, 128 * 128, 128 * 128, 128 * (128 + x), 64 * (128 + 27), 64 * 64, 128 * 128, 128, 3 * 64};
+        if (int rc = record_weight_maxima(sl, weights, counts, 9, static_cast<hipStream_t>(stream))) return rc;
+    }
     sl.weights_epoch += 1;
     sl.input_ch = input_ch;
     sl.ready = true;

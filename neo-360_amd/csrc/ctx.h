@@ -99,12 +99,14 @@ struct DeviceGuard {
 
 // Split-fp16 range guard, weight side: the first split launch after an upload scans the packed hi/lo fragments for
 // fp16 inf / NaN (|w| >= 65520 or a non-finite weight) and raises FLAG_SPLIT_RANGE in the context's flag word.
-// Slots whose upload recorded the layers' largest |w| (record_weight_maxima: vanilla and Mip-NeRF 360) are held to the low end
-// of the range as well (kernels.h SPLIT_WEIGHT_LOW), on the same launch and once per upload.
-inline void guard_split_weights(MlpSlot& sl, const void* halves, size_t bytes, uint32_t* flags, hipStream_t s) {
+// Slots whose upload recorded the layers' largest |w| (record_weight_maxima: every evaluator and the pillar stage) are held to
+// the low end of the range as well (kernels.h: `low` is the family's SPLIT_WEIGHT_LOW*), on the same launch and once per upload;
+// skip_mask names the layers (upload order) that the launched fragment set does not hold as such.
+inline void guard_split_weights(MlpSlot& sl, const void* halves, size_t bytes, uint32_t* flags, hipStream_t s,
+                                float low = neo::SPLIT_WEIGHT_LOW, uint32_t skip_mask = 0u) {
     if (sl.range_checked == sl.weights_epoch) return;
     neo::launch_half_range_check(halves, bytes / 2, flags, s);
-    if (sl.wmax_layers) neo::launch_weight_low_end_check(sl.wmax.as<uint32_t>(), sl.wmax_layers, neo::SPLIT_WEIGHT_LOW, flags, s);
+    if (sl.wmax_layers) neo::launch_low_end_check(sl.wmax.as<uint32_t>(), sl.wmax_layers, low, skip_mask, true, flags, s);
     sl.range_checked = sl.weights_epoch;
 }
 
@@ -195,6 +197,8 @@ struct neo_ctx {
     bool scene_ready = false;
     uint64_t scene_epoch = 0;          // bumped by every neo_tp_set_scene
     uint64_t planes_checked = 0, latent_checked = 0;   // scene_epoch whose maps passed the split range check
+    uint64_t planes_low_checked = 0, latent_low_checked = 0;   // ... and, where a split kernel reads them raw, its low end (guard_map_low)
+    neo_host::DevBuf map_max;          // largest |x| of the maps guard_map_low looked at: tri-planes, latent, PixelNeRF latent, pillar latent
     // Scratch LANES (round 6): four sets (grown on first use; the Python host keeps two calls in flight) of the render workspaces and of the per-launch direction table.  A caller that drives the
     // module chunk by chunk (the reference's render_rays_test loop, neo360/model.py:861-907) alternates lanes - and streams -
     // so that chunk i + 1's evaluators start while chunk i's last workgroups drain (models.py: NeRF_TP overlap).  `lane`
@@ -211,7 +215,7 @@ struct neo_ctx {
     neo_host::DevBuf pix_latent;
     neo::TpScene pix_scene{};
     bool pix_scene_ready = false;
-    bool pix_latent_checked = false;
+    bool pix_latent_checked = false, pix_latent_low_checked = false;
     uint64_t pix_scene_epoch = 0;
     int pix_preproject = 1;            // PixelNeRF: gather the latent pre-projected through pts_linears.0 (mlp_pix_h.hip)
     std::map<int, neo_host::DevBuf> quantiles;                    // n_new -> linspace(0, fl32(1-2^-32), n_new)
@@ -265,4 +269,33 @@ struct neo_ctx {
     const float* get_edges(int n, float near, float far, hipStream_t s);
     void span_begin(hipStream_t s);
     void span_end(hipStream_t s, double points, double flop_per_point);
+
+    // The one-time range checks of static operands (packed weights, uploaded maps) run again at the next split launch.  Called
+    // when the split arithmetic is entered (neo_ctx_set_precision) and when the host TAKES a flag word with the range bit set
+    // (neo_ctx_poll_flags, neo_ctx_take_flags): the read clears the device word, so a second call on the same weights and scene
+    // must trip the guard again instead of passing as "already checked".  Host bookkeeping only: the healthy path gains nothing.
+    void rearm_split_checks() {
+        for (auto& sl : vanilla) sl.range_checked = 0;
+        for (auto& sl : tp) sl.range_checked = 0;
+        for (auto& sl : mip) sl.range_checked = 0;
+        for (auto& sl : pix) sl.range_checked = 0;
+        enc.range_checked = 0;
+        planes_checked = latent_checked = planes_low_checked = latent_low_checked = 0;
+        pix_latent_checked = pix_latent_low_checked = false;
+    }
 };
+
+namespace neo_host {
+// Low end of the split range guard for fp32 maps a split kernel reads raw: max |x| over the nmaps maps of n floats each (summed
+// maps share one maximum) into slot `which` of ctx->map_max, then one scalar check against (0, low).
+enum { MAP_MAX_PLANES = 0, MAP_MAX_LATENT = 1, MAP_MAX_PIX_LATENT = 2, MAP_MAX_ENC_LATENT = 3, MAP_MAX_SLOTS = 4 };
+inline int guard_map_low(neo_ctx* ctx, int which, const float* const* maps, int nmaps, size_t n, float low, bool static_operand,
+                         hipStream_t s) {
+    if (ctx->map_max.reserve(MAP_MAX_SLOTS * sizeof(uint32_t))) return NEO_ERR_NOMEM;
+    uint32_t* m = ctx->map_max.as<uint32_t>() + which;
+    if (hipMemsetAsync(m, 0, sizeof(uint32_t), s) != hipSuccess) return fail(NEO_ERR_HIP, "hipMemsetAsync failed");
+    for (int j = 0; j < nmaps; ++j) neo::launch_abs_max(maps[j], n, m, s);
+    neo::launch_low_end_check(m, 1, low, 0u, static_operand, ctx->flags, s);
+    return NEO_OK;
+}
+}  // namespace neo_host

@@ -242,8 +242,25 @@ void launch_f32_range_check(const float* x, size_t n, float limit, uint32_t* fla
 // launch_abs_max folds max |x| over n floats into *out (bits of a non-negative float, zeroed by the caller);
 // launch_weight_low_end_check reads nl such maxima and raises flag bits 1 and 2 when one of them is inside (0, low).
 constexpr float SPLIT_WEIGHT_LOW = 0x1p-13f;
+// The 128-wide decoder MLPs and the 512-wide pillar stage reach half of their per-entry bounds at larger weights than the dense
+// 256 / 1024-wide evaluators; each value below is the smallest power of two that flags every state of tests/split_scale_cases.py
+// measured above half a bound AND keeps the share extrapolated to the threshold itself (error ~ 1 / operand) at or under half, for
+// every rescaling kind of the family (docs/split_scale_sweep.md has the curves; largest |w| of the last state at or under half /
+// of the first one above it in brackets):
+constexpr float SPLIT_WEIGHT_LOW_TP = 0x1p-11f;    // NeO-360 decoder slots (views_linear.0: 1.25e-3 at 0.13 / 3.1e-4 at 0.66)
+constexpr float SPLIT_WEIGHT_LOW_PIX = 0x1p-9f;    // PixelNeRF slots (pts_linears.2: 2.4e-3 at 0.22 / 6.0e-4 at 0.87)
+constexpr float SPLIT_WEIGHT_LOW_ENC = 0x1p-6f;    // pillar stage (depth_fc.common_branch.0: 1.9e-2 at 0.30 / 4.9e-3 at 0.96)
+// The same rule for an fp32 feature map that a split kernel reads RAW (not through the fp32 pre-projection): a map whose largest
+// |x| is inside (0, low) trips the guard - an uploaded scene map as a static operand, the pillar stage's latent per call.
+constexpr float SPLIT_MAP_LOW = 0x1p-8f;           // tri-planes / latent of the decoders (2.3e-3 at 0.46 / 5.9e-4 at 1.9)
+constexpr float SPLIT_LATENT_LOW_ENC = 0x1p-6f;    // pillar stage's latent (3.6e-2 at 0.15 / 9.0e-3 at 0.61)
 void launch_abs_max(const float* x, size_t n, uint32_t* out, hipStream_t s);
-void launch_weight_low_end_check(const uint32_t* wmax, int nl, float low, uint32_t* flags, hipStream_t s);
+// skip_mask: bit i set = maximum i is not looked at (a layer the launched fragment set folds into another one in fp64 at pack
+// time); static_operand: raise bit 2 beside bit 1
+void launch_low_end_check(const uint32_t* maxima, int n, float low, uint32_t skip_mask, bool static_operand, uint32_t* flags, hipStream_t s);
+inline void launch_weight_low_end_check(const uint32_t* wmax, int nl, float low, uint32_t* flags, hipStream_t s) {
+    launch_low_end_check(wmax, nl, low, 0u, true, flags, s);
+}
 size_t tp_wpack_h_bytes(int input_ch);
 void launch_tp_pack_h(int input_ch, const float* const* w, void* wpack_h, hipStream_t s);
 void launch_tp_mlp_h(int input_ch, const TpMlpHDev& m, const TpScene& sc, const TpViews& views, const float* rays_o,

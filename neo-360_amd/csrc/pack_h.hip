@@ -77,14 +77,15 @@ __global__ void k_abs_max(const float* __restrict__ x, size_t n, uint32_t* __res
     if (m) atomicMax(out, m);
 }
 
-__global__ void k_weight_low_end_check(const uint32_t* __restrict__ wmax, int nl, float low, uint32_t* __restrict__ flags) {
+__global__ void k_low_end_check(const uint32_t* __restrict__ maxima, int n, float low, uint32_t skip_mask, uint32_t bits,
+                                uint32_t* __restrict__ flags) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     bool bad = false;
-    for (int i = 0; i < nl; ++i) {
-        const float m = __uint_as_float(wmax[i]);
-        bad |= m > 0.0f && m < low;
+    for (int i = 0; i < n; ++i) {
+        const float m = __uint_as_float(maxima[i]);
+        bad |= !((skip_mask >> i) & 1u) && m > 0.0f && m < low;
     }
-    if (bad) atomicOr(flags, FLAG_SPLIT_RANGE | FLAG_SPLIT_STATIC);
+    if (bad) atomicOr(flags, bits);
 }
 
 // Bottleneck folded into the layer that consumes it (tp_hp_layout.h NEO_TP_FOLDB; the same algebra for the vanilla NeRFMLP,
@@ -135,9 +136,11 @@ void launch_abs_max(const float* x, size_t n, uint32_t* out, hipStream_t s) {
     hipLaunchKernelGGL(k_abs_max, dim3((unsigned)(blocks > 256 ? 256 : blocks)), dim3(256), 0, s, x, n, out);
 }
 
-void launch_weight_low_end_check(const uint32_t* wmax, int nl, float low, uint32_t* flags, hipStream_t s) {
-    if (nl <= 0) return;
-    hipLaunchKernelGGL(k_weight_low_end_check, dim3(1), dim3(64), 0, s, wmax, nl, low, flags);
+void launch_low_end_check(const uint32_t* maxima, int n, float low, uint32_t skip_mask, bool static_operand, uint32_t* flags,
+                          hipStream_t s) {
+    if (n <= 0 || n > 32) return;
+    hipLaunchKernelGGL(k_low_end_check, dim3(1), dim3(64), 0, s, maxima, n, low, skip_mask,
+                       static_operand ? FLAG_SPLIT_RANGE | FLAG_SPLIT_STATIC : FLAG_SPLIT_RANGE, flags);
 }
 
 static void f32_range_check(const float* x, size_t n, float limit, uint32_t* flags, hipStream_t s, bool static_operand) {

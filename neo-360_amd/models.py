@@ -216,8 +216,11 @@ class _HipModule(nn.Module):
                                 "call are invalid" + where)
         if flags & 2:
             what = ("weights / feature maps outside the range the split arithmetic keeps fp32 accuracy in (beyond the fp16 range: "
-                    "|x| >= 65504 or non-finite; or, for a vanilla / Mip-NeRF 360 MLP, a linear layer whose largest |w| is below 2^-13)"
-                    if flags & 4 else "an operand outside the fp16 range (|x| >= 65504 or non-finite activations / gathered features)")
+                    "|x| >= 65504 or non-finite; or small everywhere: a linear layer whose largest |w| is below 2^-13 (vanilla, "
+                    "Mip-NeRF 360), 2^-11 (NeO-360), 2^-9 (PixelNeRF) or 2^-6 (pillar stage), or a feature map read without "
+                    "pre-projection whose largest |x| is below 2^-8)"
+                    if flags & 4 else "an operand outside the range the split arithmetic keeps fp32 accuracy in (beyond the fp16 range: "
+                    "|x| >= 65504 or non-finite activations / gathered features; or a pillar-stage latent whose largest |x| is below 2^-6)")
             err = _lib.NeoRangeError("split-fp16 arithmetic (precision 'f16x3') met %s: results of that call are invalid; use "
                                      "precision 'f32'" % what + where)
             err.static_operand = bool(flags & 4)

@@ -175,21 +175,30 @@ def _scene_cast(sc, dtype):
     return {k: (v.to(dtype) if isinstance(v, torch.Tensor) else v) for k, v in sc.items()}
 
 
-@functools.lru_cache(maxsize=None)
-def neo_reference(s, P, dtype=torch.float64):
-    """(inside, outside) per-point outputs (R,N,4) of oracle.neo360.region_eval in `dtype`, per chunk slice."""
-    c, sc = point_case(s, P), _scene_cast(scene_of(s), dtype)
-    p = _neo_params(dtype)
+def neo_eval(s, P, params, sc, dtype):
+    """(inside, outside) per-point outputs (R,N,4) of oracle.neo360.region_eval on case (s, P) with the state dict `params` and the
+    scene `sc`, both cast to `dtype`, per chunk slice."""
+    c, sc, p = point_case(s, P), _scene_cast(sc, dtype), _cast_params(params, dtype)
     fg = _per_chunk(lambda b, tv, far: oracle.neo360.region_eval(p, FG_PREFIX, b, sc, tv, True, far), c, c["t_in"], dtype)
     bg = _per_chunk(lambda b, tv, far: oracle.neo360.region_eval(p, BG_PREFIX, b, sc, tv, False, far), c, c["s_out"], dtype)
     return fg, bg
 
 
 @functools.lru_cache(maxsize=None)
-def pix_reference(s, P, dtype=torch.float64):
-    c, sc = point_case(s, P), _scene_cast(scene_of(s), dtype)
-    p = _pix_params(dtype)
+def neo_reference(s, P, dtype=torch.float64):
+    """(inside, outside) per-point outputs (R,N,4) of oracle.neo360.region_eval in `dtype`, per chunk slice."""
+    return neo_eval(s, P, _neo_params(dtype), scene_of(s), dtype)
+
+
+def pix_eval(s, P, params, sc, dtype):
+    """Per-point outputs (R,N,4) of oracle.pixelnerf.region_eval on case (s, P) with `params` and `sc`, cast to `dtype`."""
+    c, sc, p = point_case(s, P), _scene_cast(sc, dtype), _cast_params(params, dtype)
     return _per_chunk(lambda b, tv, far: oracle.pixelnerf.region_eval(p, PIX_PREFIX, b, sc, tv), c, c["t_in"], dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def pix_reference(s, P, dtype=torch.float64):
+    return pix_eval(s, P, _pix_params(dtype), scene_of(s), dtype)
 
 
 def eval_checks(got, ref64, ref32):
@@ -253,14 +262,20 @@ def pillar_case(i):
                 params=synth.pillar_state(PILLAR_PARAM_SEED))
 
 
+def pillar_eval(i, params, latent, dtype):
+    """The three floor-plans (yz, xz, xy) of oracle.pillar.floorplans on pillar case i with `params` and `latent`, cast to `dtype`."""
+    c = pillar_case(i)
+    p = _cast_params(params, dtype)
+    out = oracle.pillar.floorplans(p, latent.to(dtype), c["image_wh"], c["poses"].to(dtype), c["focal"].to(dtype),
+                                   c["centre"].to(dtype), c["grid"])
+    return tuple(_d(x) for x in out)
+
+
 @functools.lru_cache(maxsize=None)
 def pillar_reference(i, dtype=torch.float64):
     """The three floor-plans (yz, xz, xy) of oracle.pillar.floorplans in `dtype`."""
     c = pillar_case(i)
-    p = _cast_params(c["params"], dtype)
-    out = oracle.pillar.floorplans(p, c["latent"].to(dtype), c["image_wh"], c["poses"].to(dtype), c["focal"].to(dtype),
-                                   c["centre"].to(dtype), c["grid"])
-    return tuple(_d(x) for x in out)
+    return pillar_eval(i, c["params"], c["latent"], dtype)
 
 
 def plan_checks(got, ref64, ref32):
