@@ -280,6 +280,41 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d,
                   float focal, float cx, float cy, int n_coarse, int n_fine, int white_bkgd,
                   const neo_tp_level_out* level0, const neo_tp_level_out* level1, void* stream);
 
+/* The per-ray EXTRAS of a NeO-360 ray's whole interval histogram, inside and outside the unit sphere together, as DISTANCES ALONG THE
+ * RAY: the unit of the ray parameter t of o + t d, which is the unit of the reference's fg_depth (and not that of its comp_depth =
+ * fg_depth + bg_lambda * bg_depth, neo360/model.py:523, which adds a sum of weights times inverse radii to a distance).
+ * Inputs per ray (all fp32, device): fg_t (R,N) ascending, fg_w (R,N), far (R) = the sphere exit of neo_intersect_sphere; bg_s (R,N)
+ * descending inverse radius in [0, 1], bg_w (R,N), lambda (R) = the inside composite's last transmittance (bg_lambda); rays_o,
+ * rays_d (R,3).  bg_s = bg_w = lambda = NULL selects the INSIDE-ONLY histogram (N intervals ending at far: the rows of
+ * neo_tp_render_objects with far = far_obj); giving only some of the three is an error.  1 <= N <= 1024.
+ * HISTOGRAM, M = 2 N intervals in ray order: inside interval i spans [fg_t[i], fg_t[i+1]] with fg_t[N] := far and has mass fg_w[i];
+ * outside interval j spans, in inverse radius, [bg_s[j], bg_s[j+1]] with bg_s[N] := 0 (the reference's 1e10 last step: the last
+ * interval runs out to infinite radius) and has mass lambda * bg_w[j].  The edge at inverse radius s lies at the distance
+ * tau(s) = d1 + sqrt(max(1 / s^2 - rho2, 0)) / |d| with d1 = -(o.d) / |d|^2 and rho2 = |o + d1 d|^2 (|o + t d| = 1 / s); tau(0) = +inf
+ * and tau(1) is the sphere exit, so the histogram is continuous there.  Knots c_0 = 0, c_{k+1} = c_k + m_k: no renormalisation, no clamp.
+ * Everything is fp64 from the fp32 inputs and each output entry is rounded to fp32 once; no atomics, results repeat bit for bit.
+ * Outputs, any of which may be NULL:  opacity (R) = c_M;  disparity (R) = sum_k m_k (1 / a_k + 1 / b_k) / 2 over the interval ends
+ * as distances, 1 / inf = 0 (the expected DISPARITY on purpose: the last outside interval ends at infinity and usually holds the
+ * remaining transmittance, so an expected distance is infinite on every ray that sees sky);  dist_pct (R, n_u) for u (n_u) [device]
+ * ascending quantiles in [0, 1], 0 <= n_u <= 8: +inf when u >= c_M (the ray leaves), otherwise with c_k <= u < c_{k+1} and
+ * off = (u - c_k) / m_k: inside a + off (b - a), outside tau(s_j + off (s_{j+1} - s_j)) - linear in inverse radius.
+ * R == 0 is a valid call.  Touches no context-owned memory. */
+int neo_tp_extras(neo_ctx* ctx, const float* fg_t, const float* fg_w, const float* far, const float* bg_s, const float* bg_w,
+                  const float* lambda, const float* rays_o, const float* rays_d, int R, int N, const float* u, int n_u,
+                  float* opacity, float* disparity, float* dist_pct /* (R, n_u) */, void* stream);
+
+/* neo_tp_render with those extras per level, from the rows the call already has on the device (far from its own sphere intersection,
+ * lambda = bg_lambda of the level): u (n_u) [device] as above, one struct per level; a struct, and any pointer in it, may be NULL.
+ * neo_tp_render IS this call with u = NULL, n_u = 0 and both structs NULL: then the launches, the workspaces and every output are
+ * what they always were.  A level whose extras are asked for has its two composites write their weights too (level 1: two more
+ * lane workspaces of R x N floats) and one more small launch after its merge; the six outputs per level do not change. */
+typedef struct { float* opacity; float* disparity; float* dist_pct; } neo_tp_extras_out;   /* (R), (R), (R, n_u) */
+int neo_tp_render_extras(neo_ctx* ctx, const float* rays_o, const float* rays_d,
+                         const float* viewdirs, int R, int chunk, const float* src_poses, int NV,
+                         float focal, float cx, float cy, int n_coarse, int n_fine, int white_bkgd,
+                         const neo_tp_level_out* level0, const neo_tp_level_out* level1, const float* u, int n_u,
+                         const neo_tp_extras_out* extras0, const neo_tp_extras_out* extras1, void* stream);
+
 /* The same render with BACKGROUND CULLING (opt-in).  The composite is rgb = fg_rgb + bg_lambda * bg_rgb and depth = fg_depth +
  * bg_lambda * bg_depth, bg_lambda being the foreground's final transmittance, and nothing in a ray's background half feeds
  * its foreground half.  The foreground of BOTH levels is therefore finished first; a ray survives iff

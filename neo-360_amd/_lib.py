@@ -30,6 +30,10 @@ class TpLevelOut(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth")]
 
 
+class TpExtrasOut(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("opacity", "disparity", "dist_pct")]
+
+
 class TpObjectOut(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("rgb", "acc", "depth", "tvals")]
 
@@ -74,6 +78,10 @@ SIGNATURES = {
     "neo_tp_mlp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, c_float_p, _i, _f, _f, _f, _vp, _vp]),
     "neo_tp_render": (_i, [_vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,
                            ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), _vp]),
+    "neo_tp_extras": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "neo_tp_render_extras": (_i, [_vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,
+                                  ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), _vp, _i,
+                                  ctypes.POINTER(TpExtrasOut), ctypes.POINTER(TpExtrasOut), _vp]),
     "neo_tp_render_culled": (_i, [_vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,
                                   ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), _f, _vp, _vp]),
     "neo_tp_render_objects": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,

@@ -328,9 +328,29 @@ int neo_tp_mlp(neo_ctx* ctx, int slot, const float* rays_o, const float* rays_d,
 int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
                   const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
                   int white_bkgd, const neo_tp_level_out* level0, const neo_tp_level_out* level1, void* stream) {
+    return neo_tp_render_extras(ctx, rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, white_bkgd,
+                                level0, level1, nullptr, 0, nullptr, nullptr, stream);
+}
+
+// neo_tp_render with the extras of tp_extras.hip per level.  Without them (both structs NULL or empty) the launch list, the
+// workspaces and every output are neo_tp_render's as they always were: the level-1 composites pass a NULL w_out and W[10] / W[11]
+// are not touched.  A level whose extras are asked for has its two composites write their weights as well (level 0 does so anyway,
+// for the resampling; level 1 into W[10] / W[11]) and one k_tp_extras launch follows its merge.
+int neo_tp_render_extras(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                         const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                         int white_bkgd, const neo_tp_level_out* level0, const neo_tp_level_out* level1, const float* u_extras,
+                         int n_u, const neo_tp_extras_out* extras0, const neo_tp_extras_out* extras1, void* stream) {
     ENTER(ctx);
     REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
     REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
+    REQUIRE(n_u >= 0 && n_u <= 8, "bad quantile count (0 <= n_u <= 8)");
+    const neo_tp_extras_out* extras[2] = {extras0, extras1};
+    bool want_extras[2];
+    for (int l = 0; l < 2; ++l) {
+        const neo_tp_extras_out* ex = extras[l];
+        want_extras[l] = ex && (ex->opacity || ex->disparity || (ex->dist_pct && n_u > 0));
+        REQUIRE(!(ex && ex->dist_pct && n_u > 0) || u_extras, "null quantile table");
+    }
     if (R == 0) return NEO_OK;
     REQUIRE(rays_o && rays_d && viewdirs && src_poses, "null pointer");
     if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
@@ -359,6 +379,7 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const 
         W[4].reserve(r * N1 * 16) || W[5].reserve(r * N0 * 4) || W[6].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) ||
         W[8].reserve(r * N1 * 4) || W[9].reserve(r * 16 * 4))
         return NEO_ERR_NOMEM;
+    if (want_extras[1] && (W[10].reserve(r * N1 * 4) || W[11].reserve(r * N1 * 4))) return NEO_ERR_NOMEM;
     float* far = W[0].as<float>();
     float* fg_t0 = W[1].as<float>();
     float* bg_s0 = W[2].as<float>();
@@ -368,6 +389,8 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const 
     float* bg_w0 = W[6].as<float>();
     float* fg_t1 = W[7].as<float>();
     float* bg_s1 = W[8].as<float>();
+    float* fg_w1 = want_extras[1] ? W[10].as<float>() : nullptr;      // level-1 weights: only the extras read them
+    float* bg_w1 = want_extras[1] ? W[11].as<float>() : nullptr;
     float* scratch = W[9].as<float>();   // per-ray: fg_rgb(3) fg_depth fg_acc lambda bg_rgb(3) bg_depth
     float* s_fg_rgb = scratch;
     float* s_fg_depth = scratch + r * 3;
@@ -396,12 +419,19 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const 
         float* bg_rgb = dens ? nullptr : (lo && lo->bg_rgb) ? lo->bg_rgb : s_bg_rgb;
         float* fg_acc = (lo && lo->fg_acc) ? lo->fg_acc : s_fg_acc;
         float* lam = (lo && lo->bg_lambda) ? lo->bg_lambda : s_lambda;
-        neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, fg_rgb, fg_acc, dens ? nullptr : s_fg_depth,
-                              level == 0 ? fg_w0 : nullptr, lam, s);
-        neo::launch_composite(2, bg_out, bg_s, N, nullptr, nullptr, R, N, 0, bg_rgb, nullptr, dens ? nullptr : s_bg_depth,
-                              level == 0 ? bg_w0 : nullptr, nullptr, s);
+        float* fg_w = level == 0 ? fg_w0 : fg_w1;
+        float* bg_w = level == 0 ? bg_w0 : bg_w1;
+        neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, fg_rgb, fg_acc, dens ? nullptr : s_fg_depth, fg_w, lam, s);
+        neo::launch_composite(2, bg_out, bg_s, N, nullptr, nullptr, R, N, 0, bg_rgb, nullptr, dens ? nullptr : s_bg_depth, bg_w,
+                              nullptr, s);
         if (lo && (lo->rgb || lo->depth))
             neo::launch_tp_merge(fg_rgb, s_fg_depth, lam, bg_rgb, s_bg_depth, R, lo->rgb, lo->depth, s);
+        if (want_extras[level]) {
+            const neo_tp_extras_out* ex = extras[level];
+            if (neo::launch_tp_extras(fg_t, fg_w, far, bg_s, bg_w, lam, rays_o, rays_d, R, N, u_extras, n_u, ex->opacity, ex->disparity,
+                                      ex->dist_pct, s))
+                return fail(NEO_ERR_INVALID, "unsupported sample or quantile count");
+        }
         if (level == 0) {
             // hierarchical resampling (model.py:306-332): fg ascending; bg on the descending inverse radius
             if (neo::launch_resample(fg_t0, N0, fg_w0, u, 0, R, N0, n_fine, 0, fg_t1, s) ||
@@ -414,6 +444,23 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const 
     return check_launch();
 }
 
+
+// the pure function of tp_extras.hip on caller rows; touches no context-owned memory: no ordering scope (as neo_mip_extras)
+int neo_tp_extras(neo_ctx* ctx, const float* fg_t, const float* fg_w, const float* far, const float* bg_s, const float* bg_w,
+                  const float* lambda, const float* rays_o, const float* rays_d, int R, int N, const float* u, int n_u, float* opacity,
+                  float* disparity, float* dist_pct, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && N >= 1 && N <= 1024, "bad shape (1 <= N <= 1024)");
+    REQUIRE(n_u >= 0 && n_u <= 8, "bad quantile count (0 <= n_u <= 8)");
+    REQUIRE((bg_s != nullptr) == (bg_w != nullptr) && (bg_s != nullptr) == (lambda != nullptr),
+            "bg_s, bg_w and lambda go together: all three, or none for the inside-only histogram");
+    if (R == 0) return NEO_OK;
+    REQUIRE(fg_t && fg_w && far && rays_o && rays_d && (u || n_u == 0 || !dist_pct), "null pointer");
+    if (neo::launch_tp_extras(fg_t, fg_w, far, bg_s, bg_w, lambda, rays_o, rays_d, R, N, u, n_u, opacity, disparity, dist_pct,
+                              static_cast<hipStream_t>(stream)))
+        return fail(NEO_ERR_INVALID, "unsupported sample or quantile count");
+    return check_launch();
+}
 
 int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
                          const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,

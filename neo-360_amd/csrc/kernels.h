@@ -223,6 +223,16 @@ int launch_mip_extras(const float* edges, const float* w, int R, int n, float ne
 int launch_mip_extras_bwd(const float* edges, const float* w, int R, int n, float near, float far, const float* g_acc,
                           const float* g_mean, float* g_w, hipStream_t s);
 
+// tp_extras.hip — opacity, expected disparity and distance percentiles of a NeO-360 ray's whole interval histogram (inside + outside
+// the sphere) as distances along the ray, one wave per ray, fp64 between fp32 ends.  fg_t / fg_w (R,N), far (R): the inside rows and
+// the sphere exit; bg_s / bg_w (R,N), lambda (R): the outside rows (inverse radius, descending) and the inside composite's last
+// transmittance - all three null: the inside-only histogram; rays_o / rays_d (R,3); u (n_u) device quantiles -> opacity (R),
+// disparity (R), dist_pct (R,n_u), each may be null.  Return -1 outside 1 <= N <= 1024, 0 <= n_u <= 8, or when only some of the
+// three outside pointers are given.
+int launch_tp_extras(const float* fg_t, const float* fg_w, const float* far, const float* bg_s, const float* bg_w, const float* lambda,
+                     const float* rays_o, const float* rays_d, int R, int N, const float* u, int n_u, float* opacity, float* disparity,
+                     float* dist_pct, hipStream_t s);
+
 // mlp_tp_h.hip — the NeO-360 evaluator on the fp16 matrix cores (hi/lo-split operands, fp32-equivalent)
 struct TpMlpHDev {
     const void* wpack;    // fp16 hi/lo fragments

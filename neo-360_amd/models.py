@@ -19,7 +19,7 @@ import weakref
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, ops
 from .context import CallOverlap, f32, new_context, ptr, ptr_table
 
 
@@ -675,7 +675,8 @@ class NeRF_TP(_HipModule):
         """out_depth=True (evaluation, neo360/model.py:521-527): per level (comp_rgb, fg_rgb, bg_rgb, fg_acc, bg_lambda,
         comp_depth), randomized=False.  With `fine_only=True` that call returns [None, level-1 tuple]: the coarse level then
         only delivers the densities the fine samples are drawn from (no level-0 tensors, density-only coarse launches where the
-        evaluator has them); the level-1 tuple is bitwise the default call's.  out_depth=False (the training call, :531-579): per level (comp_rgb, fg_weights,
+        evaluator has them); the level-1 tuple is bitwise the default call's.  With `self.compute_extras` every returned level gains
+        a seventh element, the dict of opacity / disparity / distance percentiles described at that attribute.  out_depth=False (the training call, :531-579): per level (comp_rgb, fg_weights,
         bg_weights, fg_sdist, bg_sdist, bg_acc), randomized as asked.  `near`/`far` are ignored
         exactly as in the reference (:277-278).  All rays of the call form ONE reference chunk unless `chunk` is given
         (whole-frame rendering, see render.py).
@@ -702,8 +703,29 @@ class NeRF_TP(_HipModule):
         with torch.no_grad():
             return self._forward_eval(rays, randomized, white_bkgd, chunk, fine_only)
 
+    # Opt-in extras of the deterministic out_depth=True call (neo_tp_render_extras, csrc/tp_extras.hip).  True: every returned
+    # level's tuple gains a SEVENTH element, dict(opacity (B,), disparity (B,), distance_percentiles (B, len(extras_quantiles))) of
+    # the ray's whole interval histogram, inside and outside the sphere together, as DISTANCES ALONG THE RAY (the unit of the ray
+    # parameter t of o + t d, i.e. of the reference's fg_depth - its comp_depth adds a disparity to a distance, model.py:523):
+    # the total opacity (fg_acc + bg_lambda * bg_acc, which the six-tuple does not carry), the expected disparity, and the distance
+    # at each quantile of the cumulative mass (+inf where the ray leaves with more transmittance than the quantile allows) - with the
+    # default three quantiles also as distance_percentile_5 / distance_median / distance_percentile_95.  Definitions: ops.tp_extras.
+    # The first six elements are bitwise those of the call without it; the level-1 composites then also write their weights and one
+    # small launch per level follows.  False (default): the six-tuples and the launch list are unchanged.  Not combined with
+    # `cull_background` (a culled ray has no outside rows): ValueError.  The training calls do not read it.
+    compute_extras = False
+    extras_quantiles = (0.05, 0.5, 0.95)      # at most 8, ascending, in [0, 1]
+    _DEFAULT_EXTRAS_QUANTILES = (0.05, 0.5, 0.95)
+
     def _forward_eval(self, rays, randomized, white_bkgd, chunk=None, fine_only=False):
         self._check_mode(randomized)
+        extras_on = bool(self.compute_extras)
+        if extras_on:
+            if self.cull_background is not None:
+                raise ValueError("compute_extras and cull_background are not combined: a culled ray has no outside rows")
+            quant = tuple(float(q) for q in self.extras_quantiles)
+            if len(quant) > ops.MAX_EXTRA_QUANTILES:
+                raise ValueError("at most %d extras_quantiles, got %d" % (ops.MAX_EXTRA_QUANTILES, len(quant)))
         raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
         rays_o = f32(raw[0], "rays_o")
         rays_d = f32(raw[1], "rays_d")
@@ -722,6 +744,7 @@ class NeRF_TP(_HipModule):
         grid = getattr(self, "ray_grid", None)
         ctx.set_ray_grid(*(grid if grid and grid[0] % 8 == 0 and B >= 8 * grid[0] else (0, 0)))
         levels = []
+        extras, extra_structs = [None, None], [None, None]
         eps = self.cull_background
 
         def launch():
@@ -736,11 +759,21 @@ class NeRF_TP(_HipModule):
                          bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
                 levels.append(t)
                 structs.append(_lib.TpLevelOut(*(t[k].data_ptr() for k in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth"))))
+                if extras_on:
+                    e = dict(opacity=torch.empty(B, device=dev), disparity=torch.empty(B, device=dev),
+                             distance_percentiles=torch.empty(B, len(quant), device=dev))
+                    extras[level] = e
+                    extra_structs[level] = _lib.TpExtrasOut(*(e[k].data_ptr() for k in ("opacity", "disparity", "distance_percentiles")))
             args = (ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), B, int(chunk or max(B, 1)), host_poses, NV, focal, cx, cy,
                     self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
                     ctypes.byref(structs[0]) if structs[0] is not None else None, ctypes.byref(structs[1]))
             extra = []
-            if eps is None:
+            if extras_on:
+                tab = ops._quantile_table(quant, dev) if quant else None
+                _lib.check(ctx.lib.neo_tp_render_extras(
+                    *args, ptr(tab), len(quant), *(ctypes.byref(x) if x is not None else None for x in extra_structs), ctx.stream()))
+                extra += [v for e in extras if e is not None for v in e.values()]
+            elif eps is None:
                 _lib.check(ctx.lib.neo_tp_render(*args, ctx.stream()))
             else:
                 # the survivor count stays on the device: written by the compaction, never read inside the call
@@ -754,8 +787,17 @@ class NeRF_TP(_HipModule):
             ctx.set_ray_grid(0)
         if eps is not None:
             self.last_cull_survivors = made[-1]
-        return [None if t is None else (t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"])
-                for t in levels]
+        out = [None if t is None else (t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"])
+               for t in levels]
+        if extras_on:
+            for level, e in enumerate(extras):
+                if e is None:
+                    continue
+                if quant == self._DEFAULT_EXTRAS_QUANTILES:
+                    pct = e["distance_percentiles"]
+                    e.update(distance_percentile_5=pct[:, 0], distance_median=pct[:, 1], distance_percentile_95=pct[:, 2])
+                out[level] = out[level] + (e,)
+        return out
 
     @staticmethod
     def _object_bound(rays, given, key, B):

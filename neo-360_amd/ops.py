@@ -238,3 +238,65 @@ def mip_extras(edges, w, u=(0.05, 0.5, 0.95), near=0.0, far=0.0, ctx=None):
                                       ptr(pct), ctx.stream()))
     lead = w.shape[:-1]
     return acc.reshape(lead), mean.reshape(lead), pct.reshape(*lead, n_u)
+
+
+MAX_EXTRA_QUANTILES = 8
+
+
+def _extras_row(t, name, shapes, dev):
+    if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+        raise ValueError("%s must be a floating-point tensor, got %r" % (name, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
+    if tuple(t.shape) not in shapes:
+        raise ValueError("%s must have shape %s, got %s" % (name, " or ".join(str(s) for s in shapes), tuple(t.shape)))
+    if t.device != dev:
+        raise ValueError("%s must be on the device of fg_t (%s), got %s" % (name, dev, t.device))
+    return f32(t, name)
+
+
+@torch.no_grad()
+def tp_extras(fg_t, fg_w, far, rays_o, rays_d, bg_s=None, bg_w=None, bg_lambda=None, quantiles=(0.05, 0.5, 0.95), ctx=None):
+    """Opacity, expected disparity and distance percentiles of a NeO-360 ray's WHOLE interval histogram, inside and outside the unit
+    sphere together (neo_tp_extras).  Distances are in the unit of the ray parameter t of o + t d - the unit of the reference's
+    fg_depth, not that of its comp_depth (neo360/model.py:523 adds a disparity to a distance).
+
+    fg_t (R,N) ascending, fg_w (R,N), far (R,) or (R,1) the sphere exit (ops.intersect_sphere); rays_o, rays_d (R,3); bg_s (R,N)
+    descending inverse radius, bg_w (R,N), bg_lambda (R,) or (R,1) the inside composite's last transmittance.  Without the three
+    outside arguments: the inside-only histogram of N intervals ending at `far` (the rows of render_objects(return_samples=True)
+    with far = far_obj).  M = 2 N intervals in ray order: inside [fg_t[i], fg_t[i+1]] (fg_t[N] := far) with mass fg_w[i]; outside, in
+    inverse radius, [bg_s[j], bg_s[j+1]] (bg_s[N] := 0: out to infinite radius) with mass bg_lambda bg_w[j], its edges at the
+    distance tau(s) = d1 + sqrt(max(1 / s^2 - rho2, 0)) / |d|, d1 = -(o.d) / |d|^2, rho2 = |o + d1 d|^2.  fp64 between fp32 ends.
+
+    Returns dict(opacity (R,) = total mass, disparity (R,) = sum m (1 / a + 1 / b) / 2 over the interval ends as distances
+    (1 / inf = 0), distance_percentiles (R, len(quantiles))): +inf where the quantile is not below the opacity (the ray leaves),
+    otherwise linear inside its interval - in distance inside the sphere, in inverse radius outside.  quantiles: at most 8,
+    ascending, in [0, 1]; a sequence (its device table is kept) or an fp32 device tensor.
+    Raises ValueError for shapes, dtypes or devices that do not fit, more than 8 quantiles, or only some of bg_s / bg_w / bg_lambda."""
+    if not isinstance(fg_t, torch.Tensor) or fg_t.dim() != 2 or not fg_t.is_cuda:
+        raise ValueError("fg_t must be a (R, N) device tensor")
+    R, N = fg_t.shape
+    dev = fg_t.device
+    outside = (bg_s, bg_w, bg_lambda)
+    if any(t is None for t in outside) and not all(t is None for t in outside):
+        raise ValueError("bg_s, bg_w and bg_lambda go together: give all three, or none for the inside-only histogram")
+    if not 1 <= N <= 1024:
+        raise ValueError("1 <= N <= 1024 samples per region, got %d" % N)
+    fg_t = _extras_row(fg_t, "fg_t", ((R, N),), dev)
+    fg_w = _extras_row(fg_w, "fg_w", ((R, N),), dev)
+    far = _extras_row(far, "far", ((R,), (R, 1)), dev)
+    rays_o = _extras_row(rays_o, "rays_o", ((R, 3),), dev)
+    rays_d = _extras_row(rays_d, "rays_d", ((R, 3),), dev)
+    if bg_s is not None:
+        bg_s = _extras_row(bg_s, "bg_s", ((R, N),), dev)
+        bg_w = _extras_row(bg_w, "bg_w", ((R, N),), dev)
+        bg_lambda = _extras_row(bg_lambda, "bg_lambda", ((R,), (R, 1)), dev)
+    if isinstance(quantiles, torch.Tensor) and (quantiles.device != dev or not quantiles.is_floating_point()):
+        raise ValueError("a quantile tensor must be a floating-point tensor on the device of fg_t")
+    n_u = quantiles.numel() if isinstance(quantiles, torch.Tensor) else len(quantiles)
+    if n_u > MAX_EXTRA_QUANTILES:
+        raise ValueError("at most %d quantiles per call, got %d" % (MAX_EXTRA_QUANTILES, n_u))
+    tab = _quantile_table(quantiles, dev) if n_u else None
+    ctx = _ctx(fg_t, ctx)
+    opacity, disparity, pct = torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, n_u, device=dev)
+    _lib.check(ctx.lib.neo_tp_extras(ctx.handle, ptr(fg_t), ptr(fg_w), ptr(far), ptr(bg_s), ptr(bg_w), ptr(bg_lambda), ptr(rays_o),
+                                     ptr(rays_d), R, N, ptr(tab), n_u, ptr(opacity), ptr(disparity), ptr(pct), ctx.stream()))
+    return dict(opacity=opacity, disparity=disparity, distance_percentiles=pct)

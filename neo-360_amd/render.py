@@ -31,7 +31,13 @@ def _slice(batch, lo, hi):
 def _render_once(model, batch, chunk, white_bkgd, near, far, train_frac):
     if isinstance(model, models.NeRF_TP):
         res = model(batch, False, white_bkgd, near, far, out_depth=True, chunk=chunk, fine_only=True)      # only res[1] is read
-        return dict(rgb=res[1][0], depth=res[1][5], fg_rgb=res[1][1], bg_rgb=res[1][2], acc=res[1][3])
+        out = dict(rgb=res[1][0], depth=res[1][5], fg_rgb=res[1][1], bg_rgb=res[1][2], acc=res[1][3])
+        if model.compute_extras:            # the fine level's extras ride along; every other key keeps its meaning
+            extras = res[1][6]
+            named = ("distance_median", "distance_percentile_5", "distance_percentile_95")
+            for k in ("opacity", "disparity") + (named if named[0] in extras else ("distance_percentiles",)):
+                out[k] = extras[k]
+        return out
     if isinstance(model, models.PixelNeRF):
         res = model(batch, False, white_bkgd, near, far, chunk=chunk)      # vanilla_nerf/model_pixel.py:356-383
         return dict(rgb=res[1][0], depth=res[1][2], acc=res[1][1])
@@ -109,7 +115,11 @@ def render_rays_test(model, batch, chunk=1024, white_bkgd=False, near=0.2, far=3
     render_rays_test returns them: dict(rgb (R,3), depth (R,)) plus `target` /
     `instance_mask` passed through when present.  A MipNeRF360 returns depth = 0 (the reference renders rgb only) unless
     `model.compute_extras` is set: then depth = the final level's expected distance (`distance_mean`), acc the kernel's own
-    sum, and `distance_median` / `distance_percentile_5` / `distance_percentile_95` ride along.  check=True waits for the frame and raises what the device-side
+    sum, and `distance_median` / `distance_percentile_5` / `distance_percentile_95` ride along.  A NeRF_TP with
+    `model.compute_extras` set adds `opacity`, `disparity`, `distance_median`, `distance_percentile_5` and `distance_percentile_95`
+    of the fine level (distances along the ray, in the unit of the ray parameter t of o + t d; `distance_percentiles` instead of the
+    three named ones when `model.extras_quantiles` is not the default); `depth` and `acc` stay the reference's composite depth and
+    the foreground's opacity.  check=True waits for the frame and raises what the device-side
     assertions reported (a ray that missed the unit sphere); check=False leaves that to
     a later `model.check_flags()` (a loop over frames that never wants to block).
 
