@@ -2,7 +2,8 @@
 //   k_mip_encode          the 504-d integrated positional encoding of every interval as fp32 rows - conical frustum -> Gaussian ->
 //                         contraction -> lift onto the 21-direction basis -> IPE (helper.py:33-88, 278-334) - the input of the
 //                         MLPs when the caller composes them from linear-layer operators (api_train.hip: neo_linear_*);
-//                         the same arithmetic, statement by statement, as the point set-up of the fused evaluators (mlp_mip.hip)
+//                         the statements of the point set-up of the fused evaluators (mlp_mip.hip), carried in float64 up to
+//                         the sine and the exponential
 //   k_mip_composite_bwd   backward of compute_alpha_weights(opaque_background=True) + volumetric_rendering (helper.py:246-275):
 //                         gradients of the interval weights and of the composited colour -> gradients of rgb and density
 // The sample positions carry no gradient (model.py:308-309: stop_level_grad), so the encoding needs no backward.
@@ -22,56 +23,60 @@ constexpr float EPS32 = 1.1920929e-07f;
 
 // Gaussian of interval i of a ray, contracted: z (3) and J cov J^T (3 x 3).  conical_frustum_to_gaussian (helper.py:293-306),
 // lift_gaussian with diag=False (:320-334), contract with the closed form of the reference's autograd Jacobian (:33-66).
+// In float64 on the fp32 inputs: octave k multiplies an error of the lifted mean by 2^k, so an fp32 mean (1 .. 3 ulp after this
+// chain) costs up to 3e-4 of a feature at octave 11, and WHICH rows it costs most is an accident of the rounding - per (row, octave)
+// an fp32 evaluation can be several times further from the exact encoding than another one (tests/test_gpu_frontend_sweep.py::
+// test_mip_encode_rows_per_row_and_octave, docs/frontend_sweep.md).  8 of a block's 256 threads run this, once per row.
 __device__ __forceinline__ void mip_row_gaussian(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                  const float* __restrict__ radii, const float* __restrict__ tdist, int ray, int i,
-                                                 int n, float (&z)[3], float (&cc)[3][3]) {
-    const float t0 = tdist[(long)ray * (n + 1) + i], t1 = tdist[(long)ray * (n + 1) + i + 1];
-    float o[3], d[3];
+                                                 int n, double (&z)[3], double (&cc)[3][3]) {
+    const double t0 = tdist[(long)ray * (n + 1) + i], t1 = tdist[(long)ray * (n + 1) + i + 1];
+    double o[3], d[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) { o[a] = rays_o[ray * 3 + a]; d[a] = rays_d[ray * 3 + a]; }
-    const float rad = radii[ray];
-    const float mu = (t0 + t1) / 2.0f, hw = (t1 - t0) / 2.0f;
-    const float mu2 = mu * mu, hw2 = hw * hw;
-    const float denom = fmaxf(3.0f * mu2 + hw2, EPS32);
-    const float t_mean = mu + (2.0f * mu * hw2) / denom;
-    const float hw4 = hw2 * hw2;
-    const float t_var = hw2 / 3.0f - (4.0f / 15.0f) * hw4 * (12.0f * mu2 - hw2) / (denom * denom);
-    float r_var = mu2 / 4.0f + (5.0f / 12.0f) * hw2 - (4.0f / 15.0f) * hw4 / denom;
+    const double rad = radii[ray];
+    const double mu = (t0 + t1) / 2.0, hw = (t1 - t0) / 2.0;
+    const double mu2 = mu * mu, hw2 = hw * hw;
+    const double denom = fmax(3.0 * mu2 + hw2, (double)EPS32);
+    const double t_mean = mu + (2.0 * mu * hw2) / denom;
+    const double hw4 = hw2 * hw2;
+    const double t_var = hw2 / 3.0 - (4.0 / 15.0) * hw4 * (12.0 * mu2 - hw2) / (denom * denom);
+    double r_var = mu2 / 4.0 + (5.0 / 12.0) * hw2 - (4.0 / 15.0) * hw4 / denom;
     r_var = r_var * (rad * rad);
-    float x[3];
+    double x[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) x[a] = d[a] * t_mean + o[a];
-    const float dm = fmaxf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2], 1e-10f);
-    float cov[3][3];
+    const double dm = fmax(d[0] * d[0] + d[1] * d[1] + d[2] * d[2], 1e-10);
+    double cov[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
-            const float outer = d[a] * d[b];
-            const float null_o = (a == b ? 1.0f : 0.0f) - d[a] * (d[b] / dm);
+            const double outer = d[a] * d[b];
+            const double null_o = (a == b ? 1.0 : 0.0) - d[a] * (d[b] / dm);
             cov[a][b] = t_var * outer + r_var * null_o;
         }
-    const float msq = fmaxf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2], 1e-32f);
-    float J[3][3];
-    if (msq <= 1.0f) {
+    const double msq = fmax(x[0] * x[0] + x[1] * x[1] + x[2] * x[2], 1e-32);
+    double J[3][3];
+    if (msq <= 1.0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             z[a] = x[a];
 #pragma unroll
-            for (int b = 0; b < 3; ++b) J[a][b] = a == b ? 1.0f : 0.0f;
+            for (int b = 0; b < 3; ++b) J[a][b] = a == b ? 1.0 : 0.0;
         }
     } else {
-        const float rt = sqrtf(msq);
-        const float sc = (2.0f * rt - 1.0f) / msq;
-        const float coef = 2.0f / (msq * rt) - 2.0f * sc / msq;
+        const double rt = sqrt(msq);
+        const double sc = (2.0 * rt - 1.0) / msq;
+        const double coef = 2.0 / (msq * rt) - 2.0 * sc / msq;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             z[a] = sc * x[a];
 #pragma unroll
-            for (int b = 0; b < 3; ++b) J[a][b] = (a == b ? sc : 0.0f) + coef * x[a] * x[b];
+            for (int b = 0; b < 3; ++b) J[a][b] = (a == b ? sc : 0.0) + coef * x[a] * x[b];
         }
     }
-    float tmp[3][3];
+    double tmp[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -82,12 +87,31 @@ __device__ __forceinline__ void mip_row_gaussian(const float* __restrict__ rays_
         for (int b = 0; b < 3; ++b) cc[a][b] = tmp[a][0] * J[b][0] + tmp[a][1] * J[b][1] + tmp[a][2] * J[b][2];
 }
 
-// out (R n, 504): feature f < 252: exp(-var_j 4^k / 2) sin(mean_j 2^k), f = 21 k + j; f >= 252: the same with the phase fl32(pi/2)
+// sin(a) (shifted: sin(a + pi/2)) of a float64 argument to fp32 accuracy: the reduction by pi/2 in float64 (pi/2 as a
+// double-double, as common.h:sin_big), then the fp32 polynomials of the other encodings.  Beyond 1e9 (no scene reaches it: a
+// contracted mean is below 2, octave 11 multiplies it by 2048) and for inf / NaN: the fp32 sine of the rounded argument.
+__device__ __forceinline__ float sin_of_double(double a, bool shifted) {
+    if (!(fabs(a) <= 1.0e9)) return sin_cw(shifted ? (float)a + HALF_PI_F32 : (float)a);
+    const double kd = rint(a * 0.63661977236758138);
+    double rd = __builtin_fma(-kd, 1.5707963267948966, a);
+    rd = __builtin_fma(-kd, 6.123233995736766e-17, rd);
+    const int q = (int)kd + (shifted ? 1 : 0);
+    float sn, cs;
+    sincos_poly((float)rd, sn, cs);
+    const float res = (q & 1) ? cs : sn;
+    return (q & 2) ? -res : res;
+}
+
+// out (R n, 504): feature f < 252: exp(-var_j 4^k / 2) sin(mean_j 2^k), f = 21 k + j; f >= 252: the same with the phase pi/2.
+// Means and variances are float64 up to the two fp32 function evaluations: a feature is within 1.2e-7 of the exact encoding of
+// the fp32 inputs at every octave (the largest error over tests/frontend_cases.py's table).  The fused inference evaluators
+// (mlp_mip.hip) keep fp32 means and the reference's fl32(arg + fl32(pi/2)) phase: the two paths differ by up to the rounding of
+// an fp32 argument, 2e-4 at octave 11 before the damping - on purpose.
 __global__ __launch_bounds__(256) void k_mip_encode(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                     const float* __restrict__ radii, const float* __restrict__ tdist,
                                                     const float* __restrict__ basis, int R, int n, float* __restrict__ out) {
-    __shared__ float rowz[ER][12];
-    __shared__ float lift[ER][2 * NB];
+    __shared__ double rowz[ER][12];
+    __shared__ double lift[ER][2 * NB];
     const int tid = threadIdx.x;
     const long P = (long)R * n;
     const long row0 = (long)blockIdx.x * ER;
@@ -95,7 +119,7 @@ __global__ __launch_bounds__(256) void k_mip_encode(const float* __restrict__ ra
         long g = row0 + tid;
         if (g >= P) g = P - 1;
         const int ray = (int)(g / n), i = (int)(g - (long)ray * n);
-        float z[3], cc[3][3];
+        double z[3], cc[3][3];
         mip_row_gaussian(rays_o, rays_d, radii, tdist, ray, i, n, z, cc);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -108,11 +132,11 @@ __global__ __launch_bounds__(256) void k_mip_encode(const float* __restrict__ ra
     // lift_and_diagonalize (helper.py:70-73): mean_j = z . b_j ; var_j = sum_a b_aj (cov b_j)_a
     if (tid < ER * NB) {
         const int row = tid / NB, j = tid - row * NB;
-        const float b0 = basis[j], b1 = basis[NB + j], b2 = basis[2 * NB + j];
-        const float* rz = rowz[row];
-        const float mj = rz[0] * b0 + rz[1] * b1 + rz[2] * b2;
-        float vj = 0.f;
-        const float bb[3] = {b0, b1, b2};
+        const double b0 = basis[j], b1 = basis[NB + j], b2 = basis[2 * NB + j];
+        const double* rz = rowz[row];
+        const double mj = rz[0] * b0 + rz[1] * b1 + rz[2] * b2;
+        double vj = 0.0;
+        const double bb[3] = {b0, b1, b2};
 #pragma unroll
         for (int a = 0; a < 3; ++a) vj += bb[a] * (rz[3 + a * 3] * b0 + rz[3 + a * 3 + 1] * b1 + rz[3 + a * 3 + 2] * b2);
         lift[row][j] = mj;
@@ -125,9 +149,8 @@ __global__ __launch_bounds__(256) void k_mip_encode(const float* __restrict__ ra
         const bool shifted = f >= 252;
         const int g = shifted ? f - 252 : f;
         const int k = g / NB, j = g - k * NB;
-        const float mean = lift[row][j], var = lift[row][NB + j];
-        const float arg = ldexpf(mean, k);
-        out[(row0 + row) * 504 + f] = expf(-0.5f * ldexpf(var, 2 * k)) * sin_cw(shifted ? arg + HALF_PI_F32 : arg);
+        const double mean = lift[row][j], var = lift[row][NB + j];
+        out[(row0 + row) * 504 + f] = expf((float)(-0.5 * ldexp(var, 2 * k))) * sin_of_double(ldexp(mean, k), shifted);
     }
 }
 
