@@ -387,6 +387,48 @@ int neo_tp_render_instances(neo_ctx* ctx, const float* rays_o, const float* rays
                             float focal, float cx, float cy, int n_coarse, int n_fine, int white_bkgd,
                             const neo_tp_instance_out* level0, const neo_tp_instance_out* level1, int* pairs_out, void* stream);
 
+/* EDITED render: the scene WITHOUT an instance, or with an instance faded, tinted or - as a layer - standing somewhere else.
+ * EDIT RULE (neo_tp_edit_rows; in place on rgbsigma (R,N,4) at the sample rows t (R,N)): near_inst / far_inst (K,R) [device],
+ * 0 <= K <= 32, values of the ray parameter t of o + t rays_d exactly as neo_tp_render_objects reads them; pair (i, ray) is a hit by
+ * the HIT RULE above (lo = max(near, 1e-4), hi = far, both finite, hi > lo; a NaN bound is a miss); sample j is INSIDE pair i iff
+ * lo <= t_j && t_j <= hi (closed: neo_tp_render_objects places samples on both ends).  For i = 0 .. K-1 in index order, if inside:
+ * sigma *= scale[i]; r *= tint[i][0]; g *= tint[i][1]; b *= tint[i][2] - plain fp32 multiplies, so overlapping intervals multiply;
+ * a sample inside no interval is not written.  density_scale (K) and tint (K,3) are HOST arrays (NULL = all ones) that travel to
+ * the kernel by value; they must be finite and >= 0.  K == 0 and R == 0 are valid calls.  Touches no context-owned memory. */
+int neo_tp_edit_rows(neo_ctx* ctx, float* rgbsigma, const float* t, const float* near_inst, const float* far_inst, int K,
+                     const float* density_scale, const float* tint, int R, int N, void* stream);
+
+/* neo_composite mode 1 with 0 <= L <= 32 per-ray LAYERS spliced into the ray.  Layer l of a ray: key (L,R) a ray parameter, acc
+ * (L,R) its opacity a_l, rgb (L,R,3) its premultiplied colour p_l, depth (L,R) its premultiplied depth d_l [all device].
+ * LAYER RECURRENCE: a layer is valid iff key_l is finite and a_l > 0 (written so that a NaN is invalid); valid layers are ordered
+ * by ascending key, ties to the lower index; keep_l = max(1 - a_l, 0) in fp32, then widened to double.  S(j) = the scene's own
+ * exclusive transmittance before sample j (carry * excl of the fp64 scan of neo_composite), S_end the one after its last sample;
+ * A(j) = the fp64 product, in layer order, of keep_l over the valid layers with key_l <= t_j; B(l) = that of the valid layers
+ * ordered before l; j_l = the first sample with t_j >= key_l.  Sample j contributes with trans = (float)(S(j) A(j)), w' = alpha_j
+ * trans: w' c_j to rgb, w' to acc, w' t_j to depth.  Layer l contributes with v = (float)(S(j_l) B(l)), or (float)(S_end B(l))
+ * when no such sample exists: v p_l, v a_l, v d_l; visibility (L,R) receives v a_l, and 0 for an invalid layer.  lambda =
+ * (float)(S_end * the product of all valid keeps).  weights (R,N) receives the SCENE weight alpha_j (float)S(j) - what neo_composite
+ * writes, so that a resampling that follows does not depend on the layers.  A layer is a slab at its key, not a merged medium.
+ * With no valid layer every output is bitwise neo_composite(mode 1, white_bkgd 0).  Any output may be NULL; R == 0 and L == 0 are
+ * valid calls.  Touches no context-owned memory. */
+typedef struct { const float* key; const float* rgb; const float* acc; const float* depth; } neo_tp_layers;
+int neo_composite_layers(neo_ctx* ctx, const float* rgbsigma, const float* t, const float* rays_d, const float* t_far, int R, int N,
+                         const neo_tp_layers* layers, int L, float* rgb, float* acc, float* depth, float* weights, float* lambda,
+                         float* visibility /* (L,R) */, void* stream);
+
+/* neo_tp_render (out_depth=True semantics, the coarse level always evaluated in full) with the EDIT RULE applied to the
+ * inside-sphere rows of each level before their composite, and - when L > 0 - that composite done by the LAYER RECURRENCE with the
+ * same layers at both levels.  The outside-sphere half, the resampling (on the scene weights), the merge, the flags and the scratch
+ * lanes are neo_tp_render's.  With K == 0 (or every scale and tint 1) and L == 0 the twelve outputs are bitwise neo_tp_render's.
+ * samples0 / samples1 (may be NULL, and any pointer in them): the level's sample rows fg_t, bg_s (R,N_level), its scene weights fg_w
+ * (R,N_level) and - with layers - visibility (L,R). */
+typedef struct { float* fg_t; float* fg_w; float* bg_s; float* visibility; } neo_tp_edit_samples;
+int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
+                         const float* far_inst, int K, const float* density_scale, const float* tint, const neo_tp_layers* layers,
+                         int L, int R, int chunk, const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse,
+                         int n_fine, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
+                         const neo_tp_edit_samples* samples0, const neo_tp_edit_samples* samples1, void* stream);
+
 /* ---- scene encoder: pillar stage -------------------------------------------------------- */
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).
  * weights/biases [host arrays of 9 device pointers], order: depth_fc.common_branch.0 (512x518), depth_fc.common_branch.2,

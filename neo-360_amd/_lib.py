@@ -42,6 +42,14 @@ class TpInstanceOut(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("rgb", "acc", "depth", "comp_rgb", "comp_acc", "comp_depth", "instance_id")]
 
 
+class TpLayers(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("key", "rgb", "acc", "depth")]
+
+
+class TpEditSamples(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("fg_t", "fg_w", "bg_s", "visibility")]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares
 SIGNATURES = {
     "neo_abi_version": (_i, []),
@@ -88,6 +96,11 @@ SIGNATURES = {
                                    ctypes.POINTER(TpObjectOut), ctypes.POINTER(TpObjectOut), _vp, _vp]),
     "neo_tp_render_instances": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i, _i,
                                      ctypes.POINTER(TpInstanceOut), ctypes.POINTER(TpInstanceOut), _vp, _vp]),
+    "neo_tp_edit_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, c_float_p, c_float_p, _i, _i, _vp]),
+    "neo_composite_layers": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.POINTER(TpLayers), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "neo_tp_render_edited": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, c_float_p, c_float_p, ctypes.POINTER(TpLayers), _i, _i, _i,
+                                  c_float_p, _i, _f, _f, _f, _i, _i, ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut),
+                                  ctypes.POINTER(TpEditSamples), ctypes.POINTER(TpEditSamples), _vp]),
     "neo_enc_upload": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_enc_floorplans": (_i, [_vp, _vp, _i, _i, _i, _f, _f, c_float_p, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "neo_enc_train_tape_floats": (ctypes.c_long, [_i, _i, _i, _i]),

@@ -405,4 +405,20 @@ void launch_inst_composite(const float* near_inst, const float* far_inst, int K,
                            const float* prem_depth, int white_bkgd, float* rgb, float* acc, float* depth, int* instance_id,
                            hipStream_t s);
 
+// edit.hip - edited render of neo_tp_render_edited (include/neo360_hip.h: EDIT RULE, LAYER RECURRENCE)
+constexpr int TP_MAX_EDITS = 32;
+struct TpEditTable {                 // per instance: density scale and rgb tint; travels by value as a kernel argument
+    float scale[TP_MAX_EDITS];
+    float tint[TP_MAX_EDITS][3];
+};
+// in place on (R,N,4) rows: the samples inside the closed interval of a hit pair (i, ray) are multiplied by instance i's scale /
+// tint, i ascending; a sample inside no interval is not written.  K == 0 launches nothing.
+void launch_tp_edit(float* rgbsigma, const float* t, const float* near_inst, const float* far_inst, int K, int R, int N,
+                    const TpEditTable& tab, hipStream_t s);
+// launch_composite mode 1 (t_row_stride N, no white background) with L <= 32 layers per ray: l_key, l_acc, l_depth (L,R), l_rgb
+// (L,R,3); visibility (L,R) and every other output may be null; weights are the scene's own (k_composite's)
+void launch_composite_layers(const float* rgbsigma, const float* t, const float* rays_d, const float* t_far, int R, int N,
+                             const float* l_key, const float* l_rgb, const float* l_acc, const float* l_depth, int L, float* rgb,
+                             float* acc, float* depth, float* weights, float* lambda, float* visibility, hipStream_t s);
+
 }  // namespace neo

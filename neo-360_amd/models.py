@@ -950,6 +950,82 @@ class NeRF_TP(_HipModule):
         return dict(instances=[(t["rgb"], t["acc"], t["depth"]) for t in levels] if per_instance else None,
                     composite=[(t["comp_rgb"], t["comp_acc"], t["comp_depth"], t["instance_id"]) for t in levels])
 
+    @torch.no_grad()
+    def render_edited(self, rays, near_inst, far_inst, density_scale=None, tint=None, layers=None, chunk=None, return_samples=False):
+        """The whole scene - both regions, both levels - with instances removed, faded, tinted or re-inserted somewhere else
+        (neo_tp_render_edited).  Deterministic (randomized=False); the unit-sphere assertion is that of `forward`; `chunk` as in
+        `forward`.  Reads neither `cull_background` nor `compute_extras` (nor `ray_grid`).
+
+        near_inst / far_inst: (K,B) or (K,B,1), any float dtype, on the rays' device, 0 <= K <= 32 - the intervals
+        `render_instances` takes, values of the ray parameter t of o + t rays_d.  Pair (i, ray) is a hit by the rule of
+        `render_objects` (lo = max(near, 1e-4), hi = far, both finite, hi > lo; a NaN bound is a miss); an inside-sphere sample is
+        inside the pair iff lo <= t <= hi.  At both levels, after the evaluator and before the composite, for i ascending and every
+        sample inside: sigma *= density_scale[i], rgb *= tint[i] (fp32; overlapping intervals multiply; scale 0 removes the instance
+        and what lies behind it is re-weighted by the composite).  density_scale (K values) and tint (K x 3) are HOST sequences or CPU
+        tensors, validated on the host - right length, finite, >= 0, else ValueError - and passed as kernel arguments: the call
+        synchronises nothing.  None = ones; with K = 0, or every value 1, and no layers the result is bitwise
+        `forward(rays, False, False, near, far, out_depth=True, chunk=chunk)`.
+
+        layers: None or dict(key (L,B), rgb (L,B,3), acc (L,B), depth (L,B)) on the rays' device, L <= 32 - e.g.
+        `render.instance_layers`: slabs of opacity acc, premultiplied colour rgb and premultiplied depth at the ray parameter key,
+        spliced into the inside-sphere composite of BOTH levels in ascending key (`ops.composite_layers`; a layer with a non-finite
+        key or acc <= 0 is ignored).  The fine level's sample positions do not depend on them.
+
+        Returns the two level tuples of `forward(..., out_depth=True)`: [(comp_rgb, fg_rgb, bg_rgb, fg_acc, bg_lambda, comp_depth)];
+        with layers each tuple gains `visibility` (L,B), the weight each layer's opacity enters the ray with; with return_samples a
+        third element holds per level (fg_t, fg_w, bg_s), fg_w being the SCENE weight (exactly 0 inside a removed interval)."""
+        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
+        B = raw[0].shape[0]
+        K = ops._edit_bounds(near_inst, far_inst, B, raw[0].device, "render_edited")
+        scale, tints = ops.edit_table(K, density_scale, tint)
+        L = ops._layer_rows(layers, B, raw[0].device, "render_edited")
+        rays_o = f32(raw[0], "rays_o")
+        rays_d = f32(raw[1], "rays_d")
+        viewdirs = f32(raw[2], "viewdirs")
+        dev = rays_o.device
+        near_c, far_c = ops._edit_rows(near_inst, far_inst, K, B)
+        layer_rows, layer_struct = ops._layer_struct(layers, L)
+        ctx = self._context(dev)
+        self._ensure_scene(rays, dev)
+        if self._scene_ctx is not ctx:
+            raise _lib.NeoError("scene features were uploaded on a different device")
+        self._sync_weights(ctx)
+        self._before_call(ctx)
+        host_poses, NV, focal, cx, cy = self._camera_args(rays)
+        n0 = self.num_coarse_samples + 1
+        n1 = n0 + self.num_fine_samples
+        levels = []
+
+        def launch():
+            structs, sample_structs = [], []
+            for n in (n0, n1):
+                t = dict(rgb=torch.empty(B, 3, device=dev), fg_rgb=torch.empty(B, 3, device=dev),
+                         bg_rgb=torch.empty(B, 3, device=dev), fg_acc=torch.empty(B, device=dev),
+                         bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
+                structs.append(_lib.TpLevelOut(*(t[k].data_ptr() for k in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth"))))
+                if L:
+                    t["visibility"] = torch.empty(L, B, device=dev)
+                if return_samples:
+                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev))
+                levels.append(t)
+                sample_structs.append(_lib.TpEditSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpEditSamples._fields_))
+                                      if (L or return_samples) else None)
+            _lib.check(ctx.lib.neo_tp_render_edited(
+                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(near_c), ptr(far_c), K, scale, tints,
+                ctypes.byref(layer_struct) if layer_struct is not None else None, L, B, int(chunk or max(B, 1)), host_poses, NV, focal,
+                cx, cy, self.num_coarse_samples, self.num_fine_samples, ctypes.byref(structs[0]), ctypes.byref(structs[1]),
+                *(ctypes.byref(x) if x is not None else None for x in sample_structs), ctx.stream()))
+            self._after_call(ctx)
+            return [v for t in levels for v in t.values()]
+        raw_layers = tuple(layers[k] for k in ("key", "rgb", "acc", "depth")) if L else ()
+        self._launch_overlapped(ctx, dev, raw + (near_inst, far_inst) + raw_layers,
+                                (rays_o, rays_d, viewdirs, near_c, far_c) + tuple(layer_rows), launch)
+        out = [(t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"]) + ((t["visibility"],) if L else ())
+               for t in levels]
+        if return_samples:
+            out.append([(t["fg_t"], t["fg_w"], t["bg_s"]) for t in levels])
+        return out
+
 
 class PixelNeRFMLP(nn.Module):
     """Parameter container with the layout of vanilla_nerf/model_pixel.py:35-94: pts_linears.0..3 (128 wide;

@@ -300,3 +300,134 @@ def tp_extras(fg_t, fg_w, far, rays_o, rays_d, bg_s=None, bg_w=None, bg_lambda=N
     _lib.check(ctx.lib.neo_tp_extras(ctx.handle, ptr(fg_t), ptr(fg_w), ptr(far), ptr(bg_s), ptr(bg_w), ptr(bg_lambda), ptr(rays_o),
                                      ptr(rays_d), R, N, ptr(tab), n_u, ptr(opacity), ptr(disparity), ptr(pct), ctx.stream()))
     return dict(opacity=opacity, disparity=disparity, distance_percentiles=pct)
+
+
+MAX_EDIT_INSTANCES = 32
+
+
+def _edit_bounds(near_inst, far_inst, B, dev, who):
+    """Validates near_inst / far_inst - (K,B) or (K,B,1) floating-point tensors on `dev`, K <= 32 - and returns K; nothing is
+    converted yet (_edit_rows), so that every host-side ValueError comes before the first device access."""
+    rows = []
+    for key, t in (("near_inst", near_inst), ("far_inst", far_inst)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise ValueError("%s: %s must be a floating-point tensor, got %r" % (who, key, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
+        if not (t.dim() in (2, 3) and t.shape[1] == B and (t.dim() == 2 or t.shape[2] == 1)):
+            raise ValueError("%s: %s must have shape (K, %d) or (K, %d, 1): one row per instance, got %s" % (who, key, B, B, tuple(t.shape)))
+        if t.shape[0] > MAX_EDIT_INSTANCES:
+            raise ValueError("%s: %s holds %d instances, at most %d are supported" % (who, key, t.shape[0], MAX_EDIT_INSTANCES))
+        if t.device != dev:
+            raise ValueError("%s: %s must be on the rays' device (%s), got %s" % (who, key, dev, t.device))
+        rows.append(t)
+    if rows[0].shape[0] != rows[1].shape[0]:
+        raise ValueError("%s: near_inst holds %d instances, far_inst %d" % (who, rows[0].shape[0], rows[1].shape[0]))
+    return rows[0].shape[0]
+
+
+def _edit_rows(near_inst, far_inst, K, B):
+    return f32(near_inst, "near_inst").reshape(K, B), f32(far_inst, "far_inst").reshape(K, B)
+
+
+def edit_table(K, density_scale=None, tint=None):
+    """Host side of an edit: K density scales and K x 3 tints (sequences or CPU tensors; None = all ones) -> two ctypes float arrays
+    (or None), validated here - right length, finite, >= 0, else ValueError - and never read from a device."""
+    import math
+    out = []
+    for name, v, width in (("density_scale", density_scale, 1), ("tint", tint, 3)):
+        if v is None:
+            out.append(None)
+            continue
+        if isinstance(v, torch.Tensor):
+            if v.device.type != "cpu":
+                raise ValueError("%s must be a host sequence or a CPU tensor (it travels as a kernel argument), got a tensor on %s" % (name, v.device))
+            v = v.detach().tolist()
+        rows = [list(r) if width == 3 else [r] for r in v]
+        if len(rows) != K or any(len(r) != width for r in rows):
+            raise ValueError("%s must hold %s, got %d rows" % (name, "%d values" % K if width == 1 else "%d x 3 values" % K, len(rows)))
+        flat = [float(x) for r in rows for x in r]
+        if any(not math.isfinite(x) or x < 0.0 for x in flat):
+            raise ValueError("%s must be finite and >= 0, got %r" % (name, v))
+        out.append((ctypes.c_float * max(len(flat), 1))(*flat))
+    return out[0], out[1]
+
+
+@torch.no_grad()
+def edit_rgbsigma(rgbsigma, t, near_inst, far_inst, density_scale=None, tint=None, ctx=None):
+    """The edit of `NeRF_TP.render_edited` on caller rows (neo_tp_edit_rows): an edited COPY of rgbsigma (R,N,4) at the sample rows
+    t (R,N).  near_inst / far_inst (K,R) or (K,R,1), K <= 32, ray parameters as `render_objects` reads them; pair (i, ray) is a hit
+    by its rule (lo = max(near, 1e-4), hi = far, both finite, hi > lo; a NaN bound is a miss) and sample j is inside iff
+    lo <= t_j <= hi.  For i ascending, if inside: sigma *= density_scale[i], rgb *= tint[i] (fp32; overlapping intervals multiply).
+    density_scale (K) / tint (K,3): host sequences or CPU tensors, finite and >= 0 (ValueError otherwise), None = ones."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("t must be a (R, N) tensor")
+    R, N = t.shape
+    if not isinstance(rgbsigma, torch.Tensor) or tuple(rgbsigma.shape) != (R, N, 4) or rgbsigma.device != t.device:
+        raise ValueError("rgbsigma must be a (%d, %d, 4) tensor on the device of t" % (R, N))
+    K = _edit_bounds(near_inst, far_inst, R, t.device, "edit_rgbsigma")
+    scale, tints = edit_table(K, density_scale, tint)
+    near_c, far_c = _edit_rows(near_inst, far_inst, K, R)
+    out = f32(rgbsigma, "rgbsigma").clone()
+    t = f32(t, "t")
+    ctx = _ctx(t, ctx)
+    if N:
+        _lib.check(ctx.lib.neo_tp_edit_rows(ctx.handle, ptr(out), ptr(t), ptr(near_c), ptr(far_c), K, scale, tints, R, N, ctx.stream()))
+    return out
+
+
+def _layer_rows(layers, B, dev, who):
+    """Validates layers = None or dict(key (L,B), rgb (L,B,3), acc (L,B), depth (L,B)) on `dev`, L <= 32, and returns L; nothing is
+    converted yet (_layer_struct)."""
+    if layers is None:
+        return 0
+    if not hasattr(layers, "keys") or any(k not in layers for k in ("key", "rgb", "acc", "depth")):
+        raise ValueError("%s: layers must be a dict with key (L,B), rgb (L,B,3), acc (L,B) and depth (L,B)" % who)
+    L = layers["key"].shape[0] if isinstance(layers["key"], torch.Tensor) and layers["key"].dim() == 2 else -1
+    for k in ("key", "rgb", "acc", "depth"):
+        v = layers[k]
+        want = (L, B, 3) if k == "rgb" else (L, B)
+        if not isinstance(v, torch.Tensor) or not v.is_floating_point():
+            raise ValueError("%s: layers[%r] must be a floating-point tensor" % (who, k))
+        if L < 0 or tuple(v.shape) != want:
+            raise ValueError("%s: layers[%r] must have shape %s, got %s" % (who, k, "(L, %d%s)" % (B, ", 3" if k == "rgb" else ""), tuple(v.shape)))
+        if v.device != dev:
+            raise ValueError("%s: layers[%r] must be on the rays' device (%s), got %s" % (who, k, dev, v.device))
+    if L > MAX_EDIT_INSTANCES:
+        raise ValueError("%s: %d layers, at most %d are supported" % (who, L, MAX_EDIT_INSTANCES))
+    return L
+
+
+def _layer_struct(layers, L):
+    """The fp32 rows of validated layers and the struct the library reads them through: ((), None) when L == 0."""
+    if not L:
+        return (), None
+    rows = tuple(f32(layers[k], k) for k in ("key", "rgb", "acc", "depth"))
+    return rows, _lib.TpLayers(*(r.data_ptr() for r in rows))
+
+
+@torch.no_grad()
+def composite_layers(rgbsigma, t, rays_d, t_far, layers, ctx=None):
+    """`composite(1, ...)` with up to 32 per-ray layers spliced into the ray (neo_composite_layers; the LAYER RECURRENCE of
+    include/neo360_hip.h).  layers: dict(key (L,R) ray parameters, rgb (L,R,3) premultiplied colours, acc (L,R) opacities, depth
+    (L,R) premultiplied depths) or None.  A layer is valid iff its key is finite and its acc > 0; valid layers act in ascending key
+    (ties: lower index) as slabs with keep = max(1 - acc, 0) placed before the first sample at or beyond their key.
+    Returns dict(rgb, acc, depth, weights, bg_lambda, visibility (L,R)); `weights` are the scene's own (those of `composite`), and
+    with no valid layer everything is bitwise `composite(1, ...)`."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("t must be a (R, N) tensor")
+    R, N = t.shape
+    dev = t.device
+    L = _layer_rows(layers, R, dev, "composite_layers")
+    rgbsigma, t = f32(rgbsigma, "rgbsigma"), f32(t, "t")
+    rays_d, t_far = f32(rays_d, "rays_d"), f32(t_far, "t_far")
+    ctx = _ctx(t, ctx)
+    rows, struct = _layer_struct(layers, L)
+    rgb = torch.empty(R, 3, device=dev)
+    acc = torch.empty(R, device=dev)
+    depth = torch.empty(R, device=dev)
+    w = torch.empty(R, N, device=dev)
+    lam = torch.empty(R, 1, device=dev)
+    vis = torch.empty(L, R, device=dev)
+    _lib.check(ctx.lib.neo_composite_layers(ctx.handle, ptr(rgbsigma), ptr(t), ptr(rays_d), ptr(t_far), R, N,
+                                            ctypes.byref(struct) if struct is not None else None, L, ptr(rgb), ptr(acc), ptr(depth),
+                                            ptr(w), ptr(lam), ptr(vis) if L else None, ctx.stream()))
+    return dict(rgb=rgb, acc=acc, depth=depth, weights=w, bg_lambda=lam, visibility=vis)

@@ -190,6 +190,115 @@ def render_instance_rays(model, batch, RTs=None, chunk=1024, white_bkgd=True, ch
     return _render_guarded(model, batch, once, check, on_range)
 
 
+def _rigid(M, index):
+    """A 4x4 rigid world transform as fp64 (rotation, translation); ValueError when it is not one."""
+    m = torch.as_tensor(M, dtype=torch.float64, device="cpu")
+    if tuple(m.shape) != (4, 4) or not bool(torch.isfinite(m).all()):
+        raise ValueError("moves[%r] must be a finite 4x4 matrix" % (index,))
+    rot, tran = m[:3, :3], m[:3, 3]
+    rigid = (float((rot @ rot.T - torch.eye(3, dtype=torch.float64)).abs().max()) <= 1e-6 and abs(float(torch.linalg.det(rot)) - 1.0) <= 1e-6
+             and float((m[3] - torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)).abs().max()) <= 1e-12)
+    if not rigid:
+        raise ValueError("moves[%r] is not a rigid transform (orthonormal rotation with det +1, last row 0 0 0 1)" % (index,))
+    return rot, tran
+
+
+def _check_moves(moves, K):
+    out = {}
+    for i, M in (moves or {}).items():
+        if not isinstance(i, int) or isinstance(i, bool) or not 0 <= i < K:
+            raise ValueError("moves: %r is not an instance index in [0, %d)" % (i, K))
+        out[i] = _rigid(M, i)
+    return dict(sorted(out.items()))
+
+
+@torch.no_grad()
+def instance_layers(model, batch, RTs, moves, chunk=1024):
+    """Instances of a NeRF_TP scene rendered SOMEWHERE ELSE, as the layers `NeRF_TP.render_edited` takes.  moves: {instance index
+    into RTs: 4x4 rigid world transform M, new = M * old} (ValueError for a non-rigid M).  Seeing the moved instance along a ray is
+    seeing the instance where it stands along the ray moved back: per moved instance o' = Rm^T (o - tm), d' = Rm^T d, viewdirs' =
+    Rm^T viewdirs, in fp64 and rounded to fp32; its box interval from `ops.sample_rays_in_bbox_list` on those rays (|Rm^T d| = |d|:
+    the ray parameter is unchanged); the fine level of `render_objects(..., white_bkgd=False)` on them is the layer, key = lo where
+    the pair is hit, else +inf.  The moved instance keeps the lighting and the quirk-Q1 direction row of its transformed ray.
+    Returns dict(key (L,R), rgb (L,R,3), acc (L,R), depth (L,R), index = the moved instance indices, ascending)."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("instance_layers renders NeRF_TP modules, got %r" % type(model))
+    from . import ops
+    K = len(RTs["R"])
+    moves = _check_moves(moves, K)
+    dev = batch["rays_o"].device
+    R = batch["rays_o"].shape[0]
+    out = dict(key=[], rgb=[], acc=[], depth=[])
+    for i, (rot, tran) in moves.items():
+        rot_d, tran_d = rot.to(dev), tran.to(dev)
+        moved = dict(batch)
+        moved["rays_o"] = ((batch["rays_o"].double() - tran_d) @ rot_d).float()        # row vectors: x Rm = (Rm^T x^T)^T
+        moved["rays_d"] = (batch["rays_d"].double() @ rot_d).float()
+        moved["viewdirs"] = (batch["viewdirs"].double() @ rot_d).float()
+        one = dict(R=[RTs["R"][i]], T=[RTs["T"][i]], s=[RTs["s"][i]])
+        near, far, _ = ops.sample_rays_in_bbox_list(one, moved["rays_o"], moved["viewdirs"])
+        near, far = near.reshape(R), far.reshape(R)
+        rgb, acc, depth = model.render_objects(moved, near_obj=near, far_obj=far, white_bkgd=False, chunk=chunk)[1]
+        lo = torch.clamp(near, min=1e-4)
+        hit = torch.isfinite(near) & torch.isfinite(far) & (far > lo)
+        out["key"].append(torch.where(hit, lo, torch.full_like(lo, float("inf"))))
+        out["rgb"].append(rgb)
+        out["acc"].append(acc)
+        out["depth"].append(depth)
+    layers = {k: (torch.stack(v) if v else torch.empty((0, R, 3) if k == "rgb" else (0, R), device=dev)) for k, v in out.items()}
+    layers["index"] = list(moves)
+    return layers
+
+
+@torch.no_grad()
+def render_edited_rays(model, batch, RTs=None, density_scale=None, tint=None, moves=None, chunk=1024, check=True,
+                       on_range="retry_f32"):
+    """Edited frame of a NeRF_TP module: the fine level of `model.render_edited` on every ray of `batch` in one library call, with
+    the reference chunk size passed down.  The per-instance intervals are batch["near_inst"] / batch["far_inst"] when present, else
+    they are computed from `RTs` with ops.sample_rays_in_bbox_list.  density_scale (K) / tint (K x 3): host sequences, as
+    `render_edited` takes them.  moves ({instance index: 4x4 rigid M}, needs RTs): those instances are rendered where M puts them,
+    as layers (`instance_layers`), and get density scale 0 in the scene pass; a scale or tint other than 1 given for a moved
+    instance raises ValueError.  Everything runs inside one guarded render (check / on_range: the flag read, range-guard retry and
+    latch of render_rays_test).  Returns dict(rgb (R,3), depth (R,), acc (R,), bg_lambda (R,1)[, visibility (L,R)]) of the fine
+    level plus `target` / `instance_mask` passed through; with the defaults rgb / depth are bitwise render_rays_test's."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("render_edited_rays renders NeRF_TP modules, got %r" % type(model))
+    if on_range not in ("retry_f32", "raise"):
+        raise ValueError("on_range must be 'retry_f32' or 'raise', got %r" % (on_range,))
+    from . import ops
+    if moves and RTs is None:
+        raise ValueError("render_edited_rays needs RTs to render moved instances")
+    given = "near_inst" in batch and "far_inst" in batch
+    K = batch["near_inst"].shape[0] if given else len(RTs["R"]) if RTs is not None else 0
+    if given and RTs is not None and len(RTs["R"]) != K:
+        raise ValueError("RTs holds %d boxes, the batch's intervals %d instances" % (len(RTs["R"]), K))
+    moved = _check_moves(moves, K)
+    scale, tints = ops.edit_table(K, density_scale, tint)      # validation only: render_edited builds its own tables
+    scale = [1.0] * K if scale is None else list(scale)[:K]
+    tints = [[1.0, 1.0, 1.0] for _ in range(K)] if tints is None else [list(tints)[3 * i:3 * i + 3] for i in range(K)]
+    for i in moved:
+        if scale[i] != 1.0 or tints[i] != [1.0, 1.0, 1.0]:
+            raise ValueError("instance %d is moved: it takes no density_scale or tint of its own" % i)
+        scale[i] = 0.0
+    if given:
+        near, far = batch["near_inst"], batch["far_inst"]
+    elif RTs is not None:
+        near, far, _ = ops.sample_rays_in_bbox_list(RTs, batch["rays_o"], batch["viewdirs"])
+    else:
+        near = far = torch.zeros(0, batch["rays_o"].shape[0], device=batch["rays_o"].device)
+
+    def once():
+        layers = instance_layers(model, batch, RTs, moves, chunk) if moved else None
+        if layers is not None:
+            layers = {k: layers[k] for k in ("key", "rgb", "acc", "depth")}
+        res = model.render_edited(batch, near, far, density_scale=scale, tint=tints, layers=layers, chunk=chunk)[1]
+        out = dict(rgb=res[0], depth=res[5], acc=res[3], bg_lambda=res[4])
+        if layers is not None:
+            out["visibility"] = res[6]
+        return out
+    return _render_guarded(model, batch, once, check, on_range)
+
+
 @torch.no_grad()
 def render_frame_sharded(model, batch, world, rank, chunk=1024, white_bkgd=False, near=0.2, far=3.0, group=None,
                          gather=True, train_frac=1.0, n_rays=None, out=None, reuse=False, check=True, always_gather=False,
