@@ -429,6 +429,40 @@ int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d,
                          int n_fine, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
                          const neo_tp_edit_samples* samples0, const neo_tp_edit_samples* samples1, void* stream);
 
+/* DECOMPOSED render: the frame split into per-instance layers that add up to it, a "rest" layer and an occlusion-aware id map.
+ * DECOMPOSITION RULE (neo_tp_decompose_rows).  Per ray: the (N,4) rgb/sigma row c_j, the positions t_j, the scene weights w_j
+ * exactly as neo_composite mode 1 writes them to `weights`, near_inst / far_inst (K,R) [device], 0 <= K <= 32, and optionally
+ * bg_lambda (R).  Pair (i, ray) is a hit by the HIT RULE above (lo = max(near, 1e-4), hi = far, both finite, hi > lo; the negation
+ * of the failing comparisons, so a NaN bound is a miss); sample j is INSIDE pair i iff lo <= t_j && t_j <= hi (closed, as in the
+ * EDIT RULE).  owner(j) = the smallest hit i that j is inside of, else slot K, the REST: every sample has exactly one owner, and a
+ * sample inside two boxes counts once.  For each slot s = 0 .. K: P_s = sum over owner(j) = s of w_j c_j (3 channels), a_s = sum
+ * w_j, d_s = sum w_j t_j - plain fp32 in neo_composite's own order, slot by slot: lane j mod 64 of a 64-lane wave adds its samples
+ * (the products w_j c_j, w_j t_j rounded first) in ascending j over the 64-sample rounds, starting from 0, then the butterfly of
+ * the wave sum (offsets 32, 16, .. 1).  The order is part of the contract: a slot that owns every sample of a ray is bitwise
+ * neo_composite's rgb / acc / depth on the same rows (adding 0.0f for another owner's sample changes nothing), a slot that owns
+ * nothing is exactly 0.  No atomics; bitwise repeatable.
+ * ID MAP id (R) int32: rest_total = a_K + bg_lambda (one fp32 add; a_K alone without bg_lambda); best = the largest a_i over i < K,
+ * ties to the lower index; id = its index iff a_best > 0 && a_best >= rest_total, else -1.  A NaN mass never wins, and a NaN
+ * rest_total gives -1.  The outside-sphere half of a ray always belongs to the rest: that is what bg_lambda stands for.
+ * out: rgb (K+1,R,3), acc (K+1,R), depth (K+1,R), id (R); any pointer may be NULL.  1 <= N <= 1024.  K == 0 is a valid call (the
+ * rest is then the whole ray), and so is R == 0.  Touches no context-owned memory. */
+typedef struct { float* rgb; float* acc; float* depth; int* id; } neo_tp_decomposed_out;
+int neo_tp_decompose_rows(neo_ctx* ctx, const float* rgbsigma, const float* t, const float* weights, const float* near_inst,
+                          const float* far_inst, int K, int R, int N, const float* bg_lambda /* may be NULL */,
+                          const neo_tp_decomposed_out* out, void* stream);
+
+/* neo_tp_render (out_depth=True semantics, the coarse level always evaluated in full: the launch list of neo_tp_render_edited
+ * without edits and layers, so the twelve outputs are bitwise neo_tp_render's) with the DECOMPOSITION RULE applied after the
+ * inside-sphere composite of every level whose decomposed0 / decomposed1 is not NULL, on that level's rows, positions, scene
+ * weights and bg_lambda.  The outside-sphere half, the resampling, the merge, the flags, the scratch lanes, the ray-grid hint, the
+ * range guard and the sample-count limits are neo_tp_render's.  samples0 / samples1 (may be NULL, and any pointer in them): the
+ * level's fg_t, bg_s and fg_w (R,N_level); `visibility` is not written. */
+int neo_tp_render_decomposed(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
+                             const float* far_inst, int K, int R, int chunk, const float* src_poses, int NV, float focal, float cx,
+                             float cy, int n_coarse, int n_fine, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
+                             const neo_tp_decomposed_out* decomposed0, const neo_tp_decomposed_out* decomposed1,
+                             const neo_tp_edit_samples* samples0, const neo_tp_edit_samples* samples1, void* stream);
+
 /* ---- scene encoder: pillar stage -------------------------------------------------------- */
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).
  * weights/biases [host arrays of 9 device pointers], order: depth_fc.common_branch.0 (512x518), depth_fc.common_branch.2,

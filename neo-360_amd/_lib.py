@@ -50,6 +50,10 @@ class TpEditSamples(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("fg_t", "fg_w", "bg_s", "visibility")]
 
 
+class TpDecomposedOut(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("rgb", "acc", "depth", "id")]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares
 SIGNATURES = {
     "neo_abi_version": (_i, []),
@@ -101,6 +105,11 @@ SIGNATURES = {
     "neo_tp_render_edited": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, c_float_p, c_float_p, ctypes.POINTER(TpLayers), _i, _i, _i,
                                   c_float_p, _i, _f, _f, _f, _i, _i, ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut),
                                   ctypes.POINTER(TpEditSamples), ctypes.POINTER(TpEditSamples), _vp]),
+    "neo_tp_decompose_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, ctypes.POINTER(TpDecomposedOut), _vp]),
+    "neo_tp_render_decomposed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i,
+                                      ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpDecomposedOut),
+                                      ctypes.POINTER(TpDecomposedOut), ctypes.POINTER(TpEditSamples), ctypes.POINTER(TpEditSamples),
+                                      _vp]),
     "neo_enc_upload": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_enc_floorplans": (_i, [_vp, _vp, _i, _i, _i, _f, _f, c_float_p, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "neo_enc_train_tape_floats": (ctypes.c_long, [_i, _i, _i, _i]),

@@ -275,25 +275,24 @@ int neo_composite_layers(neo_ctx* ctx, const float* rgbsigma, const float* t, co
     return check_launch();
 }
 
-// neo_tp_render's launch list with a full level 0, k_tp_edit on the inside-sphere rows of each level before their composite, and
-// k_composite_layers as that composite when layers are given.  Everything else - background half, resampling, merge, flags, lanes -
-// is neo_tp_render_extras' (api_tp.hip).
-int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
-                         const float* far_inst, int K, const float* density_scale, const float* tint, const neo_tp_layers* layers,
-                         int L, int R, int chunk, const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse,
-                         int n_fine, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
-                         const neo_tp_edit_samples* samples0, const neo_tp_edit_samples* samples1, void* stream) {
-    ENTER(ctx);
+}  // extern "C"
+
+// neo_tp_render's launch list with a full level 0, k_tp_edit on the inside-sphere rows of each level before their composite,
+// k_composite_layers as that composite when layers are given, and k_tp_decompose (decompose.hip) behind it for every level that has
+// a decomposed struct.  Everything else - background half, resampling, merge, flags, lanes - is neo_tp_render_extras' (api_tp.hip).
+// Shared by neo_tp_render_edited (below) and neo_tp_render_decomposed (decompose.hip: K_edit = 0, L = 0); the caller has entered
+// the context and checked its own counts.
+int neo_tp_render_rows(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
+                       const float* far_inst, int K_edit, const neo::TpEditTable& tab, const neo_tp_layers* layers, int L, int K_dec,
+                       const neo_tp_decomposed_out* decomposed0, const neo_tp_decomposed_out* decomposed1, int R, int chunk,
+                       const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                       const neo_tp_level_out* level0, const neo_tp_level_out* level1, const neo_tp_edit_samples* samples0,
+                       const neo_tp_edit_samples* samples1, void* stream) {
     REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
-    REQUIRE(K >= 0 && K <= neo::TP_MAX_EDITS, "0..32 instances supported");
-    REQUIRE(L >= 0 && L <= neo::TP_MAX_EDITS, "0..32 layers supported");
-    REQUIRE(static_cast<long>(K > L ? K : L) * R * 3 <= 2147483647L, "too many (instance, ray) pairs for 32-bit indices");
     REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
-    neo::TpEditTable tab;
-    if (int rc = fill_edit_table(tab, K, density_scale, tint)) return rc;
     if (R == 0) return NEO_OK;
     REQUIRE(rays_o && rays_d && viewdirs && src_poses, "null pointer");
-    REQUIRE(K == 0 || (near_inst && far_inst), "null interval pointer");
+    REQUIRE((K_edit == 0 && K_dec == 0) || (near_inst && far_inst), "null interval pointer");
     REQUIRE(L == 0 || (layers && layers->key && layers->rgb && layers->acc && layers->depth), "null layer pointer");
     if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
     REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
@@ -313,10 +312,11 @@ int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
 
     // workspaces: this lane's set, laid out as in neo_tp_render; W[10] the level-1 inside-sphere weights when they are asked for
+    // or the level is decomposed
     ORDERED_LANE(ctx, s);
     auto* W = ctx->ws;
     const size_t r = static_cast<size_t>(R);
-    const bool want_w1 = samples1 && samples1->fg_w;
+    const bool want_w1 = decomposed1 || (samples1 && samples1->fg_w);
     if (W[0].reserve(r * 4) || W[1].reserve(r * N0 * 4) || W[2].reserve(r * N0 * 4) || W[3].reserve(r * N1 * 16) ||
         W[4].reserve(r * N1 * 16) || W[5].reserve(r * N0 * 4) || W[6].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) ||
         W[8].reserve(r * N1 * 4) || W[9].reserve(r * 16 * 4))
@@ -349,6 +349,7 @@ int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d,
         const int N = level == 0 ? N0 : N1;
         const neo_tp_level_out* lo = level == 0 ? level0 : level1;
         const neo_tp_edit_samples* so = level == 0 ? samples0 : samples1;
+        const neo_tp_decomposed_out* dc = level == 0 ? decomposed0 : decomposed1;
         if (int rc = neo_tp_eval_region(ctx, level, sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s)) return rc;
         if (int rc = neo_tp_eval_region(ctx, 2 + level, sc, views, rays_o, rays_d, viewdirs, bg_s, far, R, N, chunk, bg_out, s)) return rc;
         float* fg_rgb = (lo && lo->fg_rgb) ? lo->fg_rgb : s_fg_rgb;
@@ -356,12 +357,14 @@ int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d,
         float* fg_acc = (lo && lo->fg_acc) ? lo->fg_acc : s_fg_acc;
         float* lam = (lo && lo->bg_lambda) ? lo->bg_lambda : s_lambda;
         float* fg_w = level == 0 ? fg_w0 : fg_w1;
-        neo::launch_tp_edit(fg_out, fg_t, near_inst, far_inst, K, R, N, tab, s);
+        neo::launch_tp_edit(fg_out, fg_t, near_inst, far_inst, K_edit, R, N, tab, s);
         if (L > 0)
             neo::launch_composite_layers(fg_out, fg_t, rays_d, far, R, N, layers->key, layers->rgb, layers->acc, layers->depth, L,
                                          fg_rgb, fg_acc, s_fg_depth, fg_w, lam, so ? so->visibility : nullptr, s);
         else
             neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, fg_rgb, fg_acc, s_fg_depth, fg_w, lam, s);
+        if (dc)        // rows, positions and scene weights are still in this lane's scratch; bg_lambda is this level's own
+            neo::launch_tp_decompose(fg_out, fg_t, fg_w, near_inst, far_inst, K_dec, R, N, lam, dc->rgb, dc->acc, dc->depth, dc->id, s);
         neo::launch_composite(2, bg_out, bg_s, N, nullptr, nullptr, R, N, 0, bg_rgb, nullptr, s_bg_depth, level == 0 ? bg_w0 : nullptr,
                               nullptr, s);
         if (lo && (lo->rgb || lo->depth))
@@ -382,6 +385,23 @@ int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d,
         }
     }
     return check_launch();
+}
+
+extern "C" {
+
+int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
+                         const float* far_inst, int K, const float* density_scale, const float* tint, const neo_tp_layers* layers,
+                         int L, int R, int chunk, const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse,
+                         int n_fine, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
+                         const neo_tp_edit_samples* samples0, const neo_tp_edit_samples* samples1, void* stream) {
+    ENTER(ctx);
+    REQUIRE(K >= 0 && K <= neo::TP_MAX_EDITS, "0..32 instances supported");
+    REQUIRE(L >= 0 && L <= neo::TP_MAX_EDITS, "0..32 layers supported");
+    REQUIRE(static_cast<long>(K > L ? K : L) * R * 3 <= 2147483647L, "too many (instance, ray) pairs for 32-bit indices");
+    neo::TpEditTable tab;
+    if (int rc = fill_edit_table(tab, K, density_scale, tint)) return rc;
+    return neo_tp_render_rows(ctx, rays_o, rays_d, viewdirs, near_inst, far_inst, K, tab, layers, L, 0, nullptr, nullptr, R, chunk,
+                              src_poses, NV, focal, cx, cy, n_coarse, n_fine, level0, level1, samples0, samples1, stream);
 }
 
 }  // extern "C"

@@ -421,4 +421,10 @@ void launch_composite_layers(const float* rgbsigma, const float* t, const float*
                              const float* l_key, const float* l_rgb, const float* l_acc, const float* l_depth, int L, float* rgb,
                              float* acc, float* depth, float* weights, float* lambda, float* visibility, hipStream_t s);
 
+// decompose.hip - per-instance layers of neo_tp_render_decomposed (include/neo360_hip.h: DECOMPOSITION RULE)
+// (R,N,4) rows, positions and scene weights (k_composite mode 1's w_out) -> per owner slot 0 .. K (K = the rest): rgb (K+1,R,3),
+// acc, depth (K+1,R), and id (R); bg_lambda (R) and every output may be null.  K <= 32, N <= 1024; K == 0 launches, R == 0 does not.
+void launch_tp_decompose(const float* rgbsigma, const float* t, const float* weights, const float* near_inst, const float* far_inst,
+                         int K, int R, int N, const float* bg_lambda, float* rgb, float* acc, float* depth, int* id, hipStream_t s);
+
 }  // namespace neo

@@ -1026,6 +1026,85 @@ class NeRF_TP(_HipModule):
             out.append([(t["fg_t"], t["fg_w"], t["bg_s"]) for t in levels])
         return out
 
+    @torch.no_grad()
+    def render_decomposed(self, rays, near_inst, far_inst, chunk=None, levels=(1,), return_samples=False):
+        """The frame of `forward(rays, False, False, near, far, out_depth=True, chunk=chunk)` - bitwise - together with its split into
+        per-instance layers, a "rest" layer and an occlusion-aware id map (neo_tp_render_decomposed).  Deterministic
+        (randomized=False); the unit-sphere assertion, `chunk` and `ray_grid` are those of `forward`.  Reads neither
+        `cull_background` nor `compute_extras`.
+
+        near_inst / far_inst: (K,B) or (K,B,1), any float dtype, on the rays' device, 0 <= K <= 32 - the intervals
+        `render_instances` takes.  Pair (i, ray) is a hit by the rule of `render_objects` (lo = max(near, 1e-4), hi = far, both
+        finite, hi > lo; a NaN bound is a miss); an inside-sphere sample is inside the pair iff lo <= t <= hi and belongs to the
+        lowest-indexed hit pair it is inside of, else to slot K, the rest.  After the inside-sphere composite of each level in
+        `levels` (a subset of (0, 1)), on the rows, positions and scene weights that composite worked on: per slot s = 0 .. K the
+        sums of w c (rgb), w (acc) and w t (depth) over the slot's samples, in the composite's own fp32 order - so the slots add up
+        to fg_rgb / fg_acc / the foreground depth up to the rounding of the partial sums, a slot that owns nothing is exactly 0,
+        and with K = 0 the rest IS them, bitwise.  id = the instance with the largest acc (ties: lower index) iff that is > 0 and
+        >= acc[K] + bg_lambda, else -1: the outside-sphere half counts for the rest.  `depth` is the premultiplied sum, like
+        `forward`'s; what lies outside the sphere (bg_lambda * bg_rgb) belongs to no slot - `render.render_decomposed_rays` adds it
+        to the rest.
+
+        Returns the two level tuples of `forward(..., out_depth=True)`: [(comp_rgb, fg_rgb, bg_rgb, fg_acc, bg_lambda, comp_depth)];
+        each level in `levels` gains a seventh element dict(rgb (K+1,B,3), acc (K+1,B), depth (K+1,B), id (B,) int32); with
+        return_samples a third element holds per level (fg_t, fg_w, bg_s).  ValueError - before any device access - for intervals
+        whose shape, dtype, device or count does not fit, and for levels other than 0 and 1."""
+        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
+        B = raw[0].shape[0]
+        K = ops._edit_bounds(near_inst, far_inst, B, raw[0].device, "render_decomposed")
+        want = tuple(levels)
+        if any(isinstance(lv, bool) or lv not in (0, 1) for lv in want):
+            raise ValueError("render_decomposed: levels must be a subset of (0, 1), got %r" % (levels,))
+        rays_o = f32(raw[0], "rays_o")
+        rays_d = f32(raw[1], "rays_d")
+        viewdirs = f32(raw[2], "viewdirs")
+        dev = rays_o.device
+        near_c, far_c = ops._edit_rows(near_inst, far_inst, K, B)
+        ctx = self._context(dev)
+        self._ensure_scene(rays, dev)
+        if self._scene_ctx is not ctx:
+            raise _lib.NeoError("scene features were uploaded on a different device")
+        self._sync_weights(ctx)
+        self._before_call(ctx)
+        host_poses, NV, focal, cx, cy = self._camera_args(rays)
+        grid = getattr(self, "ray_grid", None)      # the pixel-grid hint of forward: bitwise-neutral
+        ctx.set_ray_grid(*(grid if grid and grid[0] % 8 == 0 and B >= 8 * grid[0] else (0, 0)))
+        n0 = self.num_coarse_samples + 1
+        n1 = n0 + self.num_fine_samples
+        made = []
+
+        def launch():
+            structs, dec_structs, sample_structs = [], [], []
+            for lv, n in enumerate((n0, n1)):
+                t = dict(rgb=torch.empty(B, 3, device=dev), fg_rgb=torch.empty(B, 3, device=dev),
+                         bg_rgb=torch.empty(B, 3, device=dev), fg_acc=torch.empty(B, device=dev),
+                         bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
+                structs.append(_lib.TpLevelOut(*(t[k].data_ptr() for k in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth"))))
+                dec = None
+                if lv in want:
+                    t["decomposed"], dec = ops._decomposed_out(K, B, dev)
+                dec_structs.append(dec)
+                if return_samples:
+                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev))
+                made.append(t)
+                sample_structs.append(_lib.TpEditSamples(t["fg_t"].data_ptr(), t["fg_w"].data_ptr(), t["bg_s"].data_ptr(), None)
+                                      if return_samples else None)
+            _lib.check(ctx.lib.neo_tp_render_decomposed(
+                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(near_c), ptr(far_c), K, B, int(chunk or max(B, 1)), host_poses,
+                NV, focal, cx, cy, self.num_coarse_samples, self.num_fine_samples, ctypes.byref(structs[0]), ctypes.byref(structs[1]),
+                *(ctypes.byref(x) if x is not None else None for x in dec_structs + sample_structs), ctx.stream()))
+            self._after_call(ctx)
+            return [v for t in made for x in t.values() for v in (x.values() if isinstance(x, dict) else (x,))]
+        try:
+            self._launch_overlapped(ctx, dev, raw + (near_inst, far_inst), (rays_o, rays_d, viewdirs, near_c, far_c), launch)
+        finally:
+            ctx.set_ray_grid(0)
+        out = [(t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"]) + ((t["decomposed"],) if "decomposed" in t else ())
+               for t in made]
+        if return_samples:
+            out.append([(t["fg_t"], t["fg_w"], t["bg_s"]) for t in made])
+        return out
+
 
 class PixelNeRFMLP(nn.Module):
     """Parameter container with the layout of vanilla_nerf/model_pixel.py:35-94: pts_linears.0..3 (128 wide;

@@ -374,6 +374,50 @@ def edit_rgbsigma(rgbsigma, t, near_inst, far_inst, density_scale=None, tint=Non
     return out
 
 
+def _decomposed_out(K, R, dev):
+    """The output tensors of one decomposition and the struct the library writes them through."""
+    t = dict(rgb=torch.empty(K + 1, R, 3, device=dev), acc=torch.empty(K + 1, R, device=dev), depth=torch.empty(K + 1, R, device=dev),
+             id=torch.empty(R, dtype=torch.int32, device=dev))
+    return t, _lib.TpDecomposedOut(*(t[k].data_ptr() for k in ("rgb", "acc", "depth", "id")))
+
+
+@torch.no_grad()
+def decompose_rows(rgbsigma, t, weights, near_inst, far_inst, bg_lambda=None, ctx=None):
+    """The decomposition of `NeRF_TP.render_decomposed` on caller rows (neo_tp_decompose_rows; the DECOMPOSITION RULE of
+    include/neo360_hip.h): rgbsigma (R,N,4), the sample rows t (R,N), and the scene weights (R,N) as `composite(1, ...)` returns
+    them; near_inst / far_inst (K,R) or (K,R,1), K <= 32, ray parameters as `render_objects` reads them; bg_lambda None, (R,) or
+    (R,1).  Pair (i, ray) is a hit by the rule of `render_objects` (lo = max(near, 1e-4), hi = far, both finite, hi > lo; a NaN
+    bound is a miss); sample j is inside iff lo <= t_j <= hi, and belongs to the lowest-indexed hit pair it is inside of, else to
+    slot K, the rest.  Returns dict(rgb (K+1,R,3), acc (K+1,R), depth (K+1,R), id (R,) int32): per slot the sums of w c, w and w t
+    over its samples in `composite`'s own fp32 order (a slot that owns a whole ray is bitwise `composite(1, ...)`, one that owns
+    nothing is exactly 0), and id = the instance with the largest acc (ties: lower index) iff that is > 0 and >= acc[K] + bg_lambda,
+    else -1.  1 <= N <= 1024.  Raises ValueError for shapes, dtypes or devices that do not fit and for K > 32."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or not t.is_floating_point() or not t.is_cuda:
+        raise ValueError("t must be a floating-point (R, N) device tensor")
+    R, N = t.shape
+    dev = t.device
+    if not 1 <= N <= 1024:
+        raise ValueError("1 <= N <= 1024 samples per ray, got %d" % N)
+    for name, v, want in (("rgbsigma", rgbsigma, ((R, N, 4),)), ("weights", weights, ((R, N),)), ("bg_lambda", bg_lambda, ((R,), (R, 1)))):
+        if v is None and name == "bg_lambda":
+            continue
+        if not isinstance(v, torch.Tensor) or not v.is_floating_point():
+            raise ValueError("%s must be a floating-point tensor, got %r" % (name, v.dtype if isinstance(v, torch.Tensor) else type(v).__name__))
+        if tuple(v.shape) not in want:
+            raise ValueError("%s must have shape %s, got %s" % (name, " or ".join(str(s) for s in want), tuple(v.shape)))
+        if v.device != dev:
+            raise ValueError("%s must be on the device of t (%s), got %s" % (name, dev, v.device))
+    K = _edit_bounds(near_inst, far_inst, R, dev, "decompose_rows")
+    near_c, far_c = _edit_rows(near_inst, far_inst, K, R)
+    rgbsigma, t, weights = f32(rgbsigma, "rgbsigma"), f32(t, "t"), f32(weights, "weights")
+    lam = f32(bg_lambda, "bg_lambda").reshape(R) if bg_lambda is not None else None
+    ctx = _ctx(t, ctx)
+    out, struct = _decomposed_out(K, R, dev)
+    _lib.check(ctx.lib.neo_tp_decompose_rows(ctx.handle, ptr(rgbsigma), ptr(t), ptr(weights), ptr(near_c), ptr(far_c), K, R, N, ptr(lam),
+                                             ctypes.byref(struct), ctx.stream()))
+    return out
+
+
 def _layer_rows(layers, B, dev, who):
     """Validates layers = None or dict(key (L,B), rgb (L,B,3), acc (L,B), depth (L,B)) on `dev`, L <= 32, and returns L; nothing is
     converted yet (_layer_struct)."""

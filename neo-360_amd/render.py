@@ -300,6 +300,44 @@ def render_edited_rays(model, batch, RTs=None, density_scale=None, tint=None, mo
 
 
 @torch.no_grad()
+def render_decomposed_rays(model, batch, RTs=None, chunk=1024, check=True, on_range="retry_f32"):
+    """Decomposed frame of a NeRF_TP module: the fine level of `model.render_decomposed` on every ray of `batch` in one library
+    call, with the reference chunk size passed down.  The per-instance intervals are batch["near_inst"] / batch["far_inst"] when
+    present, else they are computed from `RTs` with ops.sample_rays_in_bbox_list; with neither, K = 0.  Returns dict(rgb (R,3),
+    depth (R,), acc (R,), fg_rgb, bg_rgb (R,3)) - rgb / depth bitwise render_rays_test's - plus
+        layer_rgb (K+1,R,3)  the colour each instance contributes to the frame as it is seen IN the scene (occluded by whatever
+                             stands in front of it); slot K is everything else, bg_lambda * bg_rgb included (fg + lambda bg, the
+                             merge's own two fp32 operations: with K = 0 it is `rgb`, bitwise).  The layers add up to `rgb`;
+        layer_acc (K+1,R)    the mattes (inside-sphere weight per slot; they add up to `acc`);
+        layer_depth (K+1,R)  the slot's expected ray parameter, sum w t / sum w where layer_acc > 0, else 0;
+        instance_id (R,)     int32, the instance that holds the largest share of the ray's weight if that share is at least the
+                             share of everything else (the outside-sphere half included), else -1;
+    and `target` / `instance_mask` passed through.  Everything runs inside one guarded render (check / on_range: the flag read,
+    range-guard retry and latch of render_rays_test)."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("render_decomposed_rays renders NeRF_TP modules, got %r" % type(model))
+    if "near_inst" in batch and "far_inst" in batch:
+        near, far = batch["near_inst"], batch["far_inst"]
+    elif RTs is not None:
+        from . import ops
+        near, far, _ = ops.sample_rays_in_bbox_list(RTs, batch["rays_o"], batch["viewdirs"])
+    else:
+        near = far = torch.zeros(0, batch["rays_o"].shape[0], device=batch["rays_o"].device)
+
+    def once():
+        res = model.render_decomposed(batch, near, far, chunk=chunk)[1]
+        dec = res[6]
+        K = dec["acc"].shape[0] - 1
+        layer_rgb = dec["rgb"].clone()
+        layer_rgb[K] = dec["rgb"][K] + res[4] * res[2]
+        seen = dec["acc"] > 0
+        layer_depth = torch.where(seen, dec["depth"] / torch.where(seen, dec["acc"], torch.ones_like(dec["acc"])), torch.zeros_like(dec["acc"]))
+        return dict(rgb=res[0], depth=res[5], acc=res[3], fg_rgb=res[1], bg_rgb=res[2], layer_rgb=layer_rgb, layer_acc=dec["acc"],
+                    layer_depth=layer_depth, instance_id=dec["id"])
+    return _render_guarded(model, batch, once, check, on_range)
+
+
+@torch.no_grad()
 def render_frame_sharded(model, batch, world, rank, chunk=1024, white_bkgd=False, near=0.2, far=3.0, group=None,
                          gather=True, train_frac=1.0, n_rays=None, out=None, reuse=False, check=True, always_gather=False,
                          info=None, image_width=None):
