@@ -1,6 +1,6 @@
 // NeO-360 (NeRF_TP) entry points of the C ABI: weight / scene upload and the
 // two-level, two-region render (neo360/model.py:266-581).
-#include "ctx.h"
+#include "tp_frame.h"
 
 using namespace neo_host;
 
@@ -212,12 +212,166 @@ int neo_tp_eval_region(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo
     return tp_launch(ctx, sl, sc, views, rays_o, rays_d, viewdirs, tvals, far, R, N, chunk, out, s);
 }
 
-// one COMPACT inside-sphere evaluator launch (rows are map[] entries, *count of them) for other translation units (instances.hip)
-int neo_tp_eval_compact(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
-                        const float* rays_d, const float* viewdirs, const float* tvals, int R, int N, int chunk, float* out,
-                        const int* map, const int* count, hipStream_t s) {
-    return tp_launch(ctx, ctx->tp[slot], sc, views, rays_o, rays_d, viewdirs, tvals, nullptr, R, N, chunk, out, s, map, count);
+namespace neo_host {
+
+// The preamble of every frame entry point (tp_frame.h).  The order of the checks is part of the ABI: it decides which of two bad
+// arguments a call reports.
+int TpFrame::begin(neo_ctx* c, const TpFrameArgs& a, bool outside, bool use_grid, const Own& own) {
+    ctx = c;
+    s = static_cast<hipStream_t>(a.stream);
+    REQUIRE(a.R >= 0 && a.chunk >= 1, "bad ray count / chunk");
+    REQUIRE(!own.after_rays, own.after_rays);
+    REQUIRE(a.n_coarse >= 3 && a.n_coarse <= 256 && a.n_fine >= 1 && a.n_coarse + 1 + a.n_fine <= 1024, "unsupported sample counts");
+    REQUIRE(!own.after_counts, own.after_counts);
+    if (a.R == 0 || own.empty) {
+        empty = true;
+        return NEO_OK;
+    }
+    REQUIRE(a.rays_o && a.rays_d && a.viewdirs && a.src_poses && own.ptrs, "null pointer");
+    REQUIRE(!own.after_ptrs, own.after_ptrs);
+    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
+    REQUIRE(a.NV == ctx->scene.nv, "NV differs from the uploaded scene");
+    for (int i = 0; i < (outside ? 4 : 2); ++i)          // the compact marches do not need the outside-sphere slots 2, 3
+        if (!ctx->tp[i].ready) return fail(NEO_ERR_STATE, "NeRF_TP MLP slot %d has no weights", i);
+    if (outside)
+        REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3 && ctx->tp[2].input_ch == 4 && ctx->tp[3].input_ch == 4,
+                "slots 0,1 must be fg (input_ch 3), slots 2,3 bg (input_ch 4)");
+    else
+        REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3, "slots 0,1 must be fg (input_ch 3)");
+    const CallScene cs = call_scene(ctx->scene, a.src_poses, a.NV, a.focal, a.cx, a.cy);
+    sc = cs.sc;
+    views = cs.views;
+    if (use_grid) {       // pixel-grid hint of the frame API: the evaluators walk the rays in patches; compact launches drop it (tp_launch)
+        sc.grid_w = ctx->ray_grid_w;
+        sc.grid_first = ctx->ray_grid_first;
+    }
+    N0 = a.n_coarse + 1;
+    N1 = N0 + a.n_fine;
+    edges = ctx->get_edges(a.n_coarse, 0.0f, 1.0f, s);     // linspace(0,1,n+1)
+    u = ctx->get_quantiles(a.n_fine, s);
+    if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
+    // workspaces: this lane's set (neo_ctx_set_lane); a frame call reads shared weights / maps and writes lane scratch only
+    if (int rc = ctx->order_begin(s, true)) return rc;      // ORDERED_LANE, the scope ending with this object
+    ordered = true;
+    return NEO_OK;
 }
+
+// The dense two-level launch list: sphere test, level-0 rows, then per level the two evaluator launches, [edit,] the inside-sphere
+// composite [with layers], [decompose,] the outside-sphere composite, merge, [extras,] [sample copies,] and behind level 0 the two
+// resamples.  Without options it is neo_tp_render's list with a full level 0: the level-1 composites pass a NULL w_out and
+// W[10] / W[11] are not touched.  A level whose extras are asked for has both composites write their weights (level 0
+// does so anyway, for the resampling; level 1 into W[10] / W[11]); a level-1 decomposition or a copy of the level-1 scene weights
+// needs the inside-sphere ones alone (W[10]).
+int tp_render_dense(neo_ctx* ctx, const TpFrameArgs& a, const TpDenseOptions& o) {
+    TpFrame::Own own;
+    bool want_extras[2];
+    for (int l = 0; l < 2; ++l) {
+        const neo_tp_extras_out* ex = o.extras[l];
+        want_extras[l] = ex && (ex->opacity || ex->disparity || (ex->dist_pct && o.n_u > 0));
+        if (!own.after_counts && ex && ex->dist_pct && o.n_u > 0 && !o.u_extras) own.after_counts = "null quantile table";
+    }
+    if (!(o.n_u >= 0 && o.n_u <= 8)) own.after_counts = "bad quantile count (0 <= n_u <= 8)";
+    if (!((o.K_edit == 0 && o.K_dec == 0) || (o.near_inst && o.far_inst))) own.after_ptrs = "null interval pointer";
+    else if (!(o.L == 0 || (o.layers && o.layers->key && o.layers->rgb && o.layers->acc && o.layers->depth)))
+        own.after_ptrs = "null layer pointer";
+    TpFrame f;
+    if (int rc = f.begin(ctx, a, true, true, own)) return rc;
+    if (f.empty) return NEO_OK;
+    hipStream_t s = f.s;
+    const int R = a.R, chunk = a.chunk, N0 = f.N0, N1 = f.N1;
+    const float *rays_o = a.rays_o, *rays_d = a.rays_d, *viewdirs = a.viewdirs;
+
+    auto* W = ctx->ws;
+    const size_t r = static_cast<size_t>(R);
+    const bool want_fg_w1 = want_extras[1] || o.decomposed[1] || (o.samples[1] && o.samples[1]->fg_w);
+    TpDenseRows rows;
+    if (rows.reserve(W, r, N0, N1) || W[9].reserve(r * 16 * 4)) return NEO_ERR_NOMEM;
+    if (want_fg_w1 && W[10].reserve(r * N1 * 4)) return NEO_ERR_NOMEM;
+    if (want_extras[1] && W[11].reserve(r * N1 * 4)) return NEO_ERR_NOMEM;
+    auto [far, fg_t0, bg_s0, fg_out, bg_out, fg_w0, bg_w0, fg_t1, bg_s1] = rows;
+    float* fg_w1 = want_fg_w1 ? W[10].as<float>() : nullptr;          // level-1 weights: only the options read them
+    float* bg_w1 = want_extras[1] ? W[11].as<float>() : nullptr;
+    float* scratch = W[9].as<float>();   // per-ray: fg_rgb(3) fg_depth fg_acc lambda bg_rgb(3) bg_depth
+    float* s_fg_rgb = scratch;
+    float* s_fg_depth = scratch + r * 3;
+    float* s_fg_acc = scratch + r * 4;
+    float* s_lambda = scratch + r * 5;
+    float* s_bg_rgb = scratch + r * 6;
+    float* s_bg_depth = scratch + r * 9;
+
+    neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);
+    neo::launch_tp_level0(far, f.edges, R, N0, f.near, fg_t0, bg_s0, s);
+
+    // the coarse level feeds the fine one through its weights (sigma) alone: when the caller allows it and nobody reads its colour
+    // or depth, its launches are density-only and its composites write neither
+    const bool sigma0 = o.level0_may_be_sigma_only && level0_sigma_only(o.level[0]);
+    const float* fg_t = fg_t0;
+    const float* bg_s = bg_s0;
+    for (int level = 0; level < 2; ++level) {
+        const int N = level == 0 ? N0 : N1;
+        const neo_tp_level_out* lo = o.level[level];
+        const neo_tp_edit_samples* so = o.samples[level];
+        const neo_tp_decomposed_out* dc = o.decomposed[level];
+        const bool dens = level == 0 && sigma0;
+        if (int rc = tp_launch(ctx, ctx->tp[level], f.sc, f.views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
+        if (int rc = tp_launch(ctx, ctx->tp[2 + level], f.sc, f.views, rays_o, rays_d, viewdirs, bg_s, far, R, N, chunk, bg_out, s, nullptr, nullptr, dens)) return rc;
+        float* fg_rgb = dens ? nullptr : (lo && lo->fg_rgb) ? lo->fg_rgb : s_fg_rgb;
+        float* bg_rgb = dens ? nullptr : (lo && lo->bg_rgb) ? lo->bg_rgb : s_bg_rgb;
+        float* fg_acc = (lo && lo->fg_acc) ? lo->fg_acc : s_fg_acc;
+        float* lam = (lo && lo->bg_lambda) ? lo->bg_lambda : s_lambda;
+        float* fg_w = level == 0 ? fg_w0 : fg_w1;
+        float* bg_w = level == 0 ? bg_w0 : bg_w1;
+        if (o.K_edit > 0) neo::launch_tp_edit(fg_out, fg_t, o.near_inst, o.far_inst, o.K_edit, R, N, *o.edit, s);
+        if (o.L > 0)
+            neo::launch_composite_layers(fg_out, fg_t, rays_d, far, R, N, o.layers->key, o.layers->rgb, o.layers->acc, o.layers->depth,
+                                         o.L, fg_rgb, fg_acc, dens ? nullptr : s_fg_depth, fg_w, lam, so ? so->visibility : nullptr, s);
+        else
+            neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, fg_rgb, fg_acc, dens ? nullptr : s_fg_depth, fg_w, lam, s);
+        if (dc)        // rows, positions and scene weights are still in this lane's scratch; bg_lambda is this level's own
+            neo::launch_tp_decompose(fg_out, fg_t, fg_w, o.near_inst, o.far_inst, o.K_dec, R, N, lam, dc->rgb, dc->acc, dc->depth, dc->id, s);
+        neo::launch_composite(2, bg_out, bg_s, N, nullptr, nullptr, R, N, 0, bg_rgb, nullptr, dens ? nullptr : s_bg_depth, bg_w,
+                              nullptr, s);
+        if (lo && (lo->rgb || lo->depth))
+            neo::launch_tp_merge(fg_rgb, s_fg_depth, lam, bg_rgb, s_bg_depth, R, lo->rgb, lo->depth, s);
+        if (want_extras[level]) {
+            const neo_tp_extras_out* ex = o.extras[level];
+            if (neo::launch_tp_extras(fg_t, fg_w, far, bg_s, bg_w, lam, rays_o, rays_d, R, N, o.u_extras, o.n_u, ex->opacity,
+                                      ex->disparity, ex->dist_pct, s))
+                return fail(NEO_ERR_INVALID, "unsupported sample or quantile count");
+        }
+        if (so) {
+            const size_t row = r * N * sizeof(float);
+            if (so->fg_t) HIP_TRY(hipMemcpyAsync(so->fg_t, fg_t, row, hipMemcpyDeviceToDevice, s));
+            if (so->bg_s) HIP_TRY(hipMemcpyAsync(so->bg_s, bg_s, row, hipMemcpyDeviceToDevice, s));
+            if (so->fg_w) HIP_TRY(hipMemcpyAsync(so->fg_w, fg_w, row, hipMemcpyDeviceToDevice, s));
+        }
+        if (level == 0) {
+            // hierarchical resampling (model.py:306-332) on the SCENE weights (the fine positions do not depend on layers): fg
+            // ascending; bg on the descending inverse radius
+            if (neo::launch_resample(fg_t0, N0, fg_w0, f.u, 0, R, N0, a.n_fine, 0, fg_t1, s) ||
+                neo::launch_resample(bg_s0, N0, bg_w0, f.u, 0, R, N0, a.n_fine, 1, bg_s1, s))
+                return fail(NEO_ERR_INVALID, "unsupported sample counts");
+            fg_t = fg_t1;
+            bg_s = bg_s1;
+        }
+    }
+    return check_launch();
+}
+
+// The compact two-level march (tp_frame.h): the two inside-sphere MLPs on rows that are map[] entries, *count of them.
+int tp_march_compact(const TpFrame& f, const TpFrameArgs& a, const TpCompactRows& c, const int* map, const int* count, int white) {
+    neo_ctx* ctx = f.ctx;
+    hipStream_t s = f.s;
+    const int R = a.R, N0 = f.N0, N1 = f.N1;
+    if (int rc = tp_launch(ctx, ctx->tp[0], f.sc, f.views, a.rays_o, a.rays_d, a.viewdirs, c.t0, nullptr, R, N0, a.chunk, c.out, s, map, count)) return rc;
+    neo::launch_composite(1, c.out, c.t0, N0, c.rays_d, c.far, R, N0, white, c.rgb[0], c.acc[0], c.depth[0], c.w0, nullptr, s, count);
+    if (neo::launch_resample(c.t0, N0, c.w0, f.u, 0, R, N0, a.n_fine, 0, c.t1, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    if (int rc = tp_launch(ctx, ctx->tp[1], f.sc, f.views, a.rays_o, a.rays_d, a.viewdirs, c.t1, nullptr, R, N1, a.chunk, c.out, s, map, count)) return rc;
+    neo::launch_composite(1, c.out, c.t1, N1, c.rays_d, c.far, R, N1, white, c.rgb[1], c.acc[1], c.depth[1], nullptr, nullptr, s, count);
+    return NEO_OK;
+}
+
+}  // namespace neo_host
 
 extern "C" {
 
@@ -332,118 +486,24 @@ int neo_tp_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const 
                                 level0, level1, nullptr, 0, nullptr, nullptr, stream);
 }
 
-// neo_tp_render with the extras of tp_extras.hip per level.  Without them (both structs NULL or empty) the launch list, the
-// workspaces and every output are neo_tp_render's as they always were: the level-1 composites pass a NULL w_out and W[10] / W[11]
-// are not touched.  A level whose extras are asked for has its two composites write their weights as well (level 0 does so anyway,
-// for the resampling; level 1 into W[10] / W[11]) and one k_tp_extras launch follows its merge.
+// neo_tp_render with the extras of tp_extras.hip per level: tp_render_dense with a level 0 that may be density-only.  Without
+// extras (both structs NULL or empty) the launch list, the workspaces and every output are neo_tp_render's.
 int neo_tp_render_extras(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
                          const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
                          int white_bkgd, const neo_tp_level_out* level0, const neo_tp_level_out* level1, const float* u_extras,
                          int n_u, const neo_tp_extras_out* extras0, const neo_tp_extras_out* extras1, void* stream) {
     ENTER(ctx);
-    REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
-    REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
-    REQUIRE(n_u >= 0 && n_u <= 8, "bad quantile count (0 <= n_u <= 8)");
-    const neo_tp_extras_out* extras[2] = {extras0, extras1};
-    bool want_extras[2];
-    for (int l = 0; l < 2; ++l) {
-        const neo_tp_extras_out* ex = extras[l];
-        want_extras[l] = ex && (ex->opacity || ex->disparity || (ex->dist_pct && n_u > 0));
-        REQUIRE(!(ex && ex->dist_pct && n_u > 0) || u_extras, "null quantile table");
-    }
-    if (R == 0) return NEO_OK;
-    REQUIRE(rays_o && rays_d && viewdirs && src_poses, "null pointer");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    for (int i = 0; i < 4; ++i)
-        if (!ctx->tp[i].ready) return fail(NEO_ERR_STATE, "NeRF_TP MLP slot %d has no weights", i);
-    REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3 && ctx->tp[2].input_ch == 4 && ctx->tp[3].input_ch == 4,
-            "slots 0,1 must be fg (input_ch 3), slots 2,3 bg (input_ch 4)");
     (void)white_bkgd;  // out_depth=True semantics: the reference composites with white_bkgd=False (model.py:477-501)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
-    sc.grid_w = ctx->ray_grid_w;              // pixel-grid hint of the frame API: the evaluators walk the rays in 8 x 8 patches
-    sc.grid_first = ctx->ray_grid_first;
-
-    const int N0 = n_coarse + 1, N1 = N0 + n_fine;
-    const float near = 1e-4f;                                         // model.py:277
-    const float* edges = ctx->get_edges(n_coarse, 0.0f, 1.0f, s);     // linspace(0,1,n+1)
-    const float* u = ctx->get_quantiles(n_fine, s);
-    if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
-
-    // workspaces: this lane's set (neo_ctx_set_lane); the call reads shared weights / maps and writes lane scratch only
-    ORDERED_LANE(ctx, s);
-    auto* W = ctx->ws;
-    const size_t r = static_cast<size_t>(R);
-    if (W[0].reserve(r * 4) || W[1].reserve(r * N0 * 4) || W[2].reserve(r * N0 * 4) || W[3].reserve(r * N1 * 16) ||
-        W[4].reserve(r * N1 * 16) || W[5].reserve(r * N0 * 4) || W[6].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) ||
-        W[8].reserve(r * N1 * 4) || W[9].reserve(r * 16 * 4))
-        return NEO_ERR_NOMEM;
-    if (want_extras[1] && (W[10].reserve(r * N1 * 4) || W[11].reserve(r * N1 * 4))) return NEO_ERR_NOMEM;
-    float* far = W[0].as<float>();
-    float* fg_t0 = W[1].as<float>();
-    float* bg_s0 = W[2].as<float>();
-    float* fg_out = W[3].as<float>();
-    float* bg_out = W[4].as<float>();
-    float* fg_w0 = W[5].as<float>();
-    float* bg_w0 = W[6].as<float>();
-    float* fg_t1 = W[7].as<float>();
-    float* bg_s1 = W[8].as<float>();
-    float* fg_w1 = want_extras[1] ? W[10].as<float>() : nullptr;      // level-1 weights: only the extras read them
-    float* bg_w1 = want_extras[1] ? W[11].as<float>() : nullptr;
-    float* scratch = W[9].as<float>();   // per-ray: fg_rgb(3) fg_depth fg_acc lambda bg_rgb(3) bg_depth
-    float* s_fg_rgb = scratch;
-    float* s_fg_depth = scratch + r * 3;
-    float* s_fg_acc = scratch + r * 4;
-    float* s_lambda = scratch + r * 5;
-    float* s_bg_rgb = scratch + r * 6;
-    float* s_bg_depth = scratch + r * 9;
-
-    neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);
-    neo::launch_tp_level0(far, edges, R, N0, near, fg_t0, bg_s0, s);
-
-    // the coarse level feeds the fine one through its weights (sigma) alone: when nobody reads its colour or depth, its
-    // launches are density-only and its composites write neither
-    const bool sigma0 = level0_sigma_only(level0);
-    const float* fg_t = fg_t0;
-    const float* bg_s = bg_s0;
-    for (int level = 0; level < 2; ++level) {
-        const int N = level == 0 ? N0 : N1;
-        const neo_tp_level_out* lo = level == 0 ? level0 : level1;
-        const bool dens = level == 0 && sigma0;
-        MlpSlot& fg = ctx->tp[level];
-        MlpSlot& bg = ctx->tp[2 + level];
-        if (int rc = tp_launch(ctx, fg, sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
-        if (int rc = tp_launch(ctx, bg, sc, views, rays_o, rays_d, viewdirs, bg_s, far, R, N, chunk, bg_out, s, nullptr, nullptr, dens)) return rc;
-        float* fg_rgb = dens ? nullptr : (lo && lo->fg_rgb) ? lo->fg_rgb : s_fg_rgb;
-        float* bg_rgb = dens ? nullptr : (lo && lo->bg_rgb) ? lo->bg_rgb : s_bg_rgb;
-        float* fg_acc = (lo && lo->fg_acc) ? lo->fg_acc : s_fg_acc;
-        float* lam = (lo && lo->bg_lambda) ? lo->bg_lambda : s_lambda;
-        float* fg_w = level == 0 ? fg_w0 : fg_w1;
-        float* bg_w = level == 0 ? bg_w0 : bg_w1;
-        neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, fg_rgb, fg_acc, dens ? nullptr : s_fg_depth, fg_w, lam, s);
-        neo::launch_composite(2, bg_out, bg_s, N, nullptr, nullptr, R, N, 0, bg_rgb, nullptr, dens ? nullptr : s_bg_depth, bg_w,
-                              nullptr, s);
-        if (lo && (lo->rgb || lo->depth))
-            neo::launch_tp_merge(fg_rgb, s_fg_depth, lam, bg_rgb, s_bg_depth, R, lo->rgb, lo->depth, s);
-        if (want_extras[level]) {
-            const neo_tp_extras_out* ex = extras[level];
-            if (neo::launch_tp_extras(fg_t, fg_w, far, bg_s, bg_w, lam, rays_o, rays_d, R, N, u_extras, n_u, ex->opacity, ex->disparity,
-                                      ex->dist_pct, s))
-                return fail(NEO_ERR_INVALID, "unsupported sample or quantile count");
-        }
-        if (level == 0) {
-            // hierarchical resampling (model.py:306-332): fg ascending; bg on the descending inverse radius
-            if (neo::launch_resample(fg_t0, N0, fg_w0, u, 0, R, N0, n_fine, 0, fg_t1, s) ||
-                neo::launch_resample(bg_s0, N0, bg_w0, u, 0, R, N0, n_fine, 1, bg_s1, s))
-                return fail(NEO_ERR_INVALID, "unsupported sample counts");
-            fg_t = fg_t1;
-            bg_s = bg_s1;
-        }
-    }
-    return check_launch();
+    TpDenseOptions o;
+    o.level[0] = level0;
+    o.level[1] = level1;
+    o.level0_may_be_sigma_only = true;
+    o.u_extras = u_extras;
+    o.n_u = n_u;
+    o.extras[0] = extras0;
+    o.extras[1] = extras1;
+    return tp_render_dense(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, o);
 }
-
 
 // the pure function of tp_extras.hip on caller rows; touches no context-owned memory: no ordering scope (as neo_mip_extras)
 int neo_tp_extras(neo_ctx* ctx, const float* fg_t, const float* fg_w, const float* far, const float* bg_s, const float* bg_w,
@@ -467,50 +527,31 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
                          int white_bkgd, const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps,
                          int* survivors_out, void* stream) {
     ENTER(ctx);
-    REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
-    REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
-    REQUIRE(eps > 0.0f && eps < 1.0f, "eps must lie in (0, 1)");
-    if (R == 0) {
-        if (survivors_out) HIP_TRY(hipMemsetAsync(survivors_out, 0, sizeof(int), static_cast<hipStream_t>(stream)));
+    (void)white_bkgd;  // as neo_tp_render
+    const TpFrameArgs a{rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream};
+    TpFrame::Own own;
+    if (!(eps > 0.0f && eps < 1.0f)) own.after_counts = "eps must lie in (0, 1)";
+    TpFrame f;      // the foreground launches keep the ray-patch order; compact launches drop it (tp_launch)
+    if (int rc = f.begin(ctx, a, true, true, own)) return rc;
+    hipStream_t s = f.s;
+    if (f.empty) {
+        if (survivors_out) HIP_TRY(hipMemsetAsync(survivors_out, 0, sizeof(int), s));
         return NEO_OK;
     }
-    REQUIRE(rays_o && rays_d && viewdirs && src_poses, "null pointer");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    for (int i = 0; i < 4; ++i)
-        if (!ctx->tp[i].ready) return fail(NEO_ERR_STATE, "NeRF_TP MLP slot %d has no weights", i);
-    REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3 && ctx->tp[2].input_ch == 4 && ctx->tp[3].input_ch == 4,
-            "slots 0,1 must be fg (input_ch 3), slots 2,3 bg (input_ch 4)");
-    (void)white_bkgd;  // as neo_tp_render
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
-    sc.grid_w = ctx->ray_grid_w;              // the foreground launches keep the ray-patch order; compact launches drop it (tp_launch)
-    sc.grid_first = ctx->ray_grid_first;
+    const int N0 = f.N0, N1 = f.N1;
+    const neo::TpScene& sc = f.sc;
+    const neo::TpViews& views = f.views;
 
-    const int N0 = n_coarse + 1, N1 = N0 + n_fine;
-    const float near = 1e-4f;
-    const float* edges = ctx->get_edges(n_coarse, 0.0f, 1.0f, s);
-    const float* u = ctx->get_quantiles(n_fine, s);
-    if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
-
-    // workspaces: this lane's set, as neo_tp_render (W[0..9]); W[9] holds the per-ray foreground results of BOTH levels (they are
-    // merged only after the background has run) and the compact background results, W[10] the compaction's map / slot / count
-    ORDERED_LANE(ctx, s);
+    // workspaces: the dense layout (W[0..8]); W[9] holds the per-ray foreground results of BOTH levels (they are merged only after
+    // the background has run) and the compact background results, W[10] the compaction's map / slot / count
     auto* W = ctx->ws;
     const size_t r = static_cast<size_t>(R);
-    if (W[0].reserve(r * 4) || W[1].reserve(r * N0 * 4) || W[2].reserve(r * N0 * 4) || W[3].reserve(r * N1 * 16) ||
-        W[4].reserve(r * N1 * 16) || W[5].reserve(r * N0 * 4) || W[6].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) ||
-        W[8].reserve(r * N1 * 4) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)))
+    TpDenseRows rows;
+    if (rows.reserve(W, r, N0, N1) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)))
         return NEO_ERR_NOMEM;
-    float* far = W[0].as<float>();
-    float* fg_t0 = W[1].as<float>();
-    float* bg_s0 = W[2].as<float>();      // the same row for every ray (k_tp_level0): its first `count` rows ARE the compact level-0 rows
-    float* fg_out = W[3].as<float>();
-    float* bg_out = W[4].as<float>();     // compact from here on: row k belongs to ray map[k]
-    float* fg_w0 = W[5].as<float>();
-    float* bg_w0 = W[6].as<float>();
-    float* fg_t1 = W[7].as<float>();
-    float* bg_s1 = W[8].as<float>();
+    // bg_s0 is the same row for every ray (k_tp_level0): its first `count` rows ARE the compact level-0 rows; bg_out, bg_w0 and
+    // bg_s1 are compact: row k belongs to ray map[k]
+    auto [far, fg_t0, bg_s0, fg_out, bg_out, fg_w0, bg_w0, fg_t1, bg_s1] = rows;
     float* scratch = W[9].as<float>();    // per level: fg_rgb(3) fg_depth fg_acc lambda bg_rgb(3) = 9 floats a ray; then compact bg_rgb(3) bg_depth, reused
     float* c_bg_rgb = scratch + r * 18;
     float* c_bg_depth = scratch + r * 21;
@@ -520,8 +561,7 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     const int* count = neo::cull_count_of(cws, R);
 
     neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);       // sphere-miss assertions: every ray, culled or not
-    neo::launch_tp_level0(far, edges, R, N0, near, fg_t0, bg_s0, s);
-
+    neo::launch_tp_level0(far, f.edges, R, N0, f.near, fg_t0, bg_s0, s);
     const bool sigma0 = level0_sigma_only(level0);     // as neo_tp_render: density-only level-0 launches, no level-0 colour / depth
     struct LevelFg { float* fg_rgb; float* fg_depth; float* fg_acc; float* lam; float* bg_rgb; } L[2];
     for (int level = 0; level < 2; ++level) {
@@ -534,7 +574,7 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, fg_t0, nullptr, R, N0, chunk, fg_out, s, nullptr, nullptr, sigma0)) return rc;
     neo::launch_composite(1, fg_out, fg_t0, N0, rays_d, far, R, N0, 0, sigma0 ? nullptr : L[0].fg_rgb, L[0].fg_acc,
                           sigma0 ? nullptr : L[0].fg_depth, fg_w0, L[0].lam, s);
-    if (neo::launch_resample(fg_t0, N0, fg_w0, u, 0, R, N0, n_fine, 0, fg_t1, s)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    if (neo::launch_resample(fg_t0, N0, fg_w0, f.u, 0, R, N0, n_fine, 0, fg_t1, s)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
     if (int rc = tp_launch(ctx, ctx->tp[1], sc, views, rays_o, rays_d, viewdirs, fg_t1, nullptr, R, N1, chunk, fg_out, s)) return rc;
     neo::launch_composite(1, fg_out, fg_t1, N1, rays_d, far, R, N1, 0, L[1].fg_rgb, L[1].fg_acc, L[1].fg_depth, nullptr, L[1].lam, s);
 
@@ -544,7 +584,7 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     if (int rc = tp_launch(ctx, ctx->tp[2], sc, views, rays_o, rays_d, viewdirs, bg_s0, far, R, N0, chunk, bg_out, s, map, count, sigma0)) return rc;
     neo::launch_composite(2, bg_out, bg_s0, N0, nullptr, nullptr, R, N0, 0, sigma0 ? nullptr : c_bg_rgb, nullptr,
                           sigma0 ? nullptr : c_bg_depth, bg_w0, nullptr, s, count);
-    if (neo::launch_resample(bg_s0, N0, bg_w0, u, 0, R, N0, n_fine, 1, bg_s1, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    if (neo::launch_resample(bg_s0, N0, bg_w0, f.u, 0, R, N0, n_fine, 1, bg_s1, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
     if (level0 && (level0->rgb || level0->depth || level0->bg_rgb))
         neo::launch_tp_merge_culled(L[0].fg_rgb, L[0].fg_depth, L[0].lam, c_bg_rgb, c_bg_depth, slot, R, level0->rgb, level0->depth,
                                     L[0].bg_rgb, s);
@@ -564,62 +604,34 @@ int neo_tp_render_objects(neo_ctx* ctx, const float* rays_o, const float* rays_d
                           int n_coarse, int n_fine, int white_bkgd, const neo_tp_object_out* level0,
                           const neo_tp_object_out* level1, int* hits_out, void* stream) {
     ENTER(ctx);
-    REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
-    REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
-    if (R == 0) {
-        if (hits_out) HIP_TRY(hipMemsetAsync(hits_out, 0, sizeof(int), static_cast<hipStream_t>(stream)));
+    const TpFrameArgs a{rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream};
+    TpFrame::Own own;
+    own.ptrs = near_obj && far_obj;
+    TpFrame f;      // no outside-sphere slots, no ray-grid hint: every launch is compact
+    if (int rc = f.begin(ctx, a, false, false, own)) return rc;
+    hipStream_t s = f.s;
+    if (f.empty) {
+        if (hits_out) HIP_TRY(hipMemsetAsync(hits_out, 0, sizeof(int), s));
         return NEO_OK;
     }
-    REQUIRE(rays_o && rays_d && viewdirs && src_poses && near_obj && far_obj, "null pointer");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    for (int i = 0; i < 2; ++i)          // the outside-sphere slots 2, 3 are not needed
-        if (!ctx->tp[i].ready) return fail(NEO_ERR_STATE, "NeRF_TP MLP slot %d has no weights", i);
-    REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3, "slots 0,1 must be fg (input_ch 3)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);      // no ray-grid hint: every launch is compact
-
-    const int N0 = n_coarse + 1, N1 = N0 + n_fine;
-    const float* edges = ctx->get_edges(n_coarse, 0.0f, 1.0f, s);
-    const float* u = ctx->get_quantiles(n_fine, s);
-    if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
 
     // workspaces: this lane's set.  Everything but the map is COMPACT (row k belongs to ray map[k]) and sized for R rows.
-    ORDERED_LANE(ctx, s);
     auto* W = ctx->ws;
-    const size_t r = static_cast<size_t>(R);
-    if (W[0].reserve(r * 4) || W[1].reserve(r * N0 * 4) || W[2].reserve(r * 3 * 4) || W[3].reserve(r * N1 * 16) ||
-        W[5].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) || W[9].reserve(r * 10 * 4) ||
-        W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)))
-        return NEO_ERR_NOMEM;
-    float* far_c = W[0].as<float>();
-    float* t0_c = W[1].as<float>();
-    float* rays_d_c = W[2].as<float>();
-    float* out = W[3].as<float>();
-    float* w0 = W[5].as<float>();
-    float* t1_c = W[7].as<float>();
-    float* res = W[9].as<float>();        // per level: rgb(3) acc depth = 5 floats a row
+    TpCompactRows c;
+    if (c.reserve(W, static_cast<size_t>(R), f.N0, f.N1) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int))) return NEO_ERR_NOMEM;
     int* cws = W[10].as<int>();
     const int* map = neo::cull_map_of(cws, R);
     const int* slot = neo::cull_slot_of(cws, R);
     const int* count = neo::cull_count_of(cws, R);
-    float* c_rgb[2] = {res, res + r * 5};
-    float* c_acc[2] = {res + r * 3, res + r * 8};
-    float* c_depth[2] = {res + r * 4, res + r * 9};
 
     neo::launch_obj_compact(near_obj, far_obj, R, cws, hits_out, s);
-    neo::launch_obj_level0(near_obj, far_obj, rays_d, edges, map, count, R, N0, t0_c, far_c, rays_d_c, s);
-    // grids sized for R, every kernel takes its row count from the device word
-    if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, t0_c, nullptr, R, N0, chunk, out, s, map, count)) return rc;
-    neo::launch_composite(1, out, t0_c, N0, rays_d_c, far_c, R, N0, white_bkgd ? 1 : 0, c_rgb[0], c_acc[0], c_depth[0], w0, nullptr, s, count);
-    if (neo::launch_resample(t0_c, N0, w0, u, 0, R, N0, n_fine, 0, t1_c, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
-    if (int rc = tp_launch(ctx, ctx->tp[1], sc, views, rays_o, rays_d, viewdirs, t1_c, nullptr, R, N1, chunk, out, s, map, count)) return rc;
-    neo::launch_composite(1, out, t1_c, N1, rays_d_c, far_c, R, N1, white_bkgd ? 1 : 0, c_rgb[1], c_acc[1], c_depth[1], nullptr, nullptr, s, count);
+    neo::launch_obj_level0(near_obj, far_obj, rays_d, f.edges, map, count, R, f.N0, c.t0, c.far, c.rays_d, s);
+    if (int rc = tp_march_compact(f, a, c, map, count, white_bkgd ? 1 : 0)) return rc;
     if (level0)
-        neo::launch_obj_scatter(slot, R, N0, c_rgb[0], c_acc[0], c_depth[0], t0_c, white_bkgd, level0->rgb, level0->acc, level0->depth,
+        neo::launch_obj_scatter(slot, R, f.N0, c.rgb[0], c.acc[0], c.depth[0], c.t0, white_bkgd, level0->rgb, level0->acc, level0->depth,
                                 level0->tvals, s);
     if (level1)
-        neo::launch_obj_scatter(slot, R, N1, c_rgb[1], c_acc[1], c_depth[1], t1_c, white_bkgd, level1->rgb, level1->acc, level1->depth,
+        neo::launch_obj_scatter(slot, R, f.N1, c.rgb[1], c.acc[1], c.depth[1], c.t1, white_bkgd, level1->rgb, level1->acc, level1->depth,
                                 level1->tvals, s);
     return check_launch();
 }

@@ -7,19 +7,11 @@
 //                        holds it, else the rest - and sums w c, w and w t per owner in k_composite's own order.
 //
 // The arithmetic is stated in include/neo360_hip.h (DECOMPOSITION RULE).  No evaluator, and not k_composite, is touched: the launch
-// list is neo_tp_render_edited's (edit.hip) without edits and layers, plus one k_tp_decompose per requested level.
+// list is the dense frame's (tp_render_dense, api_tp.hip) with a full level 0, plus one k_tp_decompose per requested level.
 #include "common.h"
-#include "ctx.h"
+#include "tp_frame.h"
 
 using namespace neo_host;
-
-// the launch list of the edited render (edit.hip), which runs k_tp_decompose behind the inside-sphere composite of a level
-int neo_tp_render_rows(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
-                       const float* far_inst, int K_edit, const neo::TpEditTable& tab, const neo_tp_layers* layers, int L, int K_dec,
-                       const neo_tp_decomposed_out* decomposed0, const neo_tp_decomposed_out* decomposed1, int R, int chunk,
-                       const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
-                       const neo_tp_level_out* level0, const neo_tp_level_out* level1, const neo_tp_edit_samples* samples0,
-                       const neo_tp_edit_samples* samples1, void* stream);
 
 namespace neo {
 
@@ -161,8 +153,8 @@ int neo_tp_decompose_rows(neo_ctx* ctx, const float* rgbsigma, const float* t, c
     return check_launch();
 }
 
-// neo_tp_render_edited's launch list (edit.hip) without edits and layers, with k_tp_decompose behind the inside-sphere composite of
-// every level that asks for it
+// the dense frame (tp_render_dense, api_tp.hip) with a full level 0 and k_tp_decompose behind the inside-sphere composite of every
+// level that asks for it
 int neo_tp_render_decomposed(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
                              const float* far_inst, int K, int R, int chunk, const float* src_poses, int NV, float focal, float cx,
                              float cy, int n_coarse, int n_fine, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
@@ -171,9 +163,17 @@ int neo_tp_render_decomposed(neo_ctx* ctx, const float* rays_o, const float* ray
     ENTER(ctx);
     REQUIRE(K >= 0 && K <= neo::TP_MAX_EDITS, "0..32 instances supported");
     REQUIRE(static_cast<long>(K + 1) * R * 3 <= 2147483647L, "too many (instance, ray) pairs for 32-bit indices");
-    const neo::TpEditTable no_edits{};
-    return neo_tp_render_rows(ctx, rays_o, rays_d, viewdirs, near_inst, far_inst, 0, no_edits, nullptr, 0, K, decomposed0, decomposed1,
-                              R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, level0, level1, samples0, samples1, stream);
+    TpDenseOptions o;
+    o.level[0] = level0;
+    o.level[1] = level1;
+    o.near_inst = near_inst;
+    o.far_inst = far_inst;
+    o.decomposed[0] = decomposed0;
+    o.decomposed[1] = decomposed1;
+    o.K_dec = K;
+    o.samples[0] = samples0;
+    o.samples[1] = samples1;
+    return tp_render_dense(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, o);
 }
 
 }  // extern "C"

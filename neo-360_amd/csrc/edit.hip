@@ -9,16 +9,11 @@
 //                        neo_tp_render_objects - spliced into the ray in depth order.
 //
 // The arithmetic of both is stated in include/neo360_hip.h (EDIT RULE, LAYER RECURRENCE).  No evaluator, and not k_composite, is
-// touched: without edits and layers the launch list below is neo_tp_render's with a full level 0.
+// touched: without edits and layers the launch list (tp_render_dense, api_tp.hip) is neo_tp_render's with a full level 0.
 #include "common.h"
-#include "ctx.h"
+#include "tp_frame.h"
 
 using namespace neo_host;
-
-// one region's evaluator launch (api_tp.hip)
-int neo_tp_eval_region(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
-                       const float* rays_d, const float* viewdirs, const float* tvals, const float* far, int R, int N,
-                       int chunk, float* out, hipStream_t s);
 
 namespace neo {
 
@@ -275,120 +270,8 @@ int neo_composite_layers(neo_ctx* ctx, const float* rgbsigma, const float* t, co
     return check_launch();
 }
 
-}  // extern "C"
-
-// neo_tp_render's launch list with a full level 0, k_tp_edit on the inside-sphere rows of each level before their composite,
-// k_composite_layers as that composite when layers are given, and k_tp_decompose (decompose.hip) behind it for every level that has
-// a decomposed struct.  Everything else - background half, resampling, merge, flags, lanes - is neo_tp_render_extras' (api_tp.hip).
-// Shared by neo_tp_render_edited (below) and neo_tp_render_decomposed (decompose.hip: K_edit = 0, L = 0); the caller has entered
-// the context and checked its own counts.
-int neo_tp_render_rows(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
-                       const float* far_inst, int K_edit, const neo::TpEditTable& tab, const neo_tp_layers* layers, int L, int K_dec,
-                       const neo_tp_decomposed_out* decomposed0, const neo_tp_decomposed_out* decomposed1, int R, int chunk,
-                       const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
-                       const neo_tp_level_out* level0, const neo_tp_level_out* level1, const neo_tp_edit_samples* samples0,
-                       const neo_tp_edit_samples* samples1, void* stream) {
-    REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
-    REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
-    if (R == 0) return NEO_OK;
-    REQUIRE(rays_o && rays_d && viewdirs && src_poses, "null pointer");
-    REQUIRE((K_edit == 0 && K_dec == 0) || (near_inst && far_inst), "null interval pointer");
-    REQUIRE(L == 0 || (layers && layers->key && layers->rgb && layers->acc && layers->depth), "null layer pointer");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    for (int i = 0; i < 4; ++i)
-        if (!ctx->tp[i].ready) return fail(NEO_ERR_STATE, "NeRF_TP MLP slot %d has no weights", i);
-    REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3 && ctx->tp[2].input_ch == 4 && ctx->tp[3].input_ch == 4,
-            "slots 0,1 must be fg (input_ch 3), slots 2,3 bg (input_ch 4)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);
-    sc.grid_w = ctx->ray_grid_w;              // pixel-grid hint of the frame API, as neo_tp_render
-    sc.grid_first = ctx->ray_grid_first;
-
-    const int N0 = n_coarse + 1, N1 = N0 + n_fine;
-    const float near = 1e-4f;                                         // model.py:277
-    const float* edges = ctx->get_edges(n_coarse, 0.0f, 1.0f, s);     // linspace(0,1,n+1)
-    const float* u = ctx->get_quantiles(n_fine, s);
-    if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
-
-    // workspaces: this lane's set, laid out as in neo_tp_render; W[10] the level-1 inside-sphere weights when they are asked for
-    // or the level is decomposed
-    ORDERED_LANE(ctx, s);
-    auto* W = ctx->ws;
-    const size_t r = static_cast<size_t>(R);
-    const bool want_w1 = decomposed1 || (samples1 && samples1->fg_w);
-    if (W[0].reserve(r * 4) || W[1].reserve(r * N0 * 4) || W[2].reserve(r * N0 * 4) || W[3].reserve(r * N1 * 16) ||
-        W[4].reserve(r * N1 * 16) || W[5].reserve(r * N0 * 4) || W[6].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) ||
-        W[8].reserve(r * N1 * 4) || W[9].reserve(r * 16 * 4))
-        return NEO_ERR_NOMEM;
-    if (want_w1 && W[10].reserve(r * N1 * 4)) return NEO_ERR_NOMEM;
-    float* far = W[0].as<float>();
-    float* fg_t0 = W[1].as<float>();
-    float* bg_s0 = W[2].as<float>();
-    float* fg_out = W[3].as<float>();
-    float* bg_out = W[4].as<float>();
-    float* fg_w0 = W[5].as<float>();
-    float* bg_w0 = W[6].as<float>();
-    float* fg_t1 = W[7].as<float>();
-    float* bg_s1 = W[8].as<float>();
-    float* fg_w1 = want_w1 ? W[10].as<float>() : nullptr;
-    float* scratch = W[9].as<float>();   // per-ray: fg_rgb(3) fg_depth fg_acc lambda bg_rgb(3) bg_depth
-    float* s_fg_rgb = scratch;
-    float* s_fg_depth = scratch + r * 3;
-    float* s_fg_acc = scratch + r * 4;
-    float* s_lambda = scratch + r * 5;
-    float* s_bg_rgb = scratch + r * 6;
-    float* s_bg_depth = scratch + r * 9;
-
-    neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);
-    neo::launch_tp_level0(far, edges, R, N0, near, fg_t0, bg_s0, s);
-
-    const float* fg_t = fg_t0;
-    const float* bg_s = bg_s0;
-    for (int level = 0; level < 2; ++level) {
-        const int N = level == 0 ? N0 : N1;
-        const neo_tp_level_out* lo = level == 0 ? level0 : level1;
-        const neo_tp_edit_samples* so = level == 0 ? samples0 : samples1;
-        const neo_tp_decomposed_out* dc = level == 0 ? decomposed0 : decomposed1;
-        if (int rc = neo_tp_eval_region(ctx, level, sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s)) return rc;
-        if (int rc = neo_tp_eval_region(ctx, 2 + level, sc, views, rays_o, rays_d, viewdirs, bg_s, far, R, N, chunk, bg_out, s)) return rc;
-        float* fg_rgb = (lo && lo->fg_rgb) ? lo->fg_rgb : s_fg_rgb;
-        float* bg_rgb = (lo && lo->bg_rgb) ? lo->bg_rgb : s_bg_rgb;
-        float* fg_acc = (lo && lo->fg_acc) ? lo->fg_acc : s_fg_acc;
-        float* lam = (lo && lo->bg_lambda) ? lo->bg_lambda : s_lambda;
-        float* fg_w = level == 0 ? fg_w0 : fg_w1;
-        neo::launch_tp_edit(fg_out, fg_t, near_inst, far_inst, K_edit, R, N, tab, s);
-        if (L > 0)
-            neo::launch_composite_layers(fg_out, fg_t, rays_d, far, R, N, layers->key, layers->rgb, layers->acc, layers->depth, L,
-                                         fg_rgb, fg_acc, s_fg_depth, fg_w, lam, so ? so->visibility : nullptr, s);
-        else
-            neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, fg_rgb, fg_acc, s_fg_depth, fg_w, lam, s);
-        if (dc)        // rows, positions and scene weights are still in this lane's scratch; bg_lambda is this level's own
-            neo::launch_tp_decompose(fg_out, fg_t, fg_w, near_inst, far_inst, K_dec, R, N, lam, dc->rgb, dc->acc, dc->depth, dc->id, s);
-        neo::launch_composite(2, bg_out, bg_s, N, nullptr, nullptr, R, N, 0, bg_rgb, nullptr, s_bg_depth, level == 0 ? bg_w0 : nullptr,
-                              nullptr, s);
-        if (lo && (lo->rgb || lo->depth))
-            neo::launch_tp_merge(fg_rgb, s_fg_depth, lam, bg_rgb, s_bg_depth, R, lo->rgb, lo->depth, s);
-        if (so) {
-            const size_t row = r * N * sizeof(float);
-            if (so->fg_t) HIP_TRY(hipMemcpyAsync(so->fg_t, fg_t, row, hipMemcpyDeviceToDevice, s));
-            if (so->bg_s) HIP_TRY(hipMemcpyAsync(so->bg_s, bg_s, row, hipMemcpyDeviceToDevice, s));
-            if (so->fg_w) HIP_TRY(hipMemcpyAsync(so->fg_w, fg_w, row, hipMemcpyDeviceToDevice, s));
-        }
-        if (level == 0) {
-            // hierarchical resampling (model.py:306-332) on the SCENE weights: the fine positions do not depend on the layers
-            if (neo::launch_resample(fg_t0, N0, fg_w0, u, 0, R, N0, n_fine, 0, fg_t1, s) ||
-                neo::launch_resample(bg_s0, N0, bg_w0, u, 0, R, N0, n_fine, 1, bg_s1, s))
-                return fail(NEO_ERR_INVALID, "unsupported sample counts");
-            fg_t = fg_t1;
-            bg_s = bg_s1;
-        }
-    }
-    return check_launch();
-}
-
-extern "C" {
-
+// the dense frame (tp_render_dense, api_tp.hip) with a full level 0, k_tp_edit on the inside-sphere rows of each level before their
+// composite and k_composite_layers as that composite when layers are given
 int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, const float* near_inst,
                          const float* far_inst, int K, const float* density_scale, const float* tint, const neo_tp_layers* layers,
                          int L, int R, int chunk, const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse,
@@ -400,8 +283,18 @@ int neo_tp_render_edited(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     REQUIRE(static_cast<long>(K > L ? K : L) * R * 3 <= 2147483647L, "too many (instance, ray) pairs for 32-bit indices");
     neo::TpEditTable tab;
     if (int rc = fill_edit_table(tab, K, density_scale, tint)) return rc;
-    return neo_tp_render_rows(ctx, rays_o, rays_d, viewdirs, near_inst, far_inst, K, tab, layers, L, 0, nullptr, nullptr, R, chunk,
-                              src_poses, NV, focal, cx, cy, n_coarse, n_fine, level0, level1, samples0, samples1, stream);
+    TpDenseOptions o;
+    o.level[0] = level0;
+    o.level[1] = level1;
+    o.near_inst = near_inst;
+    o.far_inst = far_inst;
+    o.edit = &tab;
+    o.K_edit = K;
+    o.layers = layers;
+    o.L = L;
+    o.samples[0] = samples0;
+    o.samples[1] = samples1;
+    return tp_render_dense(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, o);
 }
 
 }  // extern "C"

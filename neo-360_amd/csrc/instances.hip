@@ -15,14 +15,9 @@
 // The evaluators, compositing and resampling in between are the existing kernels on compact rows, untouched.
 #include "common.h"
 #include "compact.h"
-#include "ctx.h"
+#include "tp_frame.h"
 
 using namespace neo_host;
-
-// one compact inside-sphere evaluator launch (api_tp.hip)
-int neo_tp_eval_compact(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
-                        const float* rays_d, const float* viewdirs, const float* tvals, int R, int N, int chunk, float* out,
-                        const int* map, const int* count, hipStream_t s);
 
 namespace neo {
 
@@ -231,12 +226,16 @@ int neo_tp_render_instances(neo_ctx* ctx, const float* rays_o, const float* rays
                             float cy, int n_coarse, int n_fine, int white_bkgd, const neo_tp_instance_out* level0,
                             const neo_tp_instance_out* level1, int* pairs_out, void* stream) {
     ENTER(ctx);
-    REQUIRE(R >= 0 && chunk >= 1, "bad ray count / chunk");
-    REQUIRE(K >= 0 && K <= 32, "0..32 instances supported");
-    REQUIRE(static_cast<long>(K) * R * 3 <= 2147483647L, "too many (instance, ray) pairs for 32-bit indices");
-    REQUIRE(n_coarse >= 3 && n_coarse <= 256 && n_fine >= 1 && n_coarse + 1 + n_fine <= 1024, "unsupported sample counts");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (R == 0 || K == 0) {
+    const TpFrameArgs a{rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream};
+    TpFrame::Own own;
+    if (!(K >= 0 && K <= 32)) own.after_rays = "0..32 instances supported";
+    else if (!(static_cast<long>(K) * R * 3 <= 2147483647L)) own.after_rays = "too many (instance, ray) pairs for 32-bit indices";
+    own.empty = K == 0;
+    own.ptrs = near_inst && far_inst;
+    TpFrame f;      // no outside-sphere slots, no ray-grid hint: every launch is compact
+    if (int rc = f.begin(ctx, a, false, false, own)) return rc;
+    hipStream_t s = f.s;
+    if (f.empty) {
         if (pairs_out) HIP_TRY(hipMemsetAsync(pairs_out, 0, sizeof(int), s));
         if (R == 0) return NEO_OK;
         // no instances: the composite of a ray without hits (the kernel reads no input when K == 0)
@@ -246,45 +245,21 @@ int neo_tp_render_instances(neo_ctx* ctx, const float* rays_o, const float* rays
                                            lv->comp_acc, lv->comp_depth, lv->instance_id, s);
         return check_launch();
     }
-    REQUIRE(rays_o && rays_d && viewdirs && src_poses && near_inst && far_inst, "null pointer");
-    if (!ctx->scene_ready) return fail(NEO_ERR_STATE, "scene features not set (neo_tp_set_scene)");
-    REQUIRE(NV == ctx->scene.nv, "NV differs from the uploaded scene");
-    for (int i = 0; i < 2; ++i)          // the outside-sphere slots 2, 3 are not needed
-        if (!ctx->tp[i].ready) return fail(NEO_ERR_STATE, "NeRF_TP MLP slot %d has no weights", i);
-    REQUIRE(ctx->tp[0].input_ch == 3 && ctx->tp[1].input_ch == 3, "slots 0,1 must be fg (input_ch 3)");
-    auto [sc, views] = call_scene(ctx->scene, src_poses, NV, focal, cx, cy);      // no ray-grid hint: every launch is compact
 
-    const int N0 = n_coarse + 1, N1 = N0 + n_fine;
-    const float* edges = ctx->get_edges(n_coarse, 0.0f, 1.0f, s);
-    const float* u = ctx->get_quantiles(n_fine, s);
-    if (!edges || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
-
-    // workspaces: this lane's set.  W[0..9] are one WINDOW's compact rows, as in neo_tp_render_objects (sized for R rows and reused
-    // by every window: the stream orders them); W[4] keeps every pair's un-whitened results of both levels for the composite,
-    // W[10] the pair compaction, the current window's ray map and the window counts.
-    ORDERED_LANE(ctx, s);
+    // workspaces: this lane's set.  `c` is one WINDOW's compact rows, as in neo_tp_render_objects (sized for R rows and reused by
+    // every window: the stream orders them); W[4] keeps every pair's un-whitened results of both levels for the composite, W[10]
+    // the pair compaction, the current window's ray map and the window counts.
     auto* W = ctx->ws;
     const size_t r = static_cast<size_t>(R), pairs = static_cast<size_t>(K) * r;
-    if (W[0].reserve(r * 4) || W[1].reserve(r * N0 * 4) || W[2].reserve(r * 3 * 4) || W[3].reserve(r * N1 * 16) ||
-        W[4].reserve(pairs * 10 * 4) || W[5].reserve(r * N0 * 4) || W[7].reserve(r * N1 * 4) || W[9].reserve(r * 10 * 4) ||
-        W[10].reserve(neo::inst_ws_ints(K, R) * sizeof(int)))
+    TpCompactRows c;
+    if (c.reserve(W, r, f.N0, f.N1) || W[4].reserve(pairs * 10 * 4) || W[10].reserve(neo::inst_ws_ints(K, R) * sizeof(int)))
         return NEO_ERR_NOMEM;
-    float* far_c = W[0].as<float>();
-    float* t0_c = W[1].as<float>();
-    float* rays_d_c = W[2].as<float>();
-    float* out = W[3].as<float>();
     float* prem = W[4].as<float>();       // per level: rgb(3) acc depth = 5 floats a pair
-    float* w0 = W[5].as<float>();
-    float* t1_c = W[7].as<float>();
-    float* res = W[9].as<float>();        // per level: rgb(3) acc depth = 5 floats a row
     int* cws = W[10].as<int>();
     const int P = K * R;
     const int* pair_map = neo::cull_map_of(cws, P);
     int* raymap = neo::inst_raymap_of(cws, K, R);
     const int* wcount = neo::inst_wcount_of(cws, K, R);
-    float* c_rgb[2] = {res, res + r * 5};
-    float* c_acc[2] = {res + r * 3, res + r * 8};
-    float* c_depth[2] = {res + r * 4, res + r * 9};
     float* p_rgb[2] = {prem, prem + pairs * 5};
     float* p_acc[2] = {prem + pairs * 3, prem + pairs * 8};
     float* p_depth[2] = {prem + pairs * 4, prem + pairs * 9};
@@ -298,15 +273,11 @@ int neo_tp_render_instances(neo_ctx* ctx, const float* rays_o, const float* rays
         // grids sized for R, every kernel takes its row count from the window's device word
         const int* map_w = pair_map + static_cast<size_t>(p) * r;
         const int* count = wcount + p;
-        neo::launch_inst_level0(near_inst, far_inst, rays_d, edges, map_w, count, R, N0, t0_c, far_c, rays_d_c, raymap, s);
-        if (int rc = neo_tp_eval_compact(ctx, 0, sc, views, rays_o, rays_d, viewdirs, t0_c, R, N0, chunk, out, raymap, count, s)) return rc;
+        neo::launch_inst_level0(near_inst, far_inst, rays_d, f.edges, map_w, count, R, f.N0, c.t0, c.far, c.rays_d, raymap, s);
         // composited WITHOUT white: the scatter adds 1 - acc to the per-instance rows, the composite below needs them without it
-        neo::launch_composite(1, out, t0_c, N0, rays_d_c, far_c, R, N0, 0, c_rgb[0], c_acc[0], c_depth[0], w0, nullptr, s, count);
-        if (neo::launch_resample(t0_c, N0, w0, u, 0, R, N0, n_fine, 0, t1_c, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
-        if (int rc = neo_tp_eval_compact(ctx, 1, sc, views, rays_o, rays_d, viewdirs, t1_c, R, N1, chunk, out, raymap, count, s)) return rc;
-        neo::launch_composite(1, out, t1_c, N1, rays_d_c, far_c, R, N1, 0, c_rgb[1], c_acc[1], c_depth[1], nullptr, nullptr, s, count);
+        if (int rc = tp_march_compact(f, a, c, raymap, count, 0)) return rc;
         for (int l = 0; l < 2; ++l)
-            neo::launch_inst_scatter(map_w, count, R, c_rgb[l], c_acc[l], c_depth[l], white, p_rgb[l], p_acc[l], p_depth[l],
+            neo::launch_inst_scatter(map_w, count, R, c.rgb[l], c.acc[l], c.depth[l], white, p_rgb[l], p_acc[l], p_depth[l],
                                      lv[l] ? lv[l]->rgb : nullptr, lv[l] ? lv[l]->acc : nullptr, lv[l] ? lv[l]->depth : nullptr, s);
     }
     for (int l = 0; l < 2; ++l)

@@ -717,6 +717,36 @@ class NeRF_TP(_HipModule):
     extras_quantiles = (0.05, 0.5, 0.95)      # at most 8, ascending, in [0, 1]
     _DEFAULT_EXTRAS_QUANTILES = (0.05, 0.5, 0.95)
 
+    def _frame_call(self, rays, chunk=None, use_grid=False):
+        """The prologue every fused frame call of this module shares (`_TpFrameCall`): the ray tensors are converted here, the
+        device context is not touched before `.run(...)`."""
+        return _TpFrameCall(self, rays, chunk, use_grid)
+
+    _LEVEL_KEYS = ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth")
+
+    @classmethod
+    def _level_out(cls, B, dev):
+        """One level's outputs of an out_depth=True frame: the six tensors by name and the TpLevelOut that points at them."""
+        t = dict(rgb=torch.empty(B, 3, device=dev), fg_rgb=torch.empty(B, 3, device=dev),
+                 bg_rgb=torch.empty(B, 3, device=dev), fg_acc=torch.empty(B, device=dev),
+                 bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
+        return t, _lib.TpLevelOut(*(t[k].data_ptr() for k in cls._LEVEL_KEYS))
+
+    @classmethod
+    def _level_tuple(cls, t):
+        return tuple(t[k] for k in cls._LEVEL_KEYS)
+
+    @staticmethod
+    def _edit_samples(t, B, n, dev, return_samples):
+        """Adds the sample rows (fg_t, fg_w, bg_s) to level dict `t` when asked for; returns the TpEditSamples over whichever of
+        its optional rows `t` holds (these and `visibility`), or None when it holds none."""
+        if return_samples:
+            t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev))
+        names = [k for k, _ in _lib.TpEditSamples._fields_]
+        if not any(k in t for k in names):
+            return None
+        return _lib.TpEditSamples(*(t[k].data_ptr() if k in t else None for k in names))
+
     def _forward_eval(self, rays, randomized, white_bkgd, chunk=None, fine_only=False):
         self._check_mode(randomized)
         extras_on = bool(self.compute_extras)
@@ -726,47 +756,30 @@ class NeRF_TP(_HipModule):
             quant = tuple(float(q) for q in self.extras_quantiles)
             if len(quant) > ops.MAX_EXTRA_QUANTILES:
                 raise ValueError("at most %d extras_quantiles, got %d" % (ops.MAX_EXTRA_QUANTILES, len(quant)))
-        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
-        rays_o = f32(raw[0], "rays_o")
-        rays_d = f32(raw[1], "rays_d")
-        viewdirs = f32(raw[2], "viewdirs")
-        dev = rays_o.device
-        ctx = self._context(dev)
-        self._ensure_scene(rays, dev)
-        if self._scene_ctx is not ctx:
-            raise _lib.NeoError("scene features were uploaded on a different device")
-        self._sync_weights(ctx)
-        self._before_call(ctx)
-        B = rays_o.shape[0]
-        host_poses, NV, focal, cx, cy = self._camera_args(rays)
-        # pixel-grid hint (render.render_rays_test / render_frame_sharded set `ray_grid` around a frame): a scheduling hint for
-        # the evaluators' tile order, bitwise-neutral; only meaningful for a call that spans whole bands of 8 image rows
-        grid = getattr(self, "ray_grid", None)
-        ctx.set_ray_grid(*(grid if grid and grid[0] % 8 == 0 and B >= 8 * grid[0] else (0, 0)))
+        call = self._frame_call(rays, chunk, use_grid=True)
+        B, dev = call.B, call.dev
         levels = []
         extras, extra_structs = [None, None], [None, None]
         eps = self.cull_background
 
         def launch():
+            ctx = call.ctx
             structs = []
             for level in range(2):
                 if level == 0 and fine_only:       # NULL level 0: the library runs the coarse launches for their densities alone
                     levels.append(None)
                     structs.append(None)
                     continue
-                t = dict(rgb=torch.empty(B, 3, device=dev), fg_rgb=torch.empty(B, 3, device=dev),
-                         bg_rgb=torch.empty(B, 3, device=dev), fg_acc=torch.empty(B, device=dev),
-                         bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
+                t, struct = self._level_out(B, dev)
                 levels.append(t)
-                structs.append(_lib.TpLevelOut(*(t[k].data_ptr() for k in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth"))))
+                structs.append(struct)
                 if extras_on:
                     e = dict(opacity=torch.empty(B, device=dev), disparity=torch.empty(B, device=dev),
                              distance_percentiles=torch.empty(B, len(quant), device=dev))
                     extras[level] = e
                     extra_structs[level] = _lib.TpExtrasOut(*(e[k].data_ptr() for k in ("opacity", "disparity", "distance_percentiles")))
-            args = (ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), B, int(chunk or max(B, 1)), host_poses, NV, focal, cx, cy,
-                    self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
-                    ctypes.byref(structs[0]) if structs[0] is not None else None, ctypes.byref(structs[1]))
+            args = call.ray_args + call.frame_args + (
+                int(bool(white_bkgd)), ctypes.byref(structs[0]) if structs[0] is not None else None, ctypes.byref(structs[1]))
             extra = []
             if extras_on:
                 tab = ops._quantile_table(quant, dev) if quant else None
@@ -781,14 +794,10 @@ class NeRF_TP(_HipModule):
                 _lib.check(ctx.lib.neo_tp_render_culled(*args, eps, extra[0].data_ptr(), ctx.stream()))
             self._after_call(ctx)
             return [v for t in levels if t is not None for v in t.values()] + extra
-        try:
-            made = self._launch_overlapped(ctx, dev, raw, (rays_o, rays_d, viewdirs), launch)
-        finally:
-            ctx.set_ray_grid(0)
+        made = call.run(launch)
         if eps is not None:
             self.last_cull_survivors = made[-1]
-        out = [None if t is None else (t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"])
-               for t in levels]
+        out = [None if t is None else self._level_tuple(t) for t in levels]
         if extras_on:
             for level, e in enumerate(extras):
                 if e is None:
@@ -824,32 +833,21 @@ class NeRF_TP(_HipModule):
         zero sample rows.  `chunk` as in forward (quirk Q1: a ray's direction index comes from its own index, B and chunk, never
         from which other rays hit).  `last_object_hits` receives the number of hit rays as a device int32 scalar that this call
         never reads.  Reads neither `cull_background` nor `ray_grid`."""
-        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
-        B = raw[0].shape[0]
+        B = rays["rays_o"].shape[0]
         raw_near = self._object_bound(rays, near_obj, "near_obj", B)
         raw_far = self._object_bound(rays, far_obj, "far_obj", B)
-        rays_o = f32(raw[0], "rays_o")
-        rays_d = f32(raw[1], "rays_d")
-        viewdirs = f32(raw[2], "viewdirs")
+        call = self._frame_call(rays, chunk)
+        dev = call.dev
         near_c = f32(raw_near, "near_obj").reshape(B)
         far_c = f32(raw_far, "far_obj").reshape(B)
-        dev = rays_o.device
         if near_c.device != dev or far_c.device != dev:
             raise ValueError("near_obj / far_obj must be on the rays' device (%s)" % (dev,))
-        ctx = self._context(dev)
-        self._ensure_scene(rays, dev)
-        if self._scene_ctx is not ctx:
-            raise _lib.NeoError("scene features were uploaded on a different device")
-        self._sync_weights(ctx)
-        self._before_call(ctx)
-        host_poses, NV, focal, cx, cy = self._camera_args(rays)
-        n0 = self.num_coarse_samples + 1
-        n1 = n0 + self.num_fine_samples
         levels = []
 
         def launch():
+            ctx = call.ctx
             structs = []
-            for n in (n0, n1):
+            for n in call.n:
                 t = dict(rgb=torch.empty(B, 3, device=dev), acc=torch.empty(B, device=dev), depth=torch.empty(B, device=dev))
                 if return_samples:
                     t["tvals"] = torch.empty(B, n, device=dev)
@@ -858,32 +856,18 @@ class NeRF_TP(_HipModule):
                                                 t["tvals"].data_ptr() if return_samples else None))
             hits = torch.empty((), dtype=torch.int32, device=dev)     # written by the compaction, never read inside the call
             _lib.check(ctx.lib.neo_tp_render_objects(
-                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(near_c), ptr(far_c), B, int(chunk or max(B, 1)), host_poses,
-                NV, focal, cx, cy, self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
+                *call.ray_args, ptr(near_c), ptr(far_c), *call.frame_args, int(bool(white_bkgd)),
                 ctypes.byref(structs[0]), ctypes.byref(structs[1]), hits.data_ptr(), ctx.stream()))
             self._after_call(ctx)
             return [v for t in levels for v in t.values()] + [hits]
-        made = self._launch_overlapped(ctx, dev, raw + (raw_near, raw_far), (rays_o, rays_d, viewdirs, near_c, far_c), launch)
+        made = call.run(launch, (raw_near, raw_far), (near_c, far_c))
         self.last_object_hits = made[-1]
         out = [(t["rgb"], t["acc"], t["depth"]) for t in levels]
         if return_samples:
             out.append((levels[0]["tvals"], levels[1]["tvals"]))
         return out
 
-
     MAX_INSTANCES = 32
-
-    @classmethod
-    def _instance_bound(cls, t, key, B, dev):
-        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
-            raise ValueError("%s must be a floating-point tensor, got %r" % (key, type(t).__name__ if not isinstance(t, torch.Tensor) else t.dtype))
-        if not (t.dim() in (2, 3) and t.shape[1] == B and (t.dim() == 2 or t.shape[2] == 1)):
-            raise ValueError("%s must have shape (K, %d) or (K, %d, 1): one row per instance, like the rays, got %s" % (key, B, B, tuple(t.shape)))
-        if t.shape[0] > cls.MAX_INSTANCES:
-            raise ValueError("%s holds %d instances, at most %d are supported" % (key, t.shape[0], cls.MAX_INSTANCES))
-        if t.device != dev:
-            raise ValueError("%s must be on the rays' device (%s), got %s" % (key, dev, t.device))
-        return t
 
     @torch.no_grad()
     def render_instances(self, rays, near_inst, far_inst, white_bkgd=True, chunk=None, per_instance=True):
@@ -907,29 +891,15 @@ class NeRF_TP(_HipModule):
                      in that order.  A ray without hits: rgb = 1 or 0, acc = depth = 0, id = -1.
         Intervals of overlapping boxes are marched independently, so density inside an overlap counts twice.
         `last_instance_pairs` receives the number of hit pairs as a device int32 scalar that this call never reads."""
-        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
-        B = raw[0].shape[0]
-        raw_near = self._instance_bound(near_inst, "near_inst", B, raw[0].device)
-        raw_far = self._instance_bound(far_inst, "far_inst", B, raw[0].device)
-        K = raw_near.shape[0]
-        if raw_far.shape[0] != K:
-            raise ValueError("near_inst holds %d instances, far_inst %d" % (K, raw_far.shape[0]))
-        rays_o = f32(raw[0], "rays_o")
-        rays_d = f32(raw[1], "rays_d")
-        viewdirs = f32(raw[2], "viewdirs")
-        near_c = f32(raw_near, "near_inst").reshape(K, B)
-        far_c = f32(raw_far, "far_inst").reshape(K, B)
-        dev = rays_o.device
-        ctx = self._context(dev)
-        self._ensure_scene(rays, dev)
-        if self._scene_ctx is not ctx:
-            raise _lib.NeoError("scene features were uploaded on a different device")
-        self._sync_weights(ctx)
-        self._before_call(ctx)
-        host_poses, NV, focal, cx, cy = self._camera_args(rays)
+        B = rays["rays_o"].shape[0]
+        K = ops._edit_bounds(near_inst, far_inst, B, rays["rays_o"].device, None)
+        call = self._frame_call(rays, chunk)
+        dev = call.dev
+        near_c, far_c = ops._edit_rows(near_inst, far_inst, K, B)
         levels = []
 
         def launch():
+            ctx = call.ctx
             structs = []
             for _ in range(2):
                 t = dict(comp_rgb=torch.empty(B, 3, device=dev), comp_acc=torch.empty(B, device=dev),
@@ -940,12 +910,11 @@ class NeRF_TP(_HipModule):
                 structs.append(_lib.TpInstanceOut(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpInstanceOut._fields_)))
             pairs = torch.empty((), dtype=torch.int32, device=dev)    # written by the compaction, never read inside the call
             _lib.check(ctx.lib.neo_tp_render_instances(
-                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(near_c), ptr(far_c), K, B, int(chunk or max(B, 1)), host_poses,
-                NV, focal, cx, cy, self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)),
+                *call.ray_args, ptr(near_c), ptr(far_c), K, *call.frame_args, int(bool(white_bkgd)),
                 ctypes.byref(structs[0]), ctypes.byref(structs[1]), pairs.data_ptr(), ctx.stream()))
             self._after_call(ctx)
             return [v for t in levels for v in t.values()] + [pairs]
-        made = self._launch_overlapped(ctx, dev, raw + (raw_near, raw_far), (rays_o, rays_d, viewdirs, near_c, far_c), launch)
+        made = call.run(launch, (near_inst, far_inst), (near_c, far_c))
         self.last_instance_pairs = made[-1]
         return dict(instances=[(t["rgb"], t["acc"], t["depth"]) for t in levels] if per_instance else None,
                     composite=[(t["comp_rgb"], t["comp_acc"], t["comp_depth"], t["instance_id"]) for t in levels])
@@ -974,54 +943,36 @@ class NeRF_TP(_HipModule):
         Returns the two level tuples of `forward(..., out_depth=True)`: [(comp_rgb, fg_rgb, bg_rgb, fg_acc, bg_lambda, comp_depth)];
         with layers each tuple gains `visibility` (L,B), the weight each layer's opacity enters the ray with; with return_samples a
         third element holds per level (fg_t, fg_w, bg_s), fg_w being the SCENE weight (exactly 0 inside a removed interval)."""
-        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
-        B = raw[0].shape[0]
-        K = ops._edit_bounds(near_inst, far_inst, B, raw[0].device, "render_edited")
+        B = rays["rays_o"].shape[0]
+        K = ops._edit_bounds(near_inst, far_inst, B, rays["rays_o"].device, "render_edited")
         scale, tints = ops.edit_table(K, density_scale, tint)
-        L = ops._layer_rows(layers, B, raw[0].device, "render_edited")
-        rays_o = f32(raw[0], "rays_o")
-        rays_d = f32(raw[1], "rays_d")
-        viewdirs = f32(raw[2], "viewdirs")
-        dev = rays_o.device
+        L = ops._layer_rows(layers, B, rays["rays_o"].device, "render_edited")
+        call = self._frame_call(rays, chunk)
+        dev = call.dev
         near_c, far_c = ops._edit_rows(near_inst, far_inst, K, B)
         layer_rows, layer_struct = ops._layer_struct(layers, L)
-        ctx = self._context(dev)
-        self._ensure_scene(rays, dev)
-        if self._scene_ctx is not ctx:
-            raise _lib.NeoError("scene features were uploaded on a different device")
-        self._sync_weights(ctx)
-        self._before_call(ctx)
-        host_poses, NV, focal, cx, cy = self._camera_args(rays)
-        n0 = self.num_coarse_samples + 1
-        n1 = n0 + self.num_fine_samples
         levels = []
 
         def launch():
+            ctx = call.ctx
             structs, sample_structs = [], []
-            for n in (n0, n1):
-                t = dict(rgb=torch.empty(B, 3, device=dev), fg_rgb=torch.empty(B, 3, device=dev),
-                         bg_rgb=torch.empty(B, 3, device=dev), fg_acc=torch.empty(B, device=dev),
-                         bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
-                structs.append(_lib.TpLevelOut(*(t[k].data_ptr() for k in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth"))))
+            for n in call.n:
+                t, struct = self._level_out(B, dev)
+                structs.append(struct)
                 if L:
                     t["visibility"] = torch.empty(L, B, device=dev)
-                if return_samples:
-                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev))
+                sample_structs.append(self._edit_samples(t, B, n, dev, return_samples))
                 levels.append(t)
-                sample_structs.append(_lib.TpEditSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpEditSamples._fields_))
-                                      if (L or return_samples) else None)
             _lib.check(ctx.lib.neo_tp_render_edited(
-                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(near_c), ptr(far_c), K, scale, tints,
-                ctypes.byref(layer_struct) if layer_struct is not None else None, L, B, int(chunk or max(B, 1)), host_poses, NV, focal,
-                cx, cy, self.num_coarse_samples, self.num_fine_samples, ctypes.byref(structs[0]), ctypes.byref(structs[1]),
+                *call.ray_args, ptr(near_c), ptr(far_c), K, scale, tints,
+                ctypes.byref(layer_struct) if layer_struct is not None else None, L, *call.frame_args,
+                ctypes.byref(structs[0]), ctypes.byref(structs[1]),
                 *(ctypes.byref(x) if x is not None else None for x in sample_structs), ctx.stream()))
             self._after_call(ctx)
             return [v for t in levels for v in t.values()]
         raw_layers = tuple(layers[k] for k in ("key", "rgb", "acc", "depth")) if L else ()
-        self._launch_overlapped(ctx, dev, raw + (near_inst, far_inst) + raw_layers,
-                                (rays_o, rays_d, viewdirs, near_c, far_c) + tuple(layer_rows), launch)
-        out = [(t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"]) + ((t["visibility"],) if L else ())
-               for t in levels]
+        call.run(launch, (near_inst, far_inst) + raw_layers, (near_c, far_c) + tuple(layer_rows))
+        out = [self._level_tuple(t) + ((t["visibility"],) if L else ()) for t in levels]
         if return_samples:
             out.append([(t["fg_t"], t["fg_w"], t["bg_s"]) for t in levels])
         return out
@@ -1049,61 +1000,82 @@ class NeRF_TP(_HipModule):
         each level in `levels` gains a seventh element dict(rgb (K+1,B,3), acc (K+1,B), depth (K+1,B), id (B,) int32); with
         return_samples a third element holds per level (fg_t, fg_w, bg_s).  ValueError - before any device access - for intervals
         whose shape, dtype, device or count does not fit, and for levels other than 0 and 1."""
-        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
-        B = raw[0].shape[0]
-        K = ops._edit_bounds(near_inst, far_inst, B, raw[0].device, "render_decomposed")
+        B = rays["rays_o"].shape[0]
+        K = ops._edit_bounds(near_inst, far_inst, B, rays["rays_o"].device, "render_decomposed")
         want = tuple(levels)
         if any(isinstance(lv, bool) or lv not in (0, 1) for lv in want):
             raise ValueError("render_decomposed: levels must be a subset of (0, 1), got %r" % (levels,))
-        rays_o = f32(raw[0], "rays_o")
-        rays_d = f32(raw[1], "rays_d")
-        viewdirs = f32(raw[2], "viewdirs")
-        dev = rays_o.device
+        call = self._frame_call(rays, chunk, use_grid=True)      # the pixel-grid hint of forward: bitwise-neutral
+        dev = call.dev
         near_c, far_c = ops._edit_rows(near_inst, far_inst, K, B)
-        ctx = self._context(dev)
-        self._ensure_scene(rays, dev)
-        if self._scene_ctx is not ctx:
-            raise _lib.NeoError("scene features were uploaded on a different device")
-        self._sync_weights(ctx)
-        self._before_call(ctx)
-        host_poses, NV, focal, cx, cy = self._camera_args(rays)
-        grid = getattr(self, "ray_grid", None)      # the pixel-grid hint of forward: bitwise-neutral
-        ctx.set_ray_grid(*(grid if grid and grid[0] % 8 == 0 and B >= 8 * grid[0] else (0, 0)))
-        n0 = self.num_coarse_samples + 1
-        n1 = n0 + self.num_fine_samples
         made = []
 
         def launch():
+            ctx = call.ctx
             structs, dec_structs, sample_structs = [], [], []
-            for lv, n in enumerate((n0, n1)):
-                t = dict(rgb=torch.empty(B, 3, device=dev), fg_rgb=torch.empty(B, 3, device=dev),
-                         bg_rgb=torch.empty(B, 3, device=dev), fg_acc=torch.empty(B, device=dev),
-                         bg_lambda=torch.empty(B, 1, device=dev), depth=torch.empty(B, device=dev))
-                structs.append(_lib.TpLevelOut(*(t[k].data_ptr() for k in ("rgb", "fg_rgb", "bg_rgb", "fg_acc", "bg_lambda", "depth"))))
+            for lv, n in enumerate(call.n):
+                t, struct = self._level_out(B, dev)
+                structs.append(struct)
                 dec = None
                 if lv in want:
                     t["decomposed"], dec = ops._decomposed_out(K, B, dev)
                 dec_structs.append(dec)
-                if return_samples:
-                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev))
+                sample_structs.append(self._edit_samples(t, B, n, dev, return_samples))
                 made.append(t)
-                sample_structs.append(_lib.TpEditSamples(t["fg_t"].data_ptr(), t["fg_w"].data_ptr(), t["bg_s"].data_ptr(), None)
-                                      if return_samples else None)
             _lib.check(ctx.lib.neo_tp_render_decomposed(
-                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(near_c), ptr(far_c), K, B, int(chunk or max(B, 1)), host_poses,
-                NV, focal, cx, cy, self.num_coarse_samples, self.num_fine_samples, ctypes.byref(structs[0]), ctypes.byref(structs[1]),
+                *call.ray_args, ptr(near_c), ptr(far_c), K, *call.frame_args, ctypes.byref(structs[0]), ctypes.byref(structs[1]),
                 *(ctypes.byref(x) if x is not None else None for x in dec_structs + sample_structs), ctx.stream()))
             self._after_call(ctx)
             return [v for t in made for x in t.values() for v in (x.values() if isinstance(x, dict) else (x,))]
-        try:
-            self._launch_overlapped(ctx, dev, raw + (near_inst, far_inst), (rays_o, rays_d, viewdirs, near_c, far_c), launch)
-        finally:
-            ctx.set_ray_grid(0)
-        out = [(t["rgb"], t["fg_rgb"], t["bg_rgb"], t["fg_acc"], t["bg_lambda"], t["depth"]) + ((t["decomposed"],) if "decomposed" in t else ())
-               for t in made]
+        call.run(launch, (near_inst, far_inst), (near_c, far_c))
+        out = [self._level_tuple(t) + ((t["decomposed"],) if "decomposed" in t else ()) for t in made]
         if return_samples:
             out.append([(t["fg_t"], t["fg_w"], t["bg_s"]) for t in made])
         return out
+
+
+class _TpFrameCall:
+    """One fused frame call of a NeRF_TP module (forward(out_depth=True), render_objects, render_instances, render_edited,
+    render_decomposed): the prologue they share and the launch around their one library call.
+
+    Construction converts the three ray tensors and touches no device context, so that a caller's own conversions and
+    ValueErrors still come first.  `run(launch, extra_raw, extra_conv)` then does the rest, in this order:
+    context, scene check, weight sync, the deferred flags of earlier calls, the host copies of the source cameras, for a
+    `use_grid` call the module's `ray_grid` hint (reset when the call is over, however it ends), and `launch()` on the call's side
+    stream and scratch lane (`_launch_overlapped`; extra_raw / extra_conv: the call's further input tensors as passed / as the
+    library reads them).  `launch` finds the context as `.ctx` and the library arguments all frame entry points start with as
+    `.ray_args` = (handle, rays_o, rays_d, viewdirs) and `.frame_args` = (B, chunk, src poses, NV, focal, cx, cy, n_coarse, n_fine)."""
+
+    def __init__(self, net, rays, chunk, use_grid):
+        self.net, self.batch, self.use_grid = net, rays, use_grid
+        self.raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
+        self.rays = (f32(self.raw[0], "rays_o"), f32(self.raw[1], "rays_d"), f32(self.raw[2], "viewdirs"))
+        self.dev = self.rays[0].device
+        self.B = self.rays[0].shape[0]
+        self.chunk = int(chunk or max(self.B, 1))
+        self.n = (net.num_coarse_samples + 1, net.num_coarse_samples + 1 + net.num_fine_samples)      # samples per ray, per level
+        self.ctx = self.ray_args = self.frame_args = None
+
+    def run(self, launch, extra_raw=(), extra_conv=()):
+        net, dev, B = self.net, self.dev, self.B
+        ctx = self.ctx = net._context(dev)
+        net._ensure_scene(self.batch, dev)
+        if net._scene_ctx is not ctx:
+            raise _lib.NeoError("scene features were uploaded on a different device")
+        net._sync_weights(ctx)
+        net._before_call(ctx)
+        self.ray_args = (ctx.handle,) + tuple(ptr(t) for t in self.rays)
+        self.frame_args = (B, self.chunk) + tuple(net._camera_args(self.batch)) + (net.num_coarse_samples, net.num_fine_samples)
+        if self.use_grid:
+            # pixel-grid hint (render.render_rays_test / render_frame_sharded set `ray_grid` around a frame): a scheduling hint for
+            # the evaluators' tile order, bitwise-neutral; only meaningful for a call that spans whole bands of 8 image rows
+            grid = getattr(net, "ray_grid", None)
+            ctx.set_ray_grid(*(grid if grid and grid[0] % 8 == 0 and B >= 8 * grid[0] else (0, 0)))
+        try:
+            return net._launch_overlapped(ctx, dev, self.raw + tuple(extra_raw), self.rays + tuple(extra_conv), launch)
+        finally:
+            if self.use_grid:
+                ctx.set_ray_grid(0)
 
 
 class PixelNeRFMLP(nn.Module):

@@ -307,20 +307,22 @@ MAX_EDIT_INSTANCES = 32
 
 def _edit_bounds(near_inst, far_inst, B, dev, who):
     """Validates near_inst / far_inst - (K,B) or (K,B,1) floating-point tensors on `dev`, K <= 32 - and returns K; nothing is
-    converted yet (_edit_rows), so that every host-side ValueError comes before the first device access."""
+    converted yet (_edit_rows), so that every host-side ValueError comes before the first device access.  `who` names the caller
+    in front of every message; None is NeRF_TP.render_instances, whose messages carry no name."""
+    pre, like = ("%s: " % who, "") if who else ("", ", like the rays")
     rows = []
     for key, t in (("near_inst", near_inst), ("far_inst", far_inst)):
         if not isinstance(t, torch.Tensor) or not t.is_floating_point():
-            raise ValueError("%s: %s must be a floating-point tensor, got %r" % (who, key, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
+            raise ValueError("%s%s must be a floating-point tensor, got %r" % (pre, key, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
         if not (t.dim() in (2, 3) and t.shape[1] == B and (t.dim() == 2 or t.shape[2] == 1)):
-            raise ValueError("%s: %s must have shape (K, %d) or (K, %d, 1): one row per instance, got %s" % (who, key, B, B, tuple(t.shape)))
+            raise ValueError("%s%s must have shape (K, %d) or (K, %d, 1): one row per instance%s, got %s" % (pre, key, B, B, like, tuple(t.shape)))
         if t.shape[0] > MAX_EDIT_INSTANCES:
-            raise ValueError("%s: %s holds %d instances, at most %d are supported" % (who, key, t.shape[0], MAX_EDIT_INSTANCES))
+            raise ValueError("%s%s holds %d instances, at most %d are supported" % (pre, key, t.shape[0], MAX_EDIT_INSTANCES))
         if t.device != dev:
-            raise ValueError("%s: %s must be on the rays' device (%s), got %s" % (who, key, dev, t.device))
+            raise ValueError("%s%s must be on the rays' device (%s), got %s" % (pre, key, dev, t.device))
         rows.append(t)
     if rows[0].shape[0] != rows[1].shape[0]:
-        raise ValueError("%s: near_inst holds %d instances, far_inst %d" % (who, rows[0].shape[0], rows[1].shape[0]))
+        raise ValueError("%snear_inst holds %d instances, far_inst %d" % (pre, rows[0].shape[0], rows[1].shape[0]))
     return rows[0].shape[0]
 
 
