@@ -463,6 +463,51 @@ int neo_tp_render_decomposed(neo_ctx* ctx, const float* rays_o, const float* ray
                              const neo_tp_decomposed_out* decomposed0, const neo_tp_decomposed_out* decomposed1,
                              const neo_tp_edit_samples* samples0, const neo_tp_edit_samples* samples1, void* stream);
 
+/* EMPTY-SPACE SKIPPING of the NeO-360 frame: a per-scene occupancy grid decides, sample by sample, which inside-sphere points the
+ * evaluators see.
+ * OCCUPANCY GRID.  G^3 cells over the world cube [-1, 1]^3; G = 8, 16 or a multiple of 32 in [32, 256].  On the device the grid is
+ * G^3 / 32 words of 32 bits: cell (ix, iy, iz) is bit lin & 31 of word lin >> 5, lin = (ix G + iy) G + iz - the bits of a contiguous
+ * bool (G,G,G) array in little-endian bit order.  The cell of a coordinate x, in fp32: i = min(max((int)floorf((x + 1.0f) *
+ * (0.5f * G)), 0), G - 1).
+ * KEEP RULE.  Sample j of ray r, at x = rays_o[r] + t[r][j] * rays_d[r] (one fp32 multiply and one fp32 add per coordinate, the
+ * evaluators' own expression), is KEPT iff the bit of (cell(x_0), cell(x_1), cell(x_2)) is set, or a coordinate of x is not finite
+ * (written as the negation of |x| < inf, so that a NaN survives to the caller), or there is no grid.
+ *
+ * neo_tp_set_occupancy copies `bits` [device, G^3 / 8 bytes] into context-owned memory; bits == NULL removes the grid.
+ * neo_tp_set_scene removes it as well: a grid describes one scene (and its source poses and weights, which the library cannot
+ * check).  neo_tp_set_skip_window: rays per window of neo_tp_render_skipping, 1 .. 65536, 0 = the default (4096); a window bounds
+ * the extra workspace at (64 + 128) bytes per (ray, sample) of one window.  Results do not depend on it. */
+int neo_tp_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, void* stream);
+int neo_tp_set_skip_window(neo_ctx* ctx, int rays);
+
+/* The KEEP RULE on caller rows: rays_o, rays_d (R,3), t (R,N) -> keep (R,N) uint8 0 / 1.  bits [device] may be NULL (no grid: all
+ * ones).  R == 0 is a valid call.  Touches no context-owned memory. */
+int neo_tp_occupancy_keep(neo_ctx* ctx, const uint32_t* bits, int G, const float* rays_o, const float* rays_d, const float* t, int R,
+                          int N, uint8_t* keep, void* stream);
+
+/* A lattice of activated densities -> the bits of a grid.  sigma [device]: (M,M,M) floats, M = G probes, 1 <= probes <= 4; entry
+ * (lx, ly, lz) belongs to cell (lx / probes, ly / probes, lz / probes).  A cell is raw-occupied iff one of its probes^3 entries is
+ * not <= threshold (so a NaN entry is occupied and reaches the caller); occupied iff a cell at most `dilate` (0 .. 4) cells away in every axis is raw-occupied; and
+ * cleared when none of its points lies inside the closed unit sphere: with h = G / 2 and n_a = i_a - h for i_a >= h, h - 1 - i_a
+ * below, iff n_x^2 + n_y^2 + n_z^2 > h^2 (integers).  bits [device]: G^3 / 8 bytes.  Touches no context-owned memory. */
+int neo_occupancy_from_sigma(neo_ctx* ctx, const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits,
+                             void* stream);
+
+/* neo_tp_render (out_depth=True semantics, the coarse level always evaluated in full) in which an inside-sphere sample that the
+ * KEEP RULE does not keep is NOT evaluated: its (rgb, sigma) row is (0, 0, 0, 0), which the composite turns into weight exactly 0.
+ * Kept samples are evaluated by the evaluators' compact launches, one point per row, and are bitwise what neo_tp_render computes
+ * for them; the composites, the level-1 resampling (on the resulting weights), the outside-sphere half (never skipped), the merge,
+ * the flags, the scratch lanes and the ray-grid hint are neo_tp_render's.  With every cell set, or no grid installed, the twelve
+ * outputs are bitwise neo_tp_render's; with no cell set fg_rgb = fg_acc = 0, bg_lambda = 1 and no inside-sphere point is evaluated.
+ * samples0 / samples1 (may be NULL, and any pointer in them): the level's fg_t, fg_w, bg_s (R,N_level), its keep mask fg_keep
+ * (R,N_level) uint8 and its inside-sphere rows fg_rows (R,N_level,4).  kept (may be NULL): int64[2] on the device, the kept
+ * samples of level 0 and level 1; nothing is read back. */
+typedef struct { float* fg_t; float* fg_w; float* bg_s; uint8_t* fg_keep; float* fg_rows; } neo_tp_skip_samples;
+int neo_tp_render_skipping(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                           const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                           const neo_tp_level_out* level0, const neo_tp_level_out* level1, const neo_tp_skip_samples* samples0,
+                           const neo_tp_skip_samples* samples1, long long* kept, void* stream);
+
 /* ---- scene encoder: pillar stage -------------------------------------------------------- */
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).
  * weights/biases [host arrays of 9 device pointers], order: depth_fc.common_branch.0 (512x518), depth_fc.common_branch.2,

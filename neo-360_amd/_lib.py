@@ -54,6 +54,10 @@ class TpDecomposedOut(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("rgb", "acc", "depth", "id")]
 
 
+class TpSkipSamples(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("fg_t", "fg_w", "bg_s", "fg_keep", "fg_rows")]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares
 SIGNATURES = {
     "neo_abi_version": (_i, []),
@@ -110,6 +114,13 @@ SIGNATURES = {
                                       ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpDecomposedOut),
                                       ctypes.POINTER(TpDecomposedOut), ctypes.POINTER(TpEditSamples), ctypes.POINTER(TpEditSamples),
                                       _vp]),
+    "neo_tp_set_occupancy": (_i, [_vp, _vp, _i, _vp]),
+    "neo_tp_set_skip_window": (_i, [_vp, _i]),
+    "neo_tp_occupancy_keep": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "neo_occupancy_from_sigma": (_i, [_vp, _vp, _i, _i, _f, _i, _vp, _vp]),
+    "neo_tp_render_skipping": (_i, [_vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i,
+                                    ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpSkipSamples),
+                                    ctypes.POINTER(TpSkipSamples), _vp, _vp]),
     "neo_enc_upload": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_enc_floorplans": (_i, [_vp, _vp, _i, _i, _i, _f, _f, c_float_p, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "neo_enc_train_tape_floats": (ctypes.c_long, [_i, _i, _i, _i]),

@@ -2,6 +2,8 @@
 // two-level, two-region render (neo360/model.py:266-581).
 #include "tp_frame.h"
 
+#include <algorithm>
+
 using namespace neo_host;
 
 namespace {
@@ -195,6 +197,41 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
     return NEO_OK;
 }
 
+// Rays per window of the skipping frame (neo_tp_set_skip_window replaces it).  A window bounds the extra workspace: a compact row
+// is 64 B in W[12] and 128 B in the direction-sum table, so 4096 rays x 385 samples are 1.58 M rows = 101 MB + 202 MB, whatever
+// the frame's size; the frame's 75 windows per level cost 5 small launches each.
+constexpr int SKIP_WINDOW_DEFAULT = 4096;
+
+// The inside-sphere evaluation of one level of a skipping frame (tp_render_dense, TpDenseOptions::skip): per window of rays,
+// classify + compact the points (occupancy.hip), ONE compact launch of the level's evaluator on single points - R = the window's
+// rows, N = 1, the identity map, the device count - and the scatter into the dense rows.  keep: the caller's (R,N) mask of the
+// level, or null: the mask then lives one window at a time in W[13].
+int tp_eval_skipping(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* fg_t, int N, float* fg_out,
+                     uint8_t* keep, long long* kept) {
+    hipStream_t s = f.s;
+    const int win = std::min(ctx->skip_window > 0 ? ctx->skip_window : SKIP_WINDOW_DEFAULT, a.R);
+    const size_t cap = static_cast<size_t>(win) * N;
+    REQUIRE(cap * 3 <= 2147483647UL, "skip window too large for 32-bit indices");
+    if (ctx->ws[12].reserve(neo::occ_rows_bytes(cap)) || (!keep && ctx->ws[13].reserve(cap))) return NEO_ERR_NOMEM;
+    neo::OccRows w;
+    w.carve(ctx->ws[12].p, cap);
+    const uint32_t* bits = ctx->occ_G ? ctx->occ_bits.as<uint32_t>() : nullptr;
+    if (kept) HIP_TRY(hipMemsetAsync(kept, 0, sizeof(long long), s));
+    neo::launch_occ_iota(w.iota, static_cast<int>(cap), s);
+    for (int r0 = 0; r0 < a.R; r0 += win) {
+        const int rays = std::min(win, a.R - r0);
+        const int P = rays * N;
+        const size_t first = static_cast<size_t>(r0) * N;
+        uint8_t* keep_win = keep ? keep + first : ctx->ws[13].as<uint8_t>();
+        neo::launch_occ_compact(a.rays_o, a.rays_d, a.viewdirs, fg_t + first, r0, rays, a.R, N, a.chunk, bits, ctx->occ_G, keep_win,
+                                w, kept, s);
+        if (int rc = tp_launch(ctx, ctx->tp[level], f.sc, f.views, w.o, w.d, w.v, w.t, nullptr, P, 1, a.chunk, w.out, s, w.iota, w.count))
+            return rc;
+        neo::launch_occ_scatter(keep_win, P, w, fg_out + first * 4, s);
+    }
+    return NEO_OK;
+}
+
 // may the level-0 launches of a frame render be density-only?  Yes when the caller takes none of the level's colours or depth
 // (fg_acc and bg_lambda are functions of sigma and stay available)
 bool level0_sigma_only(const neo_tp_level_out* level0) {
@@ -313,7 +350,10 @@ int tp_render_dense(neo_ctx* ctx, const TpFrameArgs& a, const TpDenseOptions& o)
         const neo_tp_edit_samples* so = o.samples[level];
         const neo_tp_decomposed_out* dc = o.decomposed[level];
         const bool dens = level == 0 && sigma0;
-        if (int rc = tp_launch(ctx, ctx->tp[level], f.sc, f.views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
+        if (o.skip) {
+            if (int rc = tp_eval_skipping(ctx, f, a, level, fg_t, N, fg_out, o.fg_keep[level], o.kept ? o.kept + level : nullptr)) return rc;
+            if (o.fg_rows[level]) HIP_TRY(hipMemcpyAsync(o.fg_rows[level], fg_out, r * N * 16, hipMemcpyDeviceToDevice, s));
+        } else if (int rc = tp_launch(ctx, ctx->tp[level], f.sc, f.views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
         if (int rc = tp_launch(ctx, ctx->tp[2 + level], f.sc, f.views, rays_o, rays_d, viewdirs, bg_s, far, R, N, chunk, bg_out, s, nullptr, nullptr, dens)) return rc;
         float* fg_rgb = dens ? nullptr : (lo && lo->fg_rgb) ? lo->fg_rgb : s_fg_rgb;
         float* bg_rgb = dens ? nullptr : (lo && lo->bg_rgb) ? lo->bg_rgb : s_bg_rgb;
@@ -439,6 +479,7 @@ int neo_tp_set_scene(neo_ctx* ctx, const float* plane_xz, const float* plane_xy,
     ctx->scene.fy_sign = -1.0f;                                       // NeRF_TP projects with (f, -f) (model.py:243)
     ctx->scene_epoch += 1;
     ctx->scene_ready = true;
+    ctx->occ_G = 0;      // an occupancy grid describes one scene
     return check_launch();
 }
 
@@ -502,6 +543,31 @@ int neo_tp_render_extras(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     o.n_u = n_u;
     o.extras[0] = extras0;
     o.extras[1] = extras1;
+    return tp_render_dense(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, o);
+}
+
+// The dense frame with a full level 0 whose inside-sphere launches skip the samples the installed occupancy grid clears
+// (tp_eval_skipping); every other launch of the list is neo_tp_render's.
+int neo_tp_render_skipping(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                           const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                           const neo_tp_level_out* level0, const neo_tp_level_out* level1, const neo_tp_skip_samples* samples0,
+                           const neo_tp_skip_samples* samples1, long long* kept, void* stream) {
+    ENTER(ctx);
+    TpDenseOptions o;
+    o.level[0] = level0;
+    o.level[1] = level1;
+    o.skip = true;
+    o.kept = kept;
+    const neo_tp_skip_samples* given[2] = {samples0, samples1};
+    neo_tp_edit_samples rows[2];
+    for (int l = 0; l < 2; ++l) {
+        if (!given[l]) continue;
+        rows[l] = {given[l]->fg_t, given[l]->fg_w, given[l]->bg_s, nullptr};
+        o.samples[l] = &rows[l];
+        o.fg_keep[l] = given[l]->fg_keep;
+        o.fg_rows[l] = given[l]->fg_rows;
+    }
+    if (kept && R == 0 && chunk >= 1) HIP_TRY(hipMemsetAsync(kept, 0, 2 * sizeof(long long), static_cast<hipStream_t>(stream)));
     return tp_render_dense(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, o);
 }
 

@@ -220,9 +220,14 @@ struct neo_ctx {
     int pix_preproject = 1;            // PixelNeRF: gather the latent pre-projected through pts_linears.0 (mlp_pix_h.hip)
     std::map<int, neo_host::DevBuf> quantiles;                    // n_new -> linspace(0, fl32(1-2^-32), n_new)
     std::map<std::pair<int, uint64_t>, neo_host::DevBuf> edges;   // (n, near/far bits) -> level-0 t row
-    neo_host::DevBuf ws_sets[LANES][12];                          // render workspaces (grow-only), one set per lane
+    neo_host::DevBuf ws_sets[LANES][14];                          // render workspaces (grow-only), one set per lane
     neo_host::DevBuf* ws = ws_sets[0];                            // the current lane's set
     neo_host::DevBuf boxes;                                       // neo_aabb_multi: box frames + bounds
+    // neo_tp_set_occupancy: the scene's occupancy grid as bits (occupancy.hip: GRID LAYOUT), occ_G = 0: none installed;
+    // neo_tp_set_skip_window: rays per window of neo_tp_render_skipping (0: the default of api_tp.hip)
+    neo_host::DevBuf occ_bits;
+    int occ_G = 0;
+    int skip_window = 0;
     // pillar stage of the scene encoder (neo_enc_*): packed weights, biases (6x512), scorer heads (3x512), workspaces
     neo_host::MlpSlot enc;
     float enc_head_b[3] = {0.f, 0.f, 0.f};

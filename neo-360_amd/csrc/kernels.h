@@ -427,4 +427,28 @@ void launch_composite_layers(const float* rgbsigma, const float* t, const float*
 void launch_tp_decompose(const float* rgbsigma, const float* t, const float* weights, const float* near_inst, const float* far_inst,
                          int K, int R, int N, const float* bg_lambda, float* rgb, float* acc, float* depth, int* id, hipStream_t s);
 
+// occupancy.hip - empty-space skipping of neo_tp_render_skipping (include/neo360_hip.h: OCCUPANCY GRID, KEEP RULE)
+// keep (R,N) uint8 = the KEEP RULE at x = rays_o + t rays_d; bits null: everything is kept
+void launch_occ_keep(const float* rays_o, const float* rays_d, const float* t, int R, int N, const uint32_t* bits, int G, uint8_t* keep,
+                     hipStream_t s);
+// One window's compact rows, `cap` of them, in one buffer of occ_rows_bytes(cap): row k is ONE kept point - the origin, direction and
+// t of its ray, the view direction of its quirk-Q1 ray, dst = its point index in the window - and out its (rgb, sigma) row; iota =
+// the identity map of the evaluator's compact launch; count the device word; totals the compaction's per-workgroup sums.
+struct OccRows {
+    float *out, *o, *d, *v, *t;
+    int *dst, *iota, *count, *totals;
+    void carve(void* base, size_t cap);
+};
+size_t occ_rows_bytes(size_t cap);
+void launch_occ_iota(int* map, int n, hipStream_t s);
+// classify (into keep_win, the window's (rays, N) rows of the mask) and compact the points of rays r0 .. r0 + rays - 1 of R: kept
+// points in ascending point order, *w.count of them, also added to *kept_sum when not null.  Two launches, no atomics.
+void launch_occ_compact(const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_win, int r0, int rays, int R,
+                        int N, int chunk, const uint32_t* bits, int G, uint8_t* keep_win, const OccRows& w, long long* kept_sum,
+                        hipStream_t s);
+// out_win (P,4): w.out at the point's rank where kept, zeros where skipped (w.totals as launch_occ_compact left them)
+void launch_occ_scatter(const uint8_t* keep_win, int P, const OccRows& w, float* out_win, hipStream_t s);
+// sigma (G probes)^3 activated densities -> G^3 / 32 words: any probe > threshold, dilation, unit-sphere clip
+void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s);
+
 }  // namespace neo

@@ -3,7 +3,7 @@
 //   TpFrame::begin      the call preamble - argument, scene and slot checks, this call's scene descriptor, N0 / N1, the constant
 //                       tables, the lane ordering scope;
 //   tp_render_dense     the dense two-level launch list on all R rays, inside and outside the sphere (neo_tp_render,
-//                       neo_tp_render_extras, neo_tp_render_edited, neo_tp_render_decomposed);
+//                       neo_tp_render_extras, neo_tp_render_edited, neo_tp_render_decomposed, neo_tp_render_skipping);
 //   tp_march_compact    the two-level inside-sphere march on compact rows under a device count (neo_tp_render_objects, every
 //                       window of neo_tp_render_instances).
 //
@@ -91,6 +91,13 @@ struct TpDenseOptions {
     const neo_tp_decomposed_out* decomposed[2] = {nullptr, nullptr};      // k_tp_decompose behind the inside-sphere composite
     int K_dec = 0;
     const neo_tp_edit_samples* samples[2] = {nullptr, nullptr};          // copies of the level's sample rows and scene weights
+    // skipping (occupancy.hip): the inside-sphere launch of each level becomes, per window of rays, classify + compact, one compact
+    // launch of single points, scatter; fg_keep / fg_rows (may be null): the level's keep mask (R,N) and rgb/sigma rows (R,N,4);
+    // kept (may be null): int64[2] on the device, the kept points per level
+    bool skip = false;
+    uint8_t* fg_keep[2] = {nullptr, nullptr};
+    float* fg_rows[2] = {nullptr, nullptr};
+    long long* kept = nullptr;
 };
 
 // the caller has entered the context (ENTER) and checked its own counts

@@ -464,6 +464,9 @@ class NeRF_TP(_HipModule):
         self.last_cull_survivors = None      # int32 device tensor: rays of the last culled call that kept their background
         self.last_object_hits = None         # int32 device tensor: rays of the last render_objects call that had a box interval
         self.last_instance_pairs = None      # int32 device tensor: hit (instance, ray) pairs of the last render_instances call
+        self._occupancy = None               # the installed occupancy grid (set_occupancy): bool (G,G,G) on the device, and its context
+        self._occ_ctx = None
+        self.last_skip_kept = None           # int64[2] device tensor: kept inside-sphere samples per level of the last render_skipping call
 
     @property
     def cull_background(self):
@@ -501,6 +504,7 @@ class NeRF_TP(_HipModule):
         # (a failing upload must not leave a fingerprint that names the new tensors next to the old copy)
         self._scene_src = None
         self._scene_ctx = None
+        self._occupancy = self._occ_ctx = None      # an occupancy grid describes one scene (neo_tp_set_scene drops the device copy)
         self._scene_key = None        # whoever uploads through an attached encoder records its own key AFTER this call (_ensure_scene);
                                       # an upload from anywhere else (a training step's gather_features) must not leave an eval key behind
         if preproject is not None:
@@ -1031,6 +1035,128 @@ class NeRF_TP(_HipModule):
         out = [self._level_tuple(t) + ((t["decomposed"],) if "decomposed" in t else ()) for t in made]
         if return_samples:
             out.append([(t["fg_t"], t["fg_w"], t["bg_s"]) for t in made])
+        return out
+
+
+    # ---- empty-space skipping ------------------------------------------------------------------------------------------------
+
+    # rays per window of render_skipping (None: the library's default, 4096): a window bounds the extra workspace at about 190 bytes
+    # per (ray, sample) of ONE window; results do not depend on it
+    skip_window = None
+
+    @property
+    def occupancy(self):
+        """The installed occupancy grid as a bool (G,G,G) device tensor (a copy), or None."""
+        return None if self._occupancy is None else self._occupancy.clone()
+
+    @torch.no_grad()
+    def set_occupancy(self, grid):
+        """Installs (or, with None, removes) the occupancy grid `render_skipping` reads: a bool (G,G,G) tensor on any device over
+        the world cube [-1, 1]^3, indexed [ix, iy, iz]; G is 8, 16 or a multiple of 32 in [32, 256].  ValueError - before any device
+        access - for another shape, dtype or G.  The grid is copied to the module's device (its parameters') and, as bits, into the
+        library context.  `set_scene` removes it, because a grid describes ONE scene; it equally belongs to the source poses the
+        scene is looked up with and to the weights of the two inside-sphere MLPs, which the module cannot check: install a new grid
+        (`build_occupancy`) whenever either changes.  `forward` and every other call ignore it."""
+        if grid is None:
+            if self._occ_ctx is not None:
+                _lib.check(self._occ_ctx.lib.neo_tp_set_occupancy(self._occ_ctx.handle, None, 0, self._occ_ctx.stream()))
+            self._occupancy = self._occ_ctx = None
+            return
+        G = ops._check_occupancy(grid, "set_occupancy")
+        dev = next(self.parameters()).device
+        ctx = self._context(dev)
+        occ = grid.detach().to(dev).contiguous().clone()
+        bits = ops.pack_occupancy(occ)
+        _lib.check(ctx.lib.neo_tp_set_occupancy(ctx.handle, ptr(bits), G, ctx.stream()))
+        self._occupancy, self._occ_ctx = occ, ctx
+
+    @torch.no_grad()
+    def _occupancy_sigma(self, rays, resolution, probes, points_per_piece=1 << 22):
+        """max(sigma of slot 0, sigma of slot 1) on the (resolution * probes)^3 lattice of `ops.occupancy_lattice`, its columns
+        evaluated as rays by `eval_mlp` in pieces of at most points_per_piece points.  `rays` supplies the source cameras."""
+        dev = rays["rays_o"].device
+        M = resolution * probes
+        c, o, d = ops.occupancy_lattice(resolution, probes, dev)
+        per_ray = ("rays_o", "rays_d", "viewdirs")
+        sigma = torch.empty(M * M, M, device=dev)
+        step = max(1, points_per_piece // M)
+        for i in range(0, M * M, step):
+            part = {k: v for k, v in rays.items() if k not in per_ray}
+            part.update(rays_o=o[i:i + step], rays_d=d[i:i + step], viewdirs=d[i:i + step])
+            t = c[None, :].expand(part["rays_o"].shape[0], M).contiguous()
+            s0 = self.eval_mlp(0, part, t)[..., 3]
+            s1 = self.eval_mlp(1, part, t)[..., 3]
+            sigma[i:i + step] = torch.maximum(s0, s1)
+        return sigma.reshape(M, M, M)
+
+    @torch.no_grad()
+    def build_occupancy(self, rays, resolution, sigma_threshold, probes=2, dilate=1):
+        """Builds, installs and returns the occupancy grid of the current scene: both inside-sphere MLPs (slots 0 and 1) are
+        evaluated on the (resolution * probes)^3 lattice of cell sub-centres, a cell is occupied iff the larger of the two
+        densities at one of its probes is not <= sigma_threshold, the result is dilated by `dilate` cells over the 26-neighbourhood
+        and cells without a point inside the unit sphere are cleared (`ops.occupancy_from_sigma`).  `rays` is a batch of this scene
+        (its source cameras are what the lookups use; its own rays are not read).
+        sigma_threshold has no default: nobody has measured one on trained weights.  It reads as an opacity - a sample of density
+        sigma over a step delta has alpha = 1 - exp(-sigma * delta), and delta is about far / 128 at level 0 of the reference's
+        counts - so a threshold of 0.01 / delta skips only samples that would be less than 1 % opaque, provided the probes see
+        the density at all: anything thinner than a probe spacing, 2 / (resolution * probes), can be missed, which is what
+        `dilate` is for.  ValueError, before any device access, for a bad resolution, probes, dilate or threshold."""
+        G, probes, dilate = ops._check_build(resolution, sigma_threshold, probes, dilate, "build_occupancy")
+        sigma = self._occupancy_sigma(rays, G, probes)
+        grid = ops.occupancy_from_sigma(sigma, G, sigma_threshold, probes, dilate, ctx=self._context(sigma.device))
+        self.set_occupancy(grid)
+        return grid
+
+    @torch.no_grad()
+    def render_skipping(self, rays, chunk=None, return_samples=False):
+        """`forward(rays, False, False, near, far, out_depth=True, chunk=chunk)` in which the inside-sphere samples that fall into
+        clear cells of the installed occupancy grid are not evaluated (neo_tp_render_skipping).  At both levels a sample at
+        x = o + t d is kept iff its cell is set or a coordinate of x is not finite (`ops.occupancy_keep`); a skipped sample's
+        (rgb, sigma) row is zero, so its weight is exactly 0, and everything downstream - the composite, the level-1 resampling from
+        the resulting weights, the outside-sphere half (never skipped), the merge - is `forward`'s on those rows.  Kept samples are
+        bitwise `forward`'s; with an all-ones grid so is the whole result.  Reads neither `cull_background` nor `compute_extras`;
+        `ray_grid` as `forward`.  NeoError when no grid is installed.
+
+        Returns the two level tuples of `forward(..., out_depth=True)`; with return_samples a third element holds per level
+        (fg_t, fg_w, bg_s, fg_keep (B,N) bool) - and, with return_samples="rows", fg_rows (B,N,4) behind them.
+        `self.last_skip_kept` (int64[2], on the device) holds the kept samples per level; nothing is read back."""
+        if self._occupancy is None:
+            raise _lib.NeoError("no occupancy grid installed: call set_occupancy(...) or build_occupancy(...) first")
+        call = self._frame_call(rays, chunk, use_grid=True)
+        B, dev = call.B, call.dev
+        levels = []
+        kept = []
+
+        def launch():
+            ctx = call.ctx
+            if self._occupancy is None or self._occ_ctx is not ctx:
+                raise _lib.NeoError("the occupancy grid does not belong to this scene and device: install it again")
+            self._set_mode(ctx, "_skip_window", "neo_tp_set_skip_window", int(self.skip_window or 0))
+            structs, sample_structs = [], []
+            for n in call.n:
+                t, struct = self._level_out(B, dev)
+                structs.append(struct)
+                if return_samples:
+                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev),
+                             fg_keep=torch.empty(B, n, dtype=torch.bool, device=dev))
+                    if return_samples == "rows":
+                        t["fg_rows"] = torch.empty(B, n, 4, device=dev)
+                    sample_structs.append(_lib.TpSkipSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpSkipSamples._fields_)))
+                else:
+                    sample_structs.append(None)
+                levels.append(t)
+            kept.append(torch.empty(2, dtype=torch.int64, device=dev))
+            _lib.check(ctx.lib.neo_tp_render_skipping(
+                *call.ray_args, *call.frame_args, ctypes.byref(structs[0]), ctypes.byref(structs[1]),
+                *(ctypes.byref(x) if x is not None else None for x in sample_structs), kept[0].data_ptr(), ctx.stream()))
+            self._after_call(ctx)
+            return [v for t in levels for v in t.values()] + kept
+        call.run(launch)
+        self.last_skip_kept = kept[0]
+        out = [self._level_tuple(t) for t in levels]
+        if return_samples:
+            names = ("fg_t", "fg_w", "bg_s", "fg_keep") + (("fg_rows",) if return_samples == "rows" else ())
+            out.append([tuple(t[k] for k in names) for t in levels])
         return out
 
 

@@ -477,3 +477,105 @@ def composite_layers(rgbsigma, t, rays_d, t_far, layers, ctx=None):
                                             ctypes.byref(struct) if struct is not None else None, L, ptr(rgb), ptr(acc), ptr(depth),
                                             ptr(w), ptr(lam), ptr(vis) if L else None, ctx.stream()))
     return dict(rgb=rgb, acc=acc, depth=depth, weights=w, bg_lambda=lam, visibility=vis)
+
+
+def occupancy_resolution_ok(G):
+    """The resolutions an occupancy grid may have: 8 and 16 (tests), or a multiple of 32 in [32, 256]."""
+    return isinstance(G, int) and not isinstance(G, bool) and (G in (8, 16) or (32 <= G <= 256 and G % 32 == 0))
+
+
+def _check_occupancy(occ, who):
+    """ValueError unless occ is a bool (G,G,G) tensor of a supported G; returns G.  Touches no device."""
+    if not isinstance(occ, torch.Tensor) or occ.dtype != torch.bool:
+        raise ValueError("%s: the occupancy grid must be a bool tensor, got %r" % (who, occ.dtype if isinstance(occ, torch.Tensor) else type(occ).__name__))
+    if occ.dim() != 3 or not (occ.shape[0] == occ.shape[1] == occ.shape[2]):
+        raise ValueError("%s: the occupancy grid must have shape (G, G, G), got %s" % (who, tuple(occ.shape)))
+    G = int(occ.shape[0])
+    if not occupancy_resolution_ok(G):
+        raise ValueError("%s: G must be 8, 16 or a multiple of 32 in [32, 256], got %d" % (who, G))
+    return G
+
+
+def pack_occupancy(occ):
+    """bool (G,G,G) -> int32 (G^3 / 32,) on the same device, the layout the library reads (include/neo360_hip.h, OCCUPANCY GRID):
+    cell (ix, iy, iz) is bit lin & 31 of word lin >> 5, lin = (ix G + iy) G + iz."""
+    _check_occupancy(occ, "pack_occupancy")
+    b = occ.contiguous().reshape(-1, 32).to(torch.int64)
+    words = (b << torch.arange(32, dtype=torch.int64, device=occ.device)).sum(dim=-1)
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)           # the same 32 bits as a signed word
+    return words.to(torch.int32)
+
+
+def unpack_occupancy(words, G):
+    """The inverse of pack_occupancy: int32 (G^3 / 32,) -> bool (G,G,G)."""
+    if not occupancy_resolution_ok(G):
+        raise ValueError("unpack_occupancy: G must be 8, 16 or a multiple of 32 in [32, 256], got %r" % (G,))
+    if not isinstance(words, torch.Tensor) or words.dtype != torch.int32 or words.numel() != G ** 3 // 32:
+        raise ValueError("unpack_occupancy: expected %d int32 words" % (G ** 3 // 32))
+    w = words.reshape(-1, 1).to(torch.int64)
+    return ((w >> torch.arange(32, dtype=torch.int64, device=words.device)) & 1).to(torch.bool).reshape(G, G, G)
+
+
+@torch.no_grad()
+def occupancy_keep(occ, rays_o, rays_d, t, ctx=None):
+    """The KEEP RULE of `NeRF_TP.render_skipping` on caller rows (neo_tp_occupancy_keep): occ bool (G,G,G) on any device, or None
+    for "no grid"; rays_o, rays_d (B,3) and t (B,N) on the GPU.  Sample j of ray b, at x = rays_o[b] + t[b, j] * rays_d[b] in fp32,
+    is kept iff the cell of x - per axis min(max(floor((x + 1) * (G / 2)), 0), G - 1), in fp32 - is set, or a coordinate of x is
+    not finite, or occ is None.  Returns (B,N) bool."""
+    if occ is not None:
+        _check_occupancy(occ, "occupancy_keep")
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or not t.is_floating_point():
+        raise ValueError("occupancy_keep: t must be a floating-point (B, N) tensor")
+    B, N = t.shape
+    for name, v in (("rays_o", rays_o), ("rays_d", rays_d)):
+        if not isinstance(v, torch.Tensor) or tuple(v.shape) != (B, 3) or v.device != t.device:
+            raise ValueError("occupancy_keep: %s must be a (%d, 3) tensor on the device of t" % (name, B))
+    if N < 1:
+        raise ValueError("occupancy_keep: at least one sample per ray")
+    rays_o, rays_d, t = f32(rays_o, "rays_o"), f32(rays_d, "rays_d"), f32(t, "t")
+    ctx = _ctx(t, ctx)
+    bits = pack_occupancy(occ.to(t.device)) if occ is not None else None
+    keep = torch.empty(B, N, dtype=torch.bool, device=t.device)
+    _lib.check(ctx.lib.neo_tp_occupancy_keep(ctx.handle, ptr(bits), int(occ.shape[0]) if occ is not None else 0, ptr(rays_o),
+                                             ptr(rays_d), ptr(t), B, N, keep.data_ptr(), ctx.stream()))
+    return keep
+
+
+def occupancy_lattice(resolution, probes, device="cpu"):
+    """The probe positions of `NeRF_TP.build_occupancy`: the M = resolution * probes sub-centres -1 + (l + 1/2) * 2 / M of one axis
+    (fp64, rounded to fp32), and the lattice as rays - column (lx, ly) is the ray o = (c[lx], c[ly], 0), d = (0, 0, 1) sampled at
+    t = c, so that o + t d is the lattice point exactly.  Returns (c (M,), rays_o (M^2,3), rays_d (M^2,3))."""
+    M = int(resolution) * int(probes)
+    c = (-1.0 + (torch.arange(M, dtype=torch.float64) + 0.5) * (2.0 / M)).float().to(device)
+    rays_o = torch.stack([c[:, None].expand(M, M), c[None, :].expand(M, M), torch.zeros(M, M, device=device)], dim=-1).reshape(M * M, 3)
+    rays_d = torch.tensor([0.0, 0.0, 1.0], device=device).expand(M * M, 3).contiguous()
+    return c, rays_o.contiguous(), rays_d
+
+
+@torch.no_grad()
+def occupancy_from_sigma(sigma, resolution, sigma_threshold, probes=2, dilate=1, ctx=None):
+    """A lattice of activated densities -> a bool (G,G,G) grid (neo_occupancy_from_sigma).  sigma: (M,M,M) on the GPU, M =
+    resolution * probes, entry (lx, ly, lz) a probe of cell (lx // probes, ly // probes, lz // probes).  A cell is occupied iff a
+    probe of a cell within `dilate` cells of it in every axis is not <= sigma_threshold (a NaN density is occupied), and cleared
+    when no point of it lies inside the unit sphere."""
+    G, probes, dilate = _check_build(resolution, sigma_threshold, probes, dilate, "occupancy_from_sigma")
+    M = G * probes
+    if not isinstance(sigma, torch.Tensor) or tuple(sigma.shape) != (M, M, M) or not sigma.is_floating_point():
+        raise ValueError("occupancy_from_sigma: sigma must be a floating-point (%d, %d, %d) tensor" % (M, M, M))
+    sigma = f32(sigma, "sigma")
+    ctx = _ctx(sigma, ctx)
+    bits = torch.empty(G ** 3 // 32, dtype=torch.int32, device=sigma.device)
+    _lib.check(ctx.lib.neo_occupancy_from_sigma(ctx.handle, ptr(sigma), G, probes, float(sigma_threshold), dilate, ptr(bits), ctx.stream()))
+    return unpack_occupancy(bits, G)
+
+
+def _check_build(resolution, sigma_threshold, probes, dilate, who):
+    import math
+    if not occupancy_resolution_ok(resolution):
+        raise ValueError("%s: resolution must be 8, 16 or a multiple of 32 in [32, 256], got %r" % (who, resolution))
+    for name, v, lo, hi in (("probes", probes, 1, 4), ("dilate", dilate, 0, 4)):
+        if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+            raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (who, name, lo, hi, v))
+    if isinstance(sigma_threshold, bool) or not isinstance(sigma_threshold, (int, float)) or math.isnan(float(sigma_threshold)):
+        raise ValueError("%s: sigma_threshold must be a number, got %r" % (who, sigma_threshold))
+    return int(resolution), int(probes), int(dilate)

@@ -338,6 +338,28 @@ def render_decomposed_rays(model, batch, RTs=None, chunk=1024, check=True, on_ra
 
 
 @torch.no_grad()
+def render_skipping_rays(model, batch, chunk=1024, check=True, on_range="retry_f32"):
+    """Frame of a NeRF_TP module with empty space skipped: the fine level of `model.render_skipping` (which needs an occupancy
+    grid: `model.build_occupancy` / `model.set_occupancy`) on every ray of `batch` in one library call, with the reference chunk
+    size passed down - the place of the reference's chunk loop.  Returns dict(rgb (R,3), depth (R,), acc (R,)) plus
+    `kept_fraction`, a (2,) float64 DEVICE tensor: the share of inside-sphere samples evaluated at level 0 and level 1 (reading it
+    synchronises, the call does not), and `target` / `instance_mask` passed through.  With an all-ones grid rgb / depth are bitwise
+    render_rays_test's.  check / on_range: the flag read, range-guard retry and latch of render_rays_test (the same code path)."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("render_skipping_rays renders NeRF_TP modules, got %r" % type(model))
+
+    def once():
+        res = model.render_skipping(batch, chunk=chunk)
+        fine = res[1]
+        R = fine[0].shape[0]
+        n0 = model.num_coarse_samples + 1
+        kept = model.last_skip_kept.double()          # scalar divisors travel as kernel arguments: no copy, no wait
+        frac = torch.stack([kept[0] / float(max(R * n0, 1)), kept[1] / float(max(R * (n0 + model.num_fine_samples), 1))])
+        return dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=frac)
+    return _render_guarded(model, batch, once, check, on_range)
+
+
+@torch.no_grad()
 def render_frame_sharded(model, batch, world, rank, chunk=1024, white_bkgd=False, near=0.2, far=3.0, group=None,
                          gather=True, train_frac=1.0, n_rays=None, out=None, reuse=False, check=True, always_gather=False,
                          info=None, image_width=None):
