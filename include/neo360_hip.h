@@ -508,6 +508,61 @@ int neo_tp_render_skipping(neo_ctx* ctx, const float* rays_o, const float* rays_
                            const neo_tp_level_out* level0, const neo_tp_level_out* level1, const neo_tp_skip_samples* samples0,
                            const neo_tp_skip_samples* samples1, long long* kept, void* stream);
 
+/* EARLY RAY TERMINATION of the NeO-360 frame: a ray's inside-sphere march stops once its transmittance has fallen below eps, and
+ * the outside-sphere half is not evaluated for rays that are opaque at both levels.  No per-scene artefact, no trained threshold.
+ * STOP RULE.  A level's N inside-sphere samples are cut into SEGMENTS of `segment` samples, `segment` a positive multiple of 64; the
+ * last segment may be shorter.  64 because the inside-sphere composite (neo_composite mode 1) scans its transmittance product in
+ * rounds of 64 samples and carries an fp64 product `carry` between rounds: the transmittance it assigns to the first sample of a
+ * round is exactly (float)carry.  At a boundary b that is a multiple of 64, "the transmittance in front of sample b" is therefore a
+ * quantity the composite itself defines, bit for bit; it depends only on rows [0, b) and on t[b].  The march forms carry with the
+ * composite's own expressions - alpha = alpha(sigma * (delta * |d|)), keep = (1 - alpha) + 1e-10f, the 64-lane inclusive product scan
+ * in fp64, carry *= the round's last lane - so its value IS the composite's.
+ * Segment 0 is always evaluated.  Segment k >= 1 of a ray is evaluated iff every earlier boundary b satisfied !((float)carry_b < eps)
+ * - a negation, so a NaN keeps marching (as in the culled call).  stop[r] = the number of leading samples evaluated: N or a segment
+ * boundary.  A sample at or behind stop is NOT evaluated and its (rgb, sigma) row is (0, 0, 0, 0); the composite gives it weight
+ * exactly 0 and leaves the product unchanged (1.0f + 1e-10f == 1.0f).  The evaluated samples are a prefix, so their weights are
+ * bitwise neo_tp_render's, and a stopped ray's bg_lambda is the transmittance at stop (< eps).
+ * LEVELS.  Level 1 follows the rule.  Level 0 follows it only with coarse != 0; otherwise its inside-sphere launch is the plain dense
+ * one (ray-patch order, density-only when no level-0 colour or depth is asked for).  coarse != 0 changes the level-0 weights behind
+ * the stop from "less than eps in total" to 0, so the level-1 positions move: NO bound is claimed for that mode.
+ * BACKGROUND.  The launch order is neo_tp_render_culled's: the foreground of both levels first; a ray's two outside-sphere
+ * evaluations run iff !(bg_lambda_0 < eps) || !(bg_lambda_1 < eps) on the returned lambdas; the survivors go through that call's
+ * compact path; a culled ray gets rgb = fg_rgb, bg_rgb = 0, depth = fg_depth.
+ * eps in [0, 1).  eps == 0 stops and culls nothing: all twelve outputs are bitwise neo_tp_render's.  A ray that never stops and is
+ * not culled is bitwise neo_tp_render's at any eps.
+ * BOUND (coarse == 0, level 1; L = the returned bg_lambda < eps of a stopped ray, F = the plain frame's bg_lambda <= L).  With
+ * T_{i+1} = T_i (1 - alpha_i + 1e-10), a weight is w_i = alpha_i T_i = T_i - T_{i+1} + 1e-10 T_i, so the skipped weights sum to
+ * S = L - F + 1e-10 sum T_i <= (L - F) + 1024e-10 L.  Colours lie in (-0.001, 1.001); the background colour B is a sum of weights
+ * (<= 1 + 1e-7) times such colours.  A surviving ray changes by (L - F) B - sum_skipped w_i c_i, a sum of S-weighted differences
+ * B - c_i with |B - c_i| < 1.002 (1 + 1e-7); a culled ray by -sum_skipped w_i c_i - F B, at most 1.001 (1 + 1e-7) (S + F).  Either
+ * way |rgb change| < 1.0021 L per channel in real arithmetic; the constant 1.003 leaves 0.0009 L for the fp32 rounding of the two
+ * sums being compared (about 1e-7), which covers it wherever L > 2e-4 - below that the change is at the plain frame's own rounding.
+ * Depth: inside positions are <= t_far, the background depth is a sum of weights times inverse radii in [0, 1], and the two terms of
+ * the change have opposite signs (survivor) or sum to <= t_far (L - F) + F (culled): |depth change| <= max(t_far, 1) (1 + 1e-7) L,
+ * which is below the (t_far + 1.001) L the tests assert.
+ * Sphere-miss assertions cover every ray.  A sample that is not evaluated takes no part in the fp16 range check.  white_bkgd does
+ * not exist here (ignored by neo_tp_render).  No call synchronises the device.  An installed occupancy grid is not read; the
+ * ray-grid hint is taken by a dense level-0 launch only (compact launches never take it).
+ * Windows: a point list (one segment of the alive rays of one window) has at most
+ * skip_window x N_level rows - neo_tp_set_skip_window's bound and workspace - so a window holds skip_window N_level / segment rays;
+ * results do not depend on it.
+ * samples0 / samples1 (may be NULL, and any pointer in them): the level's fg_t, fg_w, bg_s (R,N_level; level-1 bg_s rows of culled
+ * rays are zero), stop (R) int32 and its inside-sphere rows fg_rows (R,N_level,4).  kept (may be NULL): int64[2] on the device, the
+ * evaluated inside-sphere samples per level (= sum of stop).  survivors_out (may be NULL): int on the device, the rays whose
+ * background ran. */
+typedef struct { float* fg_t; float* fg_w; float* bg_s; int* stop; float* fg_rows; } neo_tp_term_samples;
+int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                              const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                              const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps, int segment, int coarse,
+                              const neo_tp_term_samples* samples0, const neo_tp_term_samples* samples1, long long* kept,
+                              int* survivors_out, void* stream);
+
+/* The STOP RULE on caller rows: rgbsigma (R,N,4), t (R,N), rays_d (R,3), t_far (R) -> stop (R) int32, the samples a march over
+ * these rows evaluates, and trans (R), the fp32 transmittance at the stop ((float)carry there; bg_lambda of the composite when
+ * stop == N).  The kernel is the frame's.  R == 0 is a valid call.  Touches no context-owned memory. */
+int neo_tp_termination_stops(neo_ctx* ctx, const float* rgbsigma, const float* t, const float* rays_d, const float* t_far, int R, int N,
+                             float eps, int segment, int* stop, float* trans, void* stream);
+
 /* ---- scene encoder: pillar stage -------------------------------------------------------- */
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).
  * weights/biases [host arrays of 9 device pointers], order: depth_fc.common_branch.0 (512x518), depth_fc.common_branch.2,

@@ -232,6 +232,57 @@ int tp_eval_skipping(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int l
     return NEO_OK;
 }
 
+// Per-ray state of a terminating level in W[13]: [carry fp64 R | trans fp32 R | stop int R | the alive compaction of one window]
+struct TpTermState {
+    double* carry;
+    float* trans;
+    int* stop;
+    int* cws;
+    static size_t bytes(size_t r, int win) { return r * 16 + neo::cull_ws_ints(win) * sizeof(int); }
+    void carve(void* base, size_t r) {
+        carry = static_cast<double*>(base);
+        trans = reinterpret_cast<float*>(carry + r);
+        stop = reinterpret_cast<int*>(trans + r);
+        cws = stop + r;
+    }
+};
+
+// The inside-sphere evaluation of one level of a terminating frame (neo_tp_render_terminating; include/neo360_hip.h: STOP RULE) into
+// zero-filled dense rows.  Per window of rays and per segment: compact the alive rays (launch_cull_compact on the running
+// transmittance: !(trans < eps), ascending ray order, the count on the device), emit their point rows of the segment, ONE compact
+// launch of the level's evaluator on single points (as tp_eval_skipping), scatter, advance.  A point list has at most
+// skip_window x N rows - the bound, the buffer (W[12]) and the knob of the skipping frame - so a window holds skip_window N / segment
+// rays.  st.stop: samples marched per ray; *kept: their sum.
+int tp_eval_terminating(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* fg_t, const float* far, int N,
+                        float* fg_out, float eps, int segment, const TpTermState& st, int win, long long* kept) {
+    hipStream_t s = f.s;
+    const int seg = std::min(segment, N);
+    const size_t cap = static_cast<size_t>(win) * seg;
+    if (ctx->ws[12].reserve(neo::occ_rows_bytes(cap))) return NEO_ERR_NOMEM;
+    neo::OccRows w;
+    w.carve(ctx->ws[12].p, cap);
+    HIP_TRY(hipMemsetAsync(fg_out, 0, static_cast<size_t>(a.R) * N * 16, s));
+    neo::launch_term_init(st.trans, st.stop, a.R, 0, kept, 0, s);
+    neo::launch_occ_iota(w.iota, static_cast<int>(cap), s);
+    for (int r0 = 0; r0 < a.R; r0 += win) {
+        const int rays = std::min(win, a.R - r0);
+        for (int b0 = 0; b0 < N; b0 += segment) {
+            const int len = std::min(segment, N - b0);
+            const int P = rays * len;
+            neo::launch_cull_compact(st.trans + r0, st.trans + r0, rays, eps, st.cws, nullptr, s);
+            const int* map_w = neo::cull_map_of(st.cws, rays);      // the workspace's layout follows the window's ray count
+            const int* count_w = neo::cull_count_of(st.cws, rays);
+            neo::launch_term_emit(a.rays_o, a.rays_d, a.viewdirs, fg_t, map_w, count_w, r0, rays, a.R, N, b0, len, a.chunk, w, kept, s);
+            if (int rc = tp_launch(ctx, ctx->tp[level], f.sc, f.views, w.o, w.d, w.v, w.t, nullptr, P, 1, a.chunk, w.out, s, w.iota, w.count))
+                return rc;
+            neo::launch_term_scatter(w, P, fg_out, s);
+            neo::launch_term_advance(fg_out, fg_t, a.rays_d, far, N, b0, b0 + len, segment, eps, map_w, count_w, rays, r0, st.carry,
+                                     st.trans, st.stop, s);
+        }
+    }
+    return NEO_OK;
+}
+
 // may the level-0 launches of a frame render be density-only?  Yes when the caller takes none of the level's colours or depth
 // (fg_acc and bg_lambda are functions of sigma and stay available)
 bool level0_sigma_only(const neo_tp_level_out* level0) {
@@ -659,6 +710,115 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
     if (level1 && (level1->rgb || level1->depth || level1->bg_rgb))
         neo::launch_tp_merge_culled(L[1].fg_rgb, L[1].fg_depth, L[1].lam, c_bg_rgb, c_bg_depth, slot, R, level1->rgb, level1->depth,
                                     L[1].bg_rgb, s);
+    return check_launch();
+}
+
+// Early ray termination: neo_tp_render_culled's launch order (the foreground of both levels first, the background on the rays that
+// still let light through) in which the inside-sphere march of level 1 - with `coarse` also of level 0 - stops by the STOP RULE.
+int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                              const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                              const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps, int segment, int coarse,
+                              const neo_tp_term_samples* samples0, const neo_tp_term_samples* samples1, long long* kept,
+                              int* survivors_out, void* stream) {
+    ENTER(ctx);
+    const TpFrameArgs a{rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream};
+    TpFrame::Own own;
+    if (!(eps >= 0.0f && eps < 1.0f)) own.after_counts = "eps must lie in [0, 1)";
+    else if (!(segment >= 64 && segment % 64 == 0)) own.after_counts = "segment must be a positive multiple of 64";
+    TpFrame f;      // a dense level-0 launch keeps the ray-patch order; compact launches drop it (tp_launch)
+    if (int rc = f.begin(ctx, a, true, true, own)) return rc;
+    hipStream_t s = f.s;
+    if (f.empty) {
+        if (survivors_out) HIP_TRY(hipMemsetAsync(survivors_out, 0, sizeof(int), s));
+        if (kept) HIP_TRY(hipMemsetAsync(kept, 0, 2 * sizeof(long long), s));
+        return NEO_OK;
+    }
+    const int N0 = f.N0, N1 = f.N1;
+    const neo::TpScene& sc = f.sc;
+    const neo::TpViews& views = f.views;
+    const size_t r = static_cast<size_t>(R);
+    REQUIRE(r * N1 <= 2147483647UL, "too many points for 32-bit indices");
+
+    // workspaces: neo_tp_render_culled's (W[0..10]), the point rows of one segment launch in W[12], the per-ray march state in W[13]
+    auto* W = ctx->ws;
+    const int skip_window = ctx->skip_window > 0 ? ctx->skip_window : SKIP_WINDOW_DEFAULT;
+    const int win_of[2] = {static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N0 / segment))),
+                           static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N1 / segment)))};
+    REQUIRE(static_cast<size_t>(std::max(win_of[0], win_of[1])) * std::min(segment, N1) * 3 <= 2147483647UL,
+            "skip window too large for 32-bit indices");
+    TpDenseRows rows;
+    if (rows.reserve(W, r, N0, N1) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)) ||
+        W[13].reserve(TpTermState::bytes(r, std::max(win_of[0], win_of[1]))))
+        return NEO_ERR_NOMEM;
+    auto [far, fg_t0, bg_s0, fg_out, bg_out, fg_w0, bg_w0, fg_t1, bg_s1] = rows;
+    TpTermState st;
+    st.carve(W[13].p, r);
+    float* scratch = W[9].as<float>();    // as neo_tp_render_culled
+    float* c_bg_rgb = scratch + r * 18;
+    float* c_bg_depth = scratch + r * 21;
+    int* cws = W[10].as<int>();
+    const int* map = neo::cull_map_of(cws, R);
+    const int* slot = neo::cull_slot_of(cws, R);
+    const int* count = neo::cull_count_of(cws, R);
+
+    neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);       // sphere-miss assertions: every ray, stopped, culled or not
+    neo::launch_tp_level0(far, f.edges, R, N0, f.near, fg_t0, bg_s0, s);
+    const bool sigma0 = level0_sigma_only(level0);
+    const neo_tp_level_out* los[2] = {level0, level1};
+    const neo_tp_term_samples* sos[2] = {samples0, samples1};
+    struct LevelFg { float* fg_rgb; float* fg_depth; float* fg_acc; float* lam; float* bg_rgb; } L[2];
+    for (int level = 0; level < 2; ++level) {
+        const neo_tp_level_out* lo = los[level];
+        float* b = scratch + r * 9 * level;
+        L[level] = {(lo && lo->fg_rgb) ? lo->fg_rgb : b, b + r * 3, (lo && lo->fg_acc) ? lo->fg_acc : b + r * 4,
+                    (lo && lo->bg_lambda) ? lo->bg_lambda : b + r * 5, lo ? lo->bg_rgb : nullptr};
+    }
+    // foreground of both levels first
+    for (int level = 0; level < 2; ++level) {
+        const int N = level == 0 ? N0 : N1;
+        const float* fg_t = level == 0 ? fg_t0 : fg_t1;
+        const neo_tp_term_samples* so = sos[level];
+        const bool dens = level == 0 && sigma0;
+        if (level == 1 || coarse) {
+            if (int rc = tp_eval_terminating(ctx, f, a, level, fg_t, far, N, fg_out, eps, segment, st, win_of[level],
+                                             kept ? kept + level : nullptr))
+                return rc;
+        } else {
+            if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
+            neo::launch_term_init(nullptr, st.stop, R, N, kept, static_cast<long long>(r) * N, s);
+        }
+        float* fg_w = level == 0 ? fg_w0 : (so ? so->fg_w : nullptr);
+        neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, dens ? nullptr : L[level].fg_rgb, L[level].fg_acc,
+                              dens ? nullptr : L[level].fg_depth, fg_w, L[level].lam, s);
+        if (so) {
+            const size_t row = r * N * sizeof(float);
+            if (so->fg_t) HIP_TRY(hipMemcpyAsync(so->fg_t, fg_t, row, hipMemcpyDeviceToDevice, s));
+            if (so->fg_w && level == 0) HIP_TRY(hipMemcpyAsync(so->fg_w, fg_w0, row, hipMemcpyDeviceToDevice, s));
+            if (so->stop) HIP_TRY(hipMemcpyAsync(so->stop, st.stop, r * sizeof(int), hipMemcpyDeviceToDevice, s));
+            if (so->fg_rows) HIP_TRY(hipMemcpyAsync(so->fg_rows, fg_out, row * 4, hipMemcpyDeviceToDevice, s));
+        }
+        if (level == 0 && neo::launch_resample(fg_t0, N0, fg_w0, f.u, 0, R, N0, n_fine, 0, fg_t1, s))
+            return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    }
+
+    neo::launch_cull_compact(L[0].lam, L[1].lam, R, eps, cws, survivors_out, s);
+
+    // background on the survivors, exactly as neo_tp_render_culled
+    if (int rc = tp_launch(ctx, ctx->tp[2], sc, views, rays_o, rays_d, viewdirs, bg_s0, far, R, N0, chunk, bg_out, s, map, count, sigma0)) return rc;
+    neo::launch_composite(2, bg_out, bg_s0, N0, nullptr, nullptr, R, N0, 0, sigma0 ? nullptr : c_bg_rgb, nullptr,
+                          sigma0 ? nullptr : c_bg_depth, bg_w0, nullptr, s, count);
+    if (neo::launch_resample(bg_s0, N0, bg_w0, f.u, 0, R, N0, n_fine, 1, bg_s1, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    if (level0 && (level0->rgb || level0->depth || level0->bg_rgb))
+        neo::launch_tp_merge_culled(L[0].fg_rgb, L[0].fg_depth, L[0].lam, c_bg_rgb, c_bg_depth, slot, R, level0->rgb, level0->depth,
+                                    L[0].bg_rgb, s);
+    if (int rc = tp_launch(ctx, ctx->tp[3], sc, views, rays_o, rays_d, viewdirs, bg_s1, far, R, N1, chunk, bg_out, s, map, count)) return rc;
+    neo::launch_composite(2, bg_out, bg_s1, N1, nullptr, nullptr, R, N1, 0, c_bg_rgb, nullptr, c_bg_depth, nullptr, nullptr, s, count);
+    if (level1 && (level1->rgb || level1->depth || level1->bg_rgb))
+        neo::launch_tp_merge_culled(L[1].fg_rgb, L[1].fg_depth, L[1].lam, c_bg_rgb, c_bg_depth, slot, R, level1->rgb, level1->depth,
+                                    L[1].bg_rgb, s);
+    // bg_s: level 0 is one row for every ray (k_tp_level0); level 1 exists for the survivors only: a culled ray's row is zero
+    if (samples0 && samples0->bg_s) HIP_TRY(hipMemcpyAsync(samples0->bg_s, bg_s0, r * N0 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (samples1 && samples1->bg_s) neo::launch_term_rows_by_slot(bg_s1, slot, R, N1, samples1->bg_s, s);
     return check_launch();
 }
 

@@ -451,4 +451,21 @@ void launch_occ_scatter(const uint8_t* keep_win, int P, const OccRows& w, float*
 // sigma (G probes)^3 activated densities -> G^3 / 32 words: any probe > threshold, dilation, unit-sphere clip
 void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s);
 
+// terminate.hip - early ray termination of neo_tp_render_terminating (include/neo360_hip.h: STOP RULE)
+// trans (may be null) = 1, stop = stop_value for R rays; *kept (may be null) = kept_value
+void launch_term_init(float* trans, int* stop, int R, int stop_value, long long* kept, long long kept_value, hipStream_t s);
+// the point rows (OccRows, as launch_occ_compact leaves them; dst = the point's index in the level's dense (R,N) rows) of samples
+// b0 .. b0 + len - 1 of rays r0 + map[k], k < *count <= rays; *w.count = *count len, also added to *kept_sum when not null
+void launch_term_emit(const float* rays_o, const float* rays_d, const float* viewdirs, const float* t, const int* map, const int* count,
+                      int r0, int rays, int R, int N, int b0, int len, int chunk, const OccRows& w, long long* kept_sum, hipStream_t s);
+// out[w.dst[p]] = w.out[p] for p < *w.count; P: the host's bound of the row count
+void launch_term_scatter(const OccRows& w, long P, float* out, hipStream_t s);
+// the STOP RULE over samples b0 .. b_end - 1 (whole segments) of rays r0 + map[k], k < *count (map / count null: rays 0 .. n_rays - 1):
+// carry (fp64 per ray; may be null when b0 == 0 and nothing continues), trans = (float)carry at the stop, stop = samples marched
+void launch_term_advance(const float* rgbsigma, const float* t, const float* rays_d, const float* t_far, int N, int b0, int b_end,
+                         int segment, float eps, const int* map, const int* count, int n_rays, int r0, double* carry, float* trans,
+                         int* stop, hipStream_t s);
+// dst (R,N) = src_c row slot[ray], zeros where slot[ray] < 0
+void launch_term_rows_by_slot(const float* src_c, const int* slot, int R, int N, float* dst, hipStream_t s);
+
 }  // namespace neo

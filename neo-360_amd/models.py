@@ -467,6 +467,8 @@ class NeRF_TP(_HipModule):
         self._occupancy = None               # the installed occupancy grid (set_occupancy): bool (G,G,G) on the device, and its context
         self._occ_ctx = None
         self.last_skip_kept = None           # int64[2] device tensor: kept inside-sphere samples per level of the last render_skipping call
+        self.last_terminate_kept = None      # int64[2] device tensor: evaluated inside-sphere samples per level of the last render_terminating call
+        self.last_terminate_survivors = None # int32 device tensor: rays of that call whose background ran
 
     @property
     def cull_background(self):
@@ -1156,6 +1158,73 @@ class NeRF_TP(_HipModule):
         out = [self._level_tuple(t) for t in levels]
         if return_samples:
             names = ("fg_t", "fg_w", "bg_s", "fg_keep") + (("fg_rows",) if return_samples == "rows" else ())
+            out.append([tuple(t[k] for k in names) for t in levels])
+        return out
+
+    # ---- early ray termination -----------------------------------------------------------------------------------------------
+
+    @torch.no_grad()
+    def render_terminating(self, rays, eps, chunk=None, segment=64, coarse=False, return_samples=False, fine_only=False):
+        """`forward(rays, False, False, near, far, out_depth=True, chunk=chunk)` in which a ray's inside-sphere march stops once its
+        transmittance has fallen below `eps`, and the outside-sphere half is not evaluated for rays that are opaque at both levels
+        (neo_tp_render_terminating; include/neo360_hip.h: STOP RULE).  The samples of a level are cut into segments of `segment`
+        (a positive multiple of 64); segment 0 is always evaluated, a later one iff the transmittance at every earlier segment
+        boundary - the composite's own value there, bit for bit (`ops.termination_stops`) - was not below eps.  A sample behind
+        the stop is not evaluated: its (rgb, sigma) row is zero and its weight exactly 0; the evaluated prefix is bitwise `forward`'s,
+        and a stopped ray's bg_lambda is the transmittance at its stop.  A ray's background runs iff one of its two bg_lambda is
+        not below eps; a culled ray gets rgb = fg_rgb, bg_rgb = 0, depth = fg_depth.
+
+        Level 1 follows the rule; level 0 is evaluated in full unless coarse=True.  With coarse=False a stopped ray's level-1 rgb
+        differs from `forward`'s by at most 1.003 * bg_lambda per channel and its depth by at most (t_far + 1.001) * bg_lambda, with
+        the returned bg_lambda < eps; a ray that never stops and is not culled is bitwise `forward`'s, and so is everything at
+        eps = 0.  coarse=True also zeroes the level-0 weights behind the stop, which moves the level-1 sample positions: NO error
+        bound is claimed for that mode.  Needs no per-scene artefact.  Reads none of `cull_background`, `compute_extras` or an
+        installed occupancy grid; `ray_grid` as `forward`; `skip_window` bounds the workspace as in `render_skipping`.
+        ValueError, before any device access, for eps outside [0, 1) or NaN, or a segment that is not a positive multiple of 64.
+
+        Returns the two level tuples of `forward(..., out_depth=True)` (fine_only=True: None for level 0, whose colours are then not
+        computed); with return_samples a third element holds per level (fg_t, fg_w, bg_s, stop (B,) int32) - and, with
+        return_samples="rows", fg_rows (B,N,4) behind them; the level-1 bg_s row of a culled ray is zero.
+        `self.last_terminate_kept` (int64[2]: evaluated inside-sphere samples per level) and `self.last_terminate_survivors`
+        (int32: rays whose background ran) stay on the device; nothing is read back."""
+        eps, segment = ops._check_termination(eps, segment, "render_terminating")
+        call = self._frame_call(rays, chunk, use_grid=True)
+        B, dev = call.B, call.dev
+        levels = []
+        counts = []
+
+        def launch():
+            ctx = call.ctx
+            self._set_mode(ctx, "_skip_window", "neo_tp_set_skip_window", int(self.skip_window or 0))
+            structs, sample_structs = [], []
+            for level, n in enumerate(call.n):
+                if level == 0 and fine_only:
+                    t, struct = {}, None
+                else:
+                    t, struct = self._level_out(B, dev)
+                structs.append(struct)
+                if return_samples:
+                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev),
+                             stop=torch.empty(B, dtype=torch.int32, device=dev))
+                    if return_samples == "rows":
+                        t["fg_rows"] = torch.empty(B, n, 4, device=dev)
+                    sample_structs.append(_lib.TpTermSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpTermSamples._fields_)))
+                else:
+                    sample_structs.append(None)
+                levels.append(t)
+            counts.append(torch.empty(2, dtype=torch.int64, device=dev))
+            counts.append(torch.empty((), dtype=torch.int32, device=dev))
+            _lib.check(ctx.lib.neo_tp_render_terminating(
+                *call.ray_args, *call.frame_args, *(ctypes.byref(x) if x is not None else None for x in structs), eps, segment,
+                int(bool(coarse)), *(ctypes.byref(x) if x is not None else None for x in sample_structs), counts[0].data_ptr(),
+                counts[1].data_ptr(), ctx.stream()))
+            self._after_call(ctx)
+            return [v for t in levels for v in t.values()] + counts
+        call.run(launch)
+        self.last_terminate_kept, self.last_terminate_survivors = counts
+        out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
+        if return_samples:
+            names = ("fg_t", "fg_w", "bg_s", "stop") + (("fg_rows",) if return_samples == "rows" else ())
             out.append([tuple(t[k] for k in names) for t in levels])
         return out
 

@@ -579,3 +579,41 @@ def _check_build(resolution, sigma_threshold, probes, dilate, who):
     if isinstance(sigma_threshold, bool) or not isinstance(sigma_threshold, (int, float)) or math.isnan(float(sigma_threshold)):
         raise ValueError("%s: sigma_threshold must be a number, got %r" % (who, sigma_threshold))
     return int(resolution), int(probes), int(dilate)
+
+
+def _check_termination(eps, segment, who):
+    """eps in [0, 1) (NaN refused), segment a positive multiple of 64: ValueError before any device access."""
+    import math
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or math.isnan(float(eps)) or not 0.0 <= float(eps) < 1.0:
+        raise ValueError("%s: eps must be a number in [0, 1), got %r" % (who, eps))
+    if isinstance(segment, bool) or not isinstance(segment, int) or segment < 64 or segment % 64 != 0:
+        raise ValueError("%s: segment must be a positive multiple of 64, got %r" % (who, segment))
+    return float(eps), int(segment)
+
+
+@torch.no_grad()
+def termination_stops(rgbsigma, t, rays_d, t_far, eps, segment=64, ctx=None):
+    """The STOP RULE of `NeRF_TP.render_terminating` on caller rows (neo_tp_termination_stops): rgbsigma (B,N,4), t (B,N), rays_d
+    (B,3), t_far (B,) or (B,1) on the GPU - what `eval_mlp` returns for the inside-sphere samples of a level and what the
+    inside-sphere `composite` reads.  The N samples are cut into segments of `segment` (a positive multiple of 64); a march evaluates
+    segment 0, and segment k >= 1 iff at every earlier boundary b the transmittance in front of sample b - the composite's own
+    (float)carry, formed with its expressions - was not below eps (a NaN keeps marching).  Returns (stop (B,) int32, the number of
+    leading samples such a march evaluates, and trans (B,) float32, the transmittance at the stop).  stop.sum() / (B N) is the share
+    of a level's inside-sphere work the rule would keep: the tool to measure it on trained weights without the frame call."""
+    eps, segment = _check_termination(eps, segment, "termination_stops")
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or not t.is_floating_point() or t.shape[1] < 1:
+        raise ValueError("termination_stops: t must be a floating-point (B, N) tensor, N >= 1")
+    B, N = t.shape
+    if not isinstance(rgbsigma, torch.Tensor) or tuple(rgbsigma.shape) != (B, N, 4) or rgbsigma.device != t.device:
+        raise ValueError("termination_stops: rgbsigma must be a (%d, %d, 4) tensor on the device of t" % (B, N))
+    if not isinstance(rays_d, torch.Tensor) or tuple(rays_d.shape) != (B, 3) or rays_d.device != t.device:
+        raise ValueError("termination_stops: rays_d must be a (%d, 3) tensor on the device of t" % B)
+    if not isinstance(t_far, torch.Tensor) or tuple(t_far.shape) not in ((B,), (B, 1)) or t_far.device != t.device:
+        raise ValueError("termination_stops: t_far must be a (%d,) or (%d, 1) tensor on the device of t" % (B, B))
+    rgbsigma, t, rays_d, t_far = f32(rgbsigma, "rgbsigma"), f32(t, "t"), f32(rays_d, "rays_d"), f32(t_far.reshape(B), "t_far")
+    ctx = _ctx(t, ctx)
+    stop = torch.empty(B, dtype=torch.int32, device=t.device)
+    trans = torch.empty(B, device=t.device)
+    _lib.check(ctx.lib.neo_tp_termination_stops(ctx.handle, ptr(rgbsigma), ptr(t), ptr(rays_d), ptr(t_far), B, N, eps, segment,
+                                                stop.data_ptr(), trans.data_ptr(), ctx.stream()))
+    return stop, trans

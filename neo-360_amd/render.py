@@ -360,6 +360,29 @@ def render_skipping_rays(model, batch, chunk=1024, check=True, on_range="retry_f
 
 
 @torch.no_grad()
+def render_terminating_rays(model, batch, eps, chunk=1024, segment=64, coarse=False, check=True, on_range="retry_f32"):
+    """Frame of a NeRF_TP module with early ray termination: the fine level of `model.render_terminating(batch, eps, ...)` on every
+    ray of `batch` in one library call, with the reference chunk size passed down.  Returns dict(rgb (R,3), depth (R,), acc (R,))
+    plus `kept_fraction`, a (2,) float64 DEVICE tensor - the share of inside-sphere samples evaluated at level 0 and level 1 - and
+    `culled_fraction`, a float64 DEVICE scalar - the share of rays whose outside-sphere half did not run (reading either
+    synchronises, the call does not) - and `target` / `instance_mask` passed through.  With eps = 0 rgb / depth are bitwise
+    render_rays_test's.  check / on_range: the flag read, range-guard retry and latch of render_rays_test (the same code path)."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("render_terminating_rays renders NeRF_TP modules, got %r" % type(model))
+
+    def once():
+        res = model.render_terminating(batch, eps, chunk=chunk, segment=segment, coarse=coarse)
+        fine = res[1]
+        R = fine[0].shape[0]
+        n0 = model.num_coarse_samples + 1
+        kept = model.last_terminate_kept.double()          # scalar divisors travel as kernel arguments: no copy, no wait
+        frac = torch.stack([kept[0] / float(max(R * n0, 1)), kept[1] / float(max(R * (n0 + model.num_fine_samples), 1))])
+        culled = 1.0 - model.last_terminate_survivors.double() / float(max(R, 1))
+        return dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=frac, culled_fraction=culled)
+    return _render_guarded(model, batch, once, check, on_range)
+
+
+@torch.no_grad()
 def render_frame_sharded(model, batch, world, rank, chunk=1024, white_bkgd=False, near=0.2, far=3.0, group=None,
                          gather=True, train_frac=1.0, n_rays=None, out=None, reuse=False, check=True, always_gather=False,
                          info=None, image_width=None):
