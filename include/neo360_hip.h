@@ -557,6 +557,38 @@ int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* ra
                               const neo_tp_term_samples* samples0, const neo_tp_term_samples* samples1, long long* kept,
                               int* survivors_out, void* stream);
 
+/* ACCELERATED FRAME: neo_tp_render_terminating that also obeys the installed occupancy grid - the KEEP RULE and the STOP RULE together.
+ * LEVEL 1, AND LEVEL 0 WITH coarse != 0.  Sample j of ray r is evaluated iff it satisfies the KEEP RULE of the installed grid AND
+ * j < stop[r].  stop is the STOP RULE applied to the level's rows in which the samples that are not kept are (0, 0, 0, 0): a zero row
+ * leaves the composite's fp64 carry alone (1.0f + 1e-10f == 1.0f), so stop is neo_tp_termination_stops on the masked rows, bit for
+ * bit.  Segment 0 is always marched (its kept samples evaluated), `segment` is a positive multiple of 64, a NaN transmittance marches
+ * on.  A sample that is not evaluated has a zero row and weight exactly 0; an evaluated one is bitwise neo_tp_render's for its
+ * position.
+ * LEVEL 0 WITH coarse == 0 obeys the grid only, exactly as level 0 of neo_tp_render_skipping (stop = N_0).
+ * BACKGROUND AND LAUNCH ORDER are neo_tp_render_terminating's: the foreground of both levels first; a ray's two outside-sphere
+ * evaluations run iff !(bg_lambda_0 < eps) || !(bg_lambda_1 < eps), through the same compact path; a culled ray gets rgb = fg_rgb,
+ * bg_rgb = 0, depth = fg_depth.
+ * NO GRID INSTALLED: the KEEP RULE keeps everything and every output is bitwise neo_tp_render_terminating's (level 0 without
+ * `coarse` is then that call's plain dense launch in ray-patch order).  eps == 0: every output is bitwise neo_tp_render_skipping's
+ * with the same grid.  Both: bitwise neo_tp_render.
+ * BOUND (coarse == 0, level 1), against neo_tp_render_skipping with the same grid: level 0, and therefore the level-1 positions and
+ * the keep masks, are identical in the two calls, and the argument of the BOUND above only uses that the rows behind the stop
+ * become zero - it holds with "the plain frame" read as the skipping frame: |rgb change| <= 1.003 bg_lambda per channel and
+ * |depth change| <= (t_far + 1.001) bg_lambda, with the returned bg_lambda < eps of a stopped ray.  Nothing is claimed for coarse != 0,
+ * and nothing against neo_tp_render (that is the grid's own error, which the library cannot bound).
+ * Windows and workspace: the terminating frame's, plus one byte per candidate of a segment launch and one int per 1024 of them; a
+ * point list still has at most skip_window x N_level rows.  neo_tp_set_scene drops the grid: the next call is the terminating frame.
+ * No call synchronises the device.
+ * samples0 / samples1 (may be NULL, and any pointer in them): as neo_tp_term_samples, plus fg_keep (R,N_level) uint8, the KEEP RULE
+ * on the WHOLE row, samples behind the stop included (all ones without a grid): the evaluated set is fg_keep & (j < stop).
+ * kept: int64[2], the evaluated inside-sphere samples per level.  survivors_out: the rays whose background ran. */
+typedef struct { float* fg_t; float* fg_w; float* bg_s; int* stop; uint8_t* fg_keep; float* fg_rows; } neo_tp_accel_samples;
+int neo_tp_render_accelerated(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                              const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                              const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps, int segment, int coarse,
+                              const neo_tp_accel_samples* samples0, const neo_tp_accel_samples* samples1, long long* kept,
+                              int* survivors_out, void* stream);
+
 /* The STOP RULE on caller rows: rgbsigma (R,N,4), t (R,N), rays_d (R,3), t_far (R) -> stop (R) int32, the samples a march over
  * these rows evaluates, and trans (R), the fp32 transmittance at the stop ((float)carry there; bg_lambda of the composite when
  * stop == N).  The kernel is the frame's.  R == 0 is a valid call.  Touches no context-owned memory. */

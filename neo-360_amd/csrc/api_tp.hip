@@ -232,18 +232,21 @@ int tp_eval_skipping(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int l
     return NEO_OK;
 }
 
-// Per-ray state of a terminating level in W[13]: [carry fp64 R | trans fp32 R | stop int R | the alive compaction of one window]
+// Per-ray state of a terminating level in W[13]: [carry fp64 R | trans fp32 R | stop int R | the alive compaction of one window |
+// with a grid (neo_tp_render_accelerated): one keep byte per candidate of one segment launch]
 struct TpTermState {
     double* carry;
     float* trans;
     int* stop;
     int* cws;
-    static size_t bytes(size_t r, int win) { return r * 16 + neo::cull_ws_ints(win) * sizeof(int); }
-    void carve(void* base, size_t r) {
+    uint8_t* keep;
+    static size_t bytes(size_t r, int win, size_t candidates = 0) { return r * 16 + neo::cull_ws_ints(win) * sizeof(int) + candidates; }
+    void carve(void* base, size_t r, int win = 0) {
         carry = static_cast<double*>(base);
         trans = reinterpret_cast<float*>(carry + r);
         stop = reinterpret_cast<int*>(trans + r);
         cws = stop + r;
+        keep = reinterpret_cast<uint8_t*>(cws + neo::cull_ws_ints(win));
     }
 };
 
@@ -252,9 +255,11 @@ struct TpTermState {
 // transmittance: !(trans < eps), ascending ray order, the count on the device), emit their point rows of the segment, ONE compact
 // launch of the level's evaluator on single points (as tp_eval_skipping), scatter, advance.  A point list has at most
 // skip_window x N rows - the bound, the buffer (W[12]) and the knob of the skipping frame - so a window holds skip_window N / segment
-// rays.  st.stop: samples marched per ray; *kept: their sum.
+// rays.  st.stop: samples marched per ray; *kept: their sum.  bits / G (tp_eval_accelerated below; NULL here): the emit step keeps
+// only the samples that the grid keeps, and *kept counts those.
 int tp_eval_terminating(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* fg_t, const float* far, int N,
-                        float* fg_out, float eps, int segment, const TpTermState& st, int win, long long* kept) {
+                        float* fg_out, float eps, int segment, const TpTermState& st, int win, long long* kept,
+                        const uint32_t* bits = nullptr, int G = 0) {
     hipStream_t s = f.s;
     const int seg = std::min(segment, N);
     const size_t cap = static_cast<size_t>(win) * seg;
@@ -272,7 +277,11 @@ int tp_eval_terminating(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, in
             neo::launch_cull_compact(st.trans + r0, st.trans + r0, rays, eps, st.cws, nullptr, s);
             const int* map_w = neo::cull_map_of(st.cws, rays);      // the workspace's layout follows the window's ray count
             const int* count_w = neo::cull_count_of(st.cws, rays);
-            neo::launch_term_emit(a.rays_o, a.rays_d, a.viewdirs, fg_t, map_w, count_w, r0, rays, a.R, N, b0, len, a.chunk, w, kept, s);
+            if (bits)
+                neo::launch_acc_compact(a.rays_o, a.rays_d, a.viewdirs, fg_t, map_w, count_w, r0, rays, a.R, N, b0, len, a.chunk, bits, G,
+                                        st.keep, w, kept, s);
+            else
+                neo::launch_term_emit(a.rays_o, a.rays_d, a.viewdirs, fg_t, map_w, count_w, r0, rays, a.R, N, b0, len, a.chunk, w, kept, s);
             if (int rc = tp_launch(ctx, ctx->tp[level], f.sc, f.views, w.o, w.d, w.v, w.t, nullptr, P, 1, a.chunk, w.out, s, w.iota, w.count))
                 return rc;
             neo::launch_term_scatter(w, P, fg_out, s);
@@ -281,6 +290,18 @@ int tp_eval_terminating(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, in
         }
     }
     return NEO_OK;
+}
+
+// tp_eval_terminating on the samples that the grid `bits` keeps (neo_tp_render_accelerated; include/neo360_hip.h: ACCELERATED FRAME):
+// the window and segment loop above - ONE loop, not a copy - whose emit step is the fused classify + compact of accelerate.hip over
+// the segment's candidates.  A skipped sample stays a zero row of the zero-filled dense rows, which is what k_term_advance and the
+// composite read: the stops are the STOP RULE on the masked rows.  The workgroup-total prefix of the compaction is linear in the
+// workgroups of ONE segment launch, at most skip_window x N / 1024 of them - the bound of tp_eval_skipping's windows.  bits == NULL
+// (no grid): the terminating path itself, launch for launch.  *kept: the evaluated samples.
+int tp_eval_accelerated(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* fg_t, const float* far, int N,
+                        float* fg_out, float eps, int segment, const TpTermState& st, int win, const uint32_t* bits, int G,
+                        long long* kept) {
+    return tp_eval_terminating(ctx, f, a, level, fg_t, far, N, fg_out, eps, segment, st, win, kept, bits, G);
 }
 
 // may the level-0 launches of a frame render be density-only?  Yes when the caller takes none of the level's colours or depth
@@ -715,13 +736,14 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
 
 // Early ray termination: neo_tp_render_culled's launch order (the foreground of both levels first, the background on the rays that
 // still let light through) in which the inside-sphere march of level 1 - with `coarse` also of level 0 - stops by the STOP RULE.
-int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
-                              const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
-                              const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps, int segment, int coarse,
-                              const neo_tp_term_samples* samples0, const neo_tp_term_samples* samples1, long long* kept,
-                              int* survivors_out, void* stream) {
-    ENTER(ctx);
-    const TpFrameArgs a{rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream};
+// The one driver of neo_tp_render_terminating (use_occ = false: an installed grid is not read, bits stays NULL and every launch below
+// is that call's own) and of neo_tp_render_accelerated (use_occ = true: with a grid installed the marches also obey the KEEP RULE -
+// tp_eval_accelerated - and a level 0 without `coarse` is tp_eval_skipping).  The caller has entered the context.
+static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
+                              float eps, int segment, int coarse, const neo_tp_accel_samples* samples0,
+                              const neo_tp_accel_samples* samples1, long long* kept, int* survivors_out, bool use_occ) {
+    const float *rays_o = a.rays_o, *rays_d = a.rays_d, *viewdirs = a.viewdirs;
+    const int R = a.R, chunk = a.chunk, n_fine = a.n_fine;
     TpFrame::Own own;
     if (!(eps >= 0.0f && eps < 1.0f)) own.after_counts = "eps must lie in [0, 1)";
     else if (!(segment >= 64 && segment % 64 == 0)) own.after_counts = "segment must be a positive multiple of 64";
@@ -746,13 +768,23 @@ int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* ra
                            static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N1 / segment)))};
     REQUIRE(static_cast<size_t>(std::max(win_of[0], win_of[1])) * std::min(segment, N1) * 3 <= 2147483647UL,
             "skip window too large for 32-bit indices");
+    // with a grid: one keep byte per candidate of a segment launch behind the march state, and room for the keep window that a
+    // level 0 without `coarse` (tp_eval_skipping) puts at the front of W[13] before the state is initialised - reserved here, so that
+    // nothing re-allocates under the state
+    const uint32_t* bits = use_occ && ctx->occ_G ? ctx->occ_bits.as<uint32_t>() : nullptr;
+    const int G = bits ? ctx->occ_G : 0;
+    const int win_max = std::max(win_of[0], win_of[1]);
+    const size_t candidates = bits ? static_cast<size_t>(win_max) * std::min(segment, N1) : 0;
+    const size_t skip_keep = bits && !coarse ? static_cast<size_t>(std::min(skip_window, R)) * N0 : 0;
+    if (bits || (use_occ && ((samples0 && samples0->fg_keep) || (samples1 && samples1->fg_keep))))
+        REQUIRE(r * N1 <= 2147483647UL - 1024, "too many points for 32-bit indices");
     TpDenseRows rows;
     if (rows.reserve(W, r, N0, N1) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)) ||
-        W[13].reserve(TpTermState::bytes(r, std::max(win_of[0], win_of[1]))))
+        W[13].reserve(std::max(TpTermState::bytes(r, win_max, candidates), skip_keep)))
         return NEO_ERR_NOMEM;
     auto [far, fg_t0, bg_s0, fg_out, bg_out, fg_w0, bg_w0, fg_t1, bg_s1] = rows;
     TpTermState st;
-    st.carve(W[13].p, r);
+    st.carve(W[13].p, r, win_max);
     float* scratch = W[9].as<float>();    // as neo_tp_render_culled
     float* c_bg_rgb = scratch + r * 18;
     float* c_bg_depth = scratch + r * 21;
@@ -765,7 +797,7 @@ int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* ra
     neo::launch_tp_level0(far, f.edges, R, N0, f.near, fg_t0, bg_s0, s);
     const bool sigma0 = level0_sigma_only(level0);
     const neo_tp_level_out* los[2] = {level0, level1};
-    const neo_tp_term_samples* sos[2] = {samples0, samples1};
+    const neo_tp_accel_samples* sos[2] = {samples0, samples1};
     struct LevelFg { float* fg_rgb; float* fg_depth; float* fg_acc; float* lam; float* bg_rgb; } L[2];
     for (int level = 0; level < 2; ++level) {
         const neo_tp_level_out* lo = los[level];
@@ -777,12 +809,17 @@ int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* ra
     for (int level = 0; level < 2; ++level) {
         const int N = level == 0 ? N0 : N1;
         const float* fg_t = level == 0 ? fg_t0 : fg_t1;
-        const neo_tp_term_samples* so = sos[level];
+        const neo_tp_accel_samples* so = sos[level];
         const bool dens = level == 0 && sigma0;
+        uint8_t* fg_keep = use_occ && so ? so->fg_keep : nullptr;       // the KEEP RULE on the whole row, behind the stops as well
         if (level == 1 || coarse) {
-            if (int rc = tp_eval_terminating(ctx, f, a, level, fg_t, far, N, fg_out, eps, segment, st, win_of[level],
+            if (int rc = tp_eval_accelerated(ctx, f, a, level, fg_t, far, N, fg_out, eps, segment, st, win_of[level], bits, G,
                                              kept ? kept + level : nullptr))
                 return rc;
+        } else if (bits) {      // the grid alone: neo_tp_render_skipping's level 0 (it may use the front of W[13]: before the init)
+            if (int rc = tp_eval_skipping(ctx, f, a, 0, fg_t, N, fg_out, fg_keep, kept)) return rc;
+            neo::launch_term_init(nullptr, st.stop, R, N, nullptr, 0, s);
+            fg_keep = nullptr;
         } else {
             if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
             neo::launch_term_init(nullptr, st.stop, R, N, kept, static_cast<long long>(r) * N, s);
@@ -796,6 +833,7 @@ int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* ra
             if (so->fg_w && level == 0) HIP_TRY(hipMemcpyAsync(so->fg_w, fg_w0, row, hipMemcpyDeviceToDevice, s));
             if (so->stop) HIP_TRY(hipMemcpyAsync(so->stop, st.stop, r * sizeof(int), hipMemcpyDeviceToDevice, s));
             if (so->fg_rows) HIP_TRY(hipMemcpyAsync(so->fg_rows, fg_out, row * 4, hipMemcpyDeviceToDevice, s));
+            if (fg_keep) neo::launch_occ_keep(rays_o, rays_d, fg_t, R, N, bits, G, fg_keep, s);
         }
         if (level == 0 && neo::launch_resample(fg_t0, N0, fg_w0, f.u, 0, R, N0, n_fine, 0, fg_t1, s))
             return fail(NEO_ERR_INVALID, "unsupported sample counts");
@@ -820,6 +858,32 @@ int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* ra
     if (samples0 && samples0->bg_s) HIP_TRY(hipMemcpyAsync(samples0->bg_s, bg_s0, r * N0 * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (samples1 && samples1->bg_s) neo::launch_term_rows_by_slot(bg_s1, slot, R, N1, samples1->bg_s, s);
     return check_launch();
+}
+
+int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                              const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                              const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps, int segment, int coarse,
+                              const neo_tp_term_samples* samples0, const neo_tp_term_samples* samples1, long long* kept,
+                              int* survivors_out, void* stream) {
+    ENTER(ctx);
+    const neo_tp_term_samples* given[2] = {samples0, samples1};
+    neo_tp_accel_samples so[2];
+    for (int l = 0; l < 2; ++l)
+        if (given[l]) so[l] = {given[l]->fg_t, given[l]->fg_w, given[l]->bg_s, given[l]->stop, nullptr, given[l]->fg_rows};
+    return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
+                              level1, eps, segment, coarse, samples0 ? &so[0] : nullptr, samples1 ? &so[1] : nullptr, kept,
+                              survivors_out, false);
+}
+
+// Occupancy skipping and early termination together (include/neo360_hip.h: ACCELERATED FRAME): the driver above with the grid read.
+int neo_tp_render_accelerated(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                              const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                              const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps, int segment, int coarse,
+                              const neo_tp_accel_samples* samples0, const neo_tp_accel_samples* samples1, long long* kept,
+                              int* survivors_out, void* stream) {
+    ENTER(ctx);
+    return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
+                              level1, eps, segment, coarse, samples0, samples1, kept, survivors_out, true);
 }
 
 // Object-level render: the two inside-sphere MLPs between a caller-given per-ray interval, on the rays that have one.

@@ -468,4 +468,12 @@ void launch_term_advance(const float* rgbsigma, const float* t, const float* ray
 // dst (R,N) = src_c row slot[ray], zeros where slot[ray] < 0
 void launch_term_rows_by_slot(const float* src_c, const int* slot, int R, int N, float* dst, hipStream_t s);
 
+// accelerate.hip - the segment launch of neo_tp_render_accelerated: launch_term_emit restricted to the samples that the KEEP RULE keeps
+// The candidates are launch_term_emit's rows (sample b0 + p % len of ray r0 + map[p / len], p < *alive len); keep (rays x len bytes)
+// receives their keep bytes, w.totals the per-workgroup sums, and the kept ones leave point rows as launch_term_emit's, in ascending
+// candidate order; *w.count = their number, also added to *kept_sum when not null.  Two launches, no atomics.
+void launch_acc_compact(const float* rays_o, const float* rays_d, const float* viewdirs, const float* t, const int* map, const int* alive,
+                        int r0, int rays, int R, int N, int b0, int len, int chunk, const uint32_t* bits, int G, uint8_t* keep,
+                        const OccRows& w, long long* kept_sum, hipStream_t s);
+
 }  // namespace neo

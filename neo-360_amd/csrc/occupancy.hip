@@ -24,6 +24,7 @@
 // point, the origin and direction of its ray, its t, and the view direction of the quirk-Q1 ray of the DENSE launch,
 // c0 + ((r - c0) N + j) mod bc.  The evaluator sources are not touched.
 #include "common.h"
+#include "occ_points.h"
 #include "tp_frame.h"
 
 using namespace neo_host;
@@ -32,30 +33,7 @@ namespace neo {
 
 namespace {
 
-constexpr int OCC_BLOCK = 256;
-constexpr int OCC_ROUNDS = 4;
-constexpr int OCC_POINTS = OCC_BLOCK * OCC_ROUNDS;      // points per workgroup
-constexpr int OCC_SEGS = OCC_POINTS / 64;               // 64-point segments per workgroup, in point order
-
-// i = min(max((int)floorf((x + 1) (G / 2)), 0), G - 1), clamped before the conversion (the same value for every finite x)
-__device__ __forceinline__ int occ_cell(float x, int G) {
-    float c = floorf((x + 1.0f) * (0.5f * (float)G));
-    c = c > 0.0f ? c : 0.0f;
-    c = c < (float)(G - 1) ? c : (float)(G - 1);
-    return (int)c;
-}
-
-// KEEP RULE: a set cell, a non-finite coordinate (the negation of `<`, as cull_keep: a NaN survives to the caller) or no grid
-__device__ __forceinline__ bool occ_keep_point(const uint32_t* __restrict__ bits, int G, const float* __restrict__ o,
-                                               const float* __restrict__ d, float tv) {
-    float x[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = o[a] + tv * d[a];
-    if (!(fabsf(x[0]) < __builtin_inff()) || !(fabsf(x[1]) < __builtin_inff()) || !(fabsf(x[2]) < __builtin_inff())) return true;
-    if (!bits) return true;
-    const int lin = (occ_cell(x[0], G) * G + occ_cell(x[1], G)) * G + occ_cell(x[2], G);
-    return (bits[lin >> 5] >> (lin & 31)) & 1u;
-}
+// the workgroup layout, occ_cell, occ_keep_point (the KEEP RULE) and occ_rank: occ_points.h, shared with accelerate.hip
 
 // rays_o / rays_d: row 0 is the ray of point 0; t, keep: P = rays x N points.  totals (may be null): kept points per workgroup.
 __global__ __launch_bounds__(OCC_BLOCK) void k_occ_keep(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
@@ -84,42 +62,6 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_keep(const float* __restrict_
         for (int g = 0; g < OCC_SEGS; ++g) n += s_seg[g];
         totals[blockIdx.x] = n;
     }
-}
-
-// The compact index of this thread's point of every round (k[it], valid where kept[it]) and the kept points up to and including
-// this workgroup (`upto`): the sums of compact.h's emit over this file's segments.  Integer sums: any order gives the same value.
-struct OccRank {
-    bool kept[OCC_ROUNDS];
-    int k[OCC_ROUNDS];
-    int upto;
-};
-__device__ __forceinline__ OccRank occ_rank(const uint8_t* __restrict__ keep, int P, const int* __restrict__ totals, int* s_part,
-                                            int* s_seg) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int part = 0;
-    for (int b = threadIdx.x; b < (int)blockIdx.x; b += OCC_BLOCK) part += totals[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-    OccRank rk;
-    int below[OCC_ROUNDS];
-#pragma unroll
-    for (int it = 0; it < OCC_ROUNDS; ++it) {
-        const int p = blockIdx.x * OCC_POINTS + it * OCC_BLOCK + threadIdx.x;
-        rk.kept[it] = p < P && keep[p] != 0;
-        const unsigned long long ballot = __ballot(rk.kept[it]);
-        below[it] = __popcll(ballot & ((1ull << lane) - 1ull));
-        if (lane == 0) s_seg[it * 4 + wv] = __popcll(ballot);
-    }
-    if (lane == 0) s_part[wv] = part;
-    __syncthreads();
-    int run = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-#pragma unroll
-    for (int g = 0; g < OCC_SEGS; ++g) {
-        if ((g & 3) == wv) rk.k[g >> 2] = run + below[g >> 2];
-        run += s_seg[g];
-    }
-    rk.upto = run;
-    return rk;
 }
 
 // One window: rays r0 .. r0 + P / N - 1 of the frame's R rays; t and keep are the window's rows.  Per kept point p = r_w N + j:
@@ -208,8 +150,6 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_from_sigma(const float* __res
         bits[(idx >> 5) + 1] = (uint32_t)(ballot >> 32);
     }
 }
-
-inline int occ_blocks(long P) { return (int)((P + OCC_POINTS - 1) / OCC_POINTS); }
 
 }  // namespace
 

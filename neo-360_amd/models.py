@@ -469,6 +469,8 @@ class NeRF_TP(_HipModule):
         self.last_skip_kept = None           # int64[2] device tensor: kept inside-sphere samples per level of the last render_skipping call
         self.last_terminate_kept = None      # int64[2] device tensor: evaluated inside-sphere samples per level of the last render_terminating call
         self.last_terminate_survivors = None # int32 device tensor: rays of that call whose background ran
+        self.last_accel_kept = None          # int64[2] device tensor: evaluated inside-sphere samples per level of the last render_accelerated call
+        self.last_accel_survivors = None     # int32 device tensor: rays of that call whose background ran
 
     @property
     def cull_background(self):
@@ -1225,6 +1227,72 @@ class NeRF_TP(_HipModule):
         out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
         if return_samples:
             names = ("fg_t", "fg_w", "bg_s", "stop") + (("fg_rows",) if return_samples == "rows" else ())
+            out.append([tuple(t[k] for k in names) for t in levels])
+        return out
+
+    # ---- occupancy skipping and early termination together ---------------------------------------------------------------------
+
+    @torch.no_grad()
+    def render_accelerated(self, rays, eps, chunk=None, segment=64, coarse=False, return_samples=False, fine_only=False):
+        """`render_terminating(rays, eps, ...)` that also obeys the installed occupancy grid (neo_tp_render_accelerated;
+        include/neo360_hip.h: ACCELERATED FRAME).  At level 1 - and at level 0 with coarse=True - sample j of a ray is evaluated iff
+        the grid keeps it (`ops.occupancy_keep`) and j < stop, where stop is `ops.termination_stops` on the level's rows with the
+        samples that are not kept zeroed; level 0 with coarse=False obeys the grid only, as in `render_skipping`.  A sample that is
+        not evaluated has a zero row and weight exactly 0.  The background and the launch order are `render_terminating`'s.
+
+        With no grid installed the result is bitwise `render_terminating`'s (no error is raised: that is the terminating frame);
+        with eps = 0 it is bitwise `render_skipping`'s with the same grid; with neither, `forward`'s.  With coarse=False a stopped
+        ray's level-1 rgb differs from `render_skipping`'s by at most 1.003 * bg_lambda per channel and its depth by at most
+        (t_far + 1.001) * bg_lambda, with the returned bg_lambda < eps; nothing is claimed for coarse=True.  Reads neither
+        `cull_background` nor `compute_extras`; `ray_grid` as `forward`; `skip_window` bounds the workspace as in `render_skipping`.
+        ValueError, before any device access, for eps outside [0, 1) or NaN, or a segment that is not a positive multiple of 64;
+        NeoError when the installed grid belongs to another context.
+
+        Returns the two level tuples of `forward(..., out_depth=True)` (fine_only=True: None for level 0); with return_samples a
+        third element holds per level (fg_t, fg_w, bg_s, stop (B,) int32, fg_keep (B,N) bool - the grid's verdict on the whole row,
+        behind the stop as well: the evaluated set is fg_keep & (j < stop)) - and, with return_samples="rows", fg_rows (B,N,4)
+        behind them.  `self.last_accel_kept` (int64[2]: evaluated inside-sphere samples per level) and `self.last_accel_survivors`
+        (int32: rays whose background ran) stay on the device; nothing is read back."""
+        eps, segment = ops._check_termination(eps, segment, "render_accelerated")
+        call = self._frame_call(rays, chunk, use_grid=True)
+        B, dev = call.B, call.dev
+        levels = []
+        counts = []
+
+        def launch():
+            ctx = call.ctx
+            if self._occupancy is not None and self._occ_ctx is not ctx:
+                raise _lib.NeoError("the occupancy grid does not belong to this scene and device: install it again")
+            self._set_mode(ctx, "_skip_window", "neo_tp_set_skip_window", int(self.skip_window or 0))
+            structs, sample_structs = [], []
+            for level, n in enumerate(call.n):
+                if level == 0 and fine_only:
+                    t, struct = {}, None
+                else:
+                    t, struct = self._level_out(B, dev)
+                structs.append(struct)
+                if return_samples:
+                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev),
+                             stop=torch.empty(B, dtype=torch.int32, device=dev), fg_keep=torch.empty(B, n, dtype=torch.bool, device=dev))
+                    if return_samples == "rows":
+                        t["fg_rows"] = torch.empty(B, n, 4, device=dev)
+                    sample_structs.append(_lib.TpAccelSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpAccelSamples._fields_)))
+                else:
+                    sample_structs.append(None)
+                levels.append(t)
+            counts.append(torch.empty(2, dtype=torch.int64, device=dev))
+            counts.append(torch.empty((), dtype=torch.int32, device=dev))
+            _lib.check(ctx.lib.neo_tp_render_accelerated(
+                *call.ray_args, *call.frame_args, *(ctypes.byref(x) if x is not None else None for x in structs), eps, segment,
+                int(bool(coarse)), *(ctypes.byref(x) if x is not None else None for x in sample_structs), counts[0].data_ptr(),
+                counts[1].data_ptr(), ctx.stream()))
+            self._after_call(ctx)
+            return [v for t in levels for v in t.values()] + counts
+        call.run(launch)
+        self.last_accel_kept, self.last_accel_survivors = counts
+        out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
+        if return_samples:
+            names = ("fg_t", "fg_w", "bg_s", "stop", "fg_keep") + (("fg_rows",) if return_samples == "rows" else ())
             out.append([tuple(t[k] for k in names) for t in levels])
         return out
 

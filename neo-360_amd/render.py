@@ -383,6 +383,30 @@ def render_terminating_rays(model, batch, eps, chunk=1024, segment=64, coarse=Fa
 
 
 @torch.no_grad()
+def render_accelerated_rays(model, batch, eps, chunk=1024, segment=64, coarse=False, check=True, on_range="retry_f32"):
+    """Frame of a NeRF_TP module with empty space skipped AND early ray termination: the fine level of
+    `model.render_accelerated(batch, eps, ...)` on every ray of `batch` in one library call, with the reference chunk size passed
+    down.  Returns dict(rgb (R,3), depth (R,), acc (R,)) plus `kept_fraction`, a (2,) float64 DEVICE tensor - the share of
+    inside-sphere samples evaluated at level 0 and level 1 - and `culled_fraction`, a float64 DEVICE scalar - the share of rays whose
+    outside-sphere half did not run (reading either synchronises, the call does not) - and `target` / `instance_mask` passed through.
+    Without a grid it is render_terminating_rays; with eps = 0, render_skipping_rays.  check / on_range: the flag read, range-guard
+    retry and latch of render_rays_test (the same code path)."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("render_accelerated_rays renders NeRF_TP modules, got %r" % type(model))
+
+    def once():
+        res = model.render_accelerated(batch, eps, chunk=chunk, segment=segment, coarse=coarse)
+        fine = res[1]
+        R = fine[0].shape[0]
+        n0 = model.num_coarse_samples + 1
+        kept = model.last_accel_kept.double()          # scalar divisors travel as kernel arguments: no copy, no wait
+        frac = torch.stack([kept[0] / float(max(R * n0, 1)), kept[1] / float(max(R * (n0 + model.num_fine_samples), 1))])
+        culled = 1.0 - model.last_accel_survivors.double() / float(max(R, 1))
+        return dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=frac, culled_fraction=culled)
+    return _render_guarded(model, batch, once, check, on_range)
+
+
+@torch.no_grad()
 def render_frame_sharded(model, batch, world, rank, chunk=1024, white_bkgd=False, near=0.2, far=3.0, group=None,
                          gather=True, train_frac=1.0, n_rays=None, out=None, reuse=False, check=True, always_gather=False,
                          info=None, image_width=None):
