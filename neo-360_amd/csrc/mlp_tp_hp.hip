@@ -45,6 +45,9 @@
 // the latent taps alone; 512 the loads are replaced by undefined registers (blends, LDS transposition and adds stay)
 #define NEO_TP_ABLATE 0
 #endif
+#ifndef NEO_TP_ROW_POINT
+#define NEO_TP_ROW_POINT 1    // the closing block reads each row's launch point from LDS (kept by point_setup) instead of re-deriving it
+#endif
 #define TP_SYNC() __syncthreads()
 #ifndef NEO_TP_TRACE
 #define NEO_TP_TRACE 0        // 1: per-phase s_memtime sums of wave 0 of every workgroup -> g_tp_trace (tools/tp_phase_trace.py)
@@ -62,6 +65,9 @@ namespace {
 
 using namespace hp;
 constexpr int RING = NEO_TP_RING;
+constexpr int HP_OFF_POINT = tp::LDS_WORDS + 768 + 336;          // long[64] behind the biases and heads: the launch point of every row
+constexpr int HP_LDS_WORDS = HP_OFF_POINT + (NEO_TP_ROW_POINT ? TM * 2 : 0);
+static_assert(HP_OFF_POINT % 2 == 0, "8-byte records");
 
 // DENS: density-only variant (level-0 launches of a frame whose coarse colour nobody reads): everything up to the view-mean trunk
 // and the density head is the full kernel's; the direction-encoding staging, the 14 tail k-steps and the rgb head are not run,
@@ -108,7 +114,9 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
 #if NEO_TP_TRACE
     unsigned long long tr_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #endif
-    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr, CULL ? 0 : sc.quad);
+    [[maybe_unused]] long* row_point = reinterpret_cast<long*>(smem + HP_OFF_POINT);
+    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr, CULL ? 0 : sc.quad,
+                          NEO_TP_ROW_POINT ? row_point : nullptr);
     float* dens_w = smem + tp::OFF_DENSW;
     if (tid < 128) dens_w[tid] = m.heads[HD_DW + tid];
     // biases and head weights are read from LDS: an accumulator initialisation is on the critical path of every layer
@@ -602,7 +610,9 @@ __global__ __launch_bounds__(256, NEO_TP_WPS) void k_tp_mlp_hp(TpMlpHDev m, cons
         }
         range_commit(L, m.flags);
         const long gv = tile0 + pt;
-        const long gi = tp::launch_point(gv, N, R, CULL ? 0 : sc.quad, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
+        long gi;            // rows past P hold P - 1's point there and are not written
+        if constexpr (NEO_TP_ROW_POINT != 0) gi = row_point[pt];
+        else gi = tp::launch_point(gv, N, R, CULL ? 0 : sc.quad, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
         if (part == 0 && gv < P) {
             if constexpr (DENS)
                 out[gi] = make_float4(0.0f, 0.0f, 0.0f, density_act(raw_sigma));
@@ -808,7 +818,7 @@ void launch_tp_mlp_hp(int input_ch, const TpMlpHDev& m, const float* proj, const
         const char* e = getenv("NEO_TP_LDS_PAD");
         lds_pad = e ? (size_t)atol(e) : 0;
     }
-    const size_t lds = (tp::LDS_WORDS + 768 + 336) * sizeof(float) + lds_pad;
+    const size_t lds = HP_LDS_WORDS * sizeof(float) + lds_pad;
     if (lds > 65536) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tp_mlp_hp<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

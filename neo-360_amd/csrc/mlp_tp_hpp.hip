@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "pe_schedule.h"
 #include "tp_hp_layout.h"
 
 #ifndef NEO_TPP_WPS
@@ -45,6 +46,11 @@
 #ifndef NEO_TPP_TD
 #define NEO_TPP_TD 6           // tail weight stream prefetch distance
 #endif
+#ifndef NEO_TPP_FRONT
+#define NEO_TPP_FRONT 7        // front-end work done once instead of repeatedly (bit mask; 0 = none, the kernels before these existed):
+#endif                         //   1: outside the sphere, 1/r is encoded once per tile and the view loop's pairs are balanced (pe_schedule.h)
+                               //   2: the closing block reads each row's launch point from LDS (kept by point_setup) instead of re-deriving it
+                               //   4: the work list's group bits come from the wave that computed the map's weights (one LDS word per map)
 #define TPP_SYNC() __syncthreads()
 #ifndef NEO_TP_TRACE
 #define NEO_TP_TRACE 0         // 1: per-phase s_memtime sums of wave 0 of every workgroup -> g_tpp_trace (tools/bench_tp_kernel.py TRACE=1)
@@ -76,7 +82,10 @@ constexpr int PP_OFF_VDIR = PP_OFF_FEAT + TM * 4;
 constexpr int PP_OFF_DENSW = PP_OFF_VDIR + TM * 4;
 constexpr int PP_OFF_BIAS = PP_OFF_DENSW + 128;
 constexpr int PP_OFF_XPE0 = PP_OFF_BIAS + 768 + 336;
-constexpr int PP_LDS_WORDS = PP_OFF_XPE0 + TM * 64;          // [64][64] halves x 2 planes = 16 KB; total 77,760 B: 2 workgroups per CU
+constexpr int PP_OFF_POINT = PP_OFF_XPE0 + TM * 64;          // [64][64] halves x 2 planes = 16 KB
+constexpr int PP_OFF_WBITS = PP_OFF_POINT + TM * 2;          // long[64]: the launch point of every row (NEO_TPP_FRONT & 2)
+constexpr int PP_LDS_WORDS = PP_OFF_WBITS + 4;               // unsigned[4]: group bits of every map (NEO_TPP_FRONT & 4); total 78,288 B: 2 workgroups per CU
+static_assert(PP_OFF_POINT % 2 == 0 && PP_OFF_WBITS % 4 == 0, "8-byte records, one 16-byte read");
 static_assert(PP_LDS_WORDS * 4 <= 81920, "two workgroups per CU");
 
 struct TpPlaneBase { int texels[3]; };      // first texel of each projected tri-plane inside the one projected-maps buffer
@@ -128,7 +137,12 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
 #if NEO_TP_TRACE
     unsigned long long tr_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #endif
-    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr, CULL ? 0 : sc.quad);
+    constexpr bool PE_TILE = PE_C == 4 && (NEO_TPP_FRONT & 1) != 0;      // 1/r encoded once per tile (pe_schedule.h)
+    constexpr bool ROW_POINT = (NEO_TPP_FRONT & 2) != 0, WBITS = (NEO_TPP_FRONT & 4) != 0;
+    [[maybe_unused]] long* row_point = reinterpret_cast<long*>(smem + PP_OFF_POINT);
+    [[maybe_unused]] unsigned* wbits = reinterpret_cast<unsigned*>(smem + PP_OFF_WBITS);
+    tp::point_setup<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, false, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph, CULL ? sc.cull_map : nullptr, CULL ? 0 : sc.quad,
+                          ROW_POINT ? row_point : nullptr);
     float* dens_w = smem + PP_OFF_DENSW;
     if (tid < 128) dens_w[tid] = m.heads[HD_DW + tid];
     if (tid < DESC_BLOCK) {                            // the all-zero descriptor block (offset 0 = the buffer's first texel, weight 0)
@@ -141,6 +155,55 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
     const float* lbias = lbias_w;
     const float* lheads = lbias_w + 768;
     TPP_SYNC();
+    // pos_enc position `pos` (pe_schedule.h) of row `row`: halves from smem to its hi plane; the lo plane lies LO0 / LO1 halves behind.
+    // Which of the two encoding tiles a position falls into is a compile-time property of every caller's slot.
+    [[maybe_unused]] _Float16* const pe_h = reinterpret_cast<_Float16*>(smem);
+    [[maybe_unused]] auto pe_at = [&](auto firstc, int row, int pos) __attribute__((always_inline)) {
+        if constexpr (decltype(firstc)::value) return PP_OFF_XPE0 * 2 + chunk_off<64>(row, pos >> 3) + (pos & 7);         // positions 0..63
+        else return tp::OFF_DIR * 2 + chunk_off<32>(row, (pos - 64) >> 3) + (pos & 7);                                       // 64..95
+    };
+    [[maybe_unused]] constexpr std::true_type PE_FIRST{};
+    [[maybe_unused]] constexpr std::false_type PE_SECOND{};
+    [[maybe_unused]] constexpr int LO0 = TM * 64, LO1 = TM * 32;      // hi -> lo plane of the first / the second tile (halves)
+    if constexpr (PE_TILE) {
+        // ---- the view-independent part of the encoding, once per tile: the 10 pairs of 1/r (row = tid % 64, wave q takes octaves
+        //      q, 4 + q, 8 + q), identity position 83 and the zero padding.  Nothing else writes these bytes before the tail (the
+        //      second tile aliases dsm), so they serve every view; the first reader waits behind the view loop's first barrier. ----
+        namespace ps = pe_sched;
+        const int row = tid & 63, q = L.wv;
+        const float tv = S.pe_world[row * 4 + 3];
+        static_for<0, ps::TILE_SLOTS>([&](auto sl) {
+            constexpr int slot = decltype(sl)::value;
+            constexpr bool first = ps::WAVES * slot + ps::WAVES <= 8;      // octaves q + 4 slot: slots 0, 1 below 8, slot 2 = 8, 9
+            if (slot < ps::OCTAVES / ps::WAVES || slot < ps::tile_pairs(q)) {
+                const int oct = ps::tile_octave(q, slot);
+                float sn, cs;
+                sincos_pair(ldexpf(tv, oct), sn, cs);
+                h2 h, l;
+                split2(sn, cs, h, l);
+                const int o = pe_at(std::bool_constant<first>(), row, ps::pair_pos(oct, 3));
+                *reinterpret_cast<h2*>(pe_h + o) = h;
+                *reinterpret_cast<h2*>(pe_h + o + (first ? LO0 : LO1)) = l;
+            }
+        });
+        if (q == ps::TILE_IDENT_WAVE) {                // position 83 = 1/r; 84..87 = 0
+            range_see(L, tv);
+            h2 h, l;
+            split2(tv, 0.0f, h, l);
+            const int o = pe_at(PE_SECOND, row, ps::IDENT_POS + 3);
+            pe_h[o] = h[0];
+            pe_h[o + LO1] = l[0];
+            const h4 z = {0, 0, 0, 0};
+            *reinterpret_cast<h4*>(pe_h + o + 1) = z;
+            *reinterpret_cast<h4*>(pe_h + o + 1 + LO1) = z;
+        }
+        if (q == ps::TILE_PAD_WAVE) {                  // 88..95 = 0
+            const int o = pe_at(PE_SECOND, row, ps::PAD_POS + 4);
+            const h8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+            *reinterpret_cast<h8*>(pe_h + o) = z;
+            *reinterpret_cast<h8*>(pe_h + o + LO1) = z;
+        }
+    }
 
     // view means by linearity (mlp_tp_h.hip): only sum_v relu(L3_v) is accumulated per view; sum_v dir_enc_v comes ready-made
     // per ray from k_tp_dirsum and is only needed in the tail
@@ -161,12 +224,80 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
         L.key = L.lane & 15;
         const float* rot = views.rot[v];
         const float* trn = views.trans[v];
-        tp::view_descriptors<PROJ_TEXEL_BYTES, false, PROJ_TEXEL_BYTES>(S, L, sc, rot, trn, v, [](int, int, float) {},
-                                                                        L.wv == 0 ? 0 : plb.texels[L.wv == 0 ? 0 : L.wv - 1]);
+        const bool weighted =
+            tp::view_descriptors<PROJ_TEXEL_BYTES, false, PROJ_TEXEL_BYTES>(S, L, sc, rot, trn, v, [](int, int, float) {},
+                                                                            L.wv == 0 ? 0 : plb.texels[L.wv == 0 ? 0 : L.wv - 1]);
+        if constexpr (WBITS) {
+            // the work list's input: bit g of word w = some row of group g (rows 16 g .. 16 g + 15) has a weighted tap in map w.  The
+            // wave that just computed map w's weights ballots them; the barrier behind the encoding publishes the four words.
+            const unsigned long long z = __ballot(weighted);
+            unsigned bits = 0;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) bits |= (((z >> (16 * g)) & 0xFFFFull) != 0ull ? 1u : 0u) << g;
+            if (L.lane == 0) wbits[L.wv] = bits;
+        }
         // ---- pos_enc of this view's camera-frame point into its own tile: row = tid % 64, wave q takes chunks q and 4 + q of
         //      stage 0 (and chunk q of stage 1).  The camera-frame point is computed here with the arithmetic of
         //      view_descriptors (same expression, no contraction), so no barrier separates it from the descriptors. ----
-        {
+        if constexpr (PE_TILE) {
+            // outside the sphere: only the 30 pairs of x, y, z and identity positions 80..82; 1/r, the rest of the identity chunk and
+            // the padding were written once per tile.  Wave q: x, y, z of octaves 2 q and 2 q + 1 (12 contiguous bytes each), then one
+            // pair of octaves 8 / 9 in slot 6 and - waves 0, 1 - slot 7: 8 / 8 / 7 / 7 pairs (pe_schedule.h).
+            namespace ps = pe_sched;
+            const int row = tid & 63;
+            int q = L.wv;
+            asm volatile("" : "+s"(q));      // opaque per view: the slots' scalar octaves / positions are not hoisted out of the view loop (SGPR spills)
+            const float ex = S.pe_world[row * 4], ey = S.pe_world[row * 4 + 1], ez = S.pe_world[row * 4 + 2];
+            float xv[3];
+            xv[0] = (rot[0] * ex + rot[1] * ey + rot[2] * ez) + trn[0];
+            xv[1] = (rot[3] * ex + rot[4] * ey + rot[5] * ez) + trn[1];
+            xv[2] = (rot[6] * ex + rot[7] * ey + rot[8] * ez) + trn[2];
+            asm("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]));      // computed once, here: not sunk into the slots
+            static_for<0, ps::VIEW_LOW_SLOTS / 3>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                const int oct = ps::view_octave(q, 3 * k);           // slots 3 k .. 3 k + 2: coordinates 0, 1, 2 of this octave
+                h2 h[3], l[3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    static_assert(ps::view_coord(0, 3 * k) == 0 && ps::view_coord(3, 3 * k + 1) == 1 && ps::view_coord(1, 3 * k + 2) == 2);
+                    float sn, cs;
+                    sincos_pair(ldexpf(xv[a], oct), sn, cs);
+                    split2(sn, cs, h[a], l[a]);
+                }
+                const int o = pe_at(PE_FIRST, row, ps::pair_pos(oct, 0));
+                *reinterpret_cast<h4*>(pe_h + o) = h4{h[0][0], h[0][1], h[1][0], h[1][1]};
+                *reinterpret_cast<h2*>(pe_h + o + 4) = h[2];
+                *reinterpret_cast<h4*>(pe_h + o + LO0) = h4{l[0][0], l[0][1], l[1][0], l[1][1]};
+                *reinterpret_cast<h2*>(pe_h + o + 4 + LO0) = l[2];
+            });
+            static_for<ps::VIEW_LOW_SLOTS, ps::VIEW_SLOTS>([&](auto sl) {
+                constexpr int slot = decltype(sl)::value;
+                if (slot < ps::VIEW_PAIRS / ps::WAVES || slot < ps::view_pairs(q)) {
+                    const int oct = ps::view_octave(q, slot), a = ps::view_coord(q, slot);      // wave-uniform: scalar arithmetic
+                    // the coordinate by scalar bit masks: a ternary here compiles to branches around register moves
+                    const unsigned m0 = a == 0 ? ~0u : 0u, m1 = a == 1 ? ~0u : 0u, m2 = a == 2 ? ~0u : 0u;
+                    const float x = __uint_as_float((__float_as_uint(xv[0]) & m0) | (__float_as_uint(xv[1]) & m1) | (__float_as_uint(xv[2]) & m2));
+                    float sn, cs;
+                    sincos_pair(ldexpf(x, oct), sn, cs);
+                    h2 h, l;
+                    split2(sn, cs, h, l);
+                    const int o = pe_at(PE_SECOND, row, ps::pair_pos(oct, a));
+                    *reinterpret_cast<h2*>(pe_h + o) = h;
+                    *reinterpret_cast<h2*>(pe_h + o + LO1) = l;
+                }
+            });
+            if (q == ps::VIEW_IDENT_WAVE) {
+                range_see(L, xv[0]); range_see(L, xv[1]); range_see(L, xv[2]);
+                h2 h, l, hz, lz;
+                split2(xv[0], xv[1], h, l);
+                split2(xv[2], 0.0f, hz, lz);
+                const int o = pe_at(PE_SECOND, row, ps::IDENT_POS);
+                *reinterpret_cast<h2*>(pe_h + o) = h;
+                *reinterpret_cast<h2*>(pe_h + o + LO1) = l;
+                pe_h[o + 2] = hz[0];
+                pe_h[o + 2 + LO1] = lz[0];
+            }
+        } else {
             const int row = tid & 63, q = tid >> 6;
             const float ex = S.pe_world[row * 4], ey = S.pe_world[row * 4 + 1], ez = S.pe_world[row * 4 + 2];
             f32x4 xv;
@@ -311,6 +442,15 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
             {
                 int4* mylist = reinterpret_cast<int4*>(smem + PP_OFF_LIST) + L.wv * LIST_MAX;
                 unsigned am = 0;                             // bit 4 q + m: a row of group q (rows 16 q .. 16 q + 15) has a weighted tap in map m
+                if constexpr (WBITS) {
+                    const uint4 wb = *reinterpret_cast<const uint4*>(wbits);      // one word per map, from the wave that computed it
+                    const unsigned w4[4] = {wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+                    for (int mp = 0; mp < 4; ++mp)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) am |= ((w4[mp] >> q) & 1u) << (4 * q + mp);
+                    am = __builtin_amdgcn_readfirstlane(am);
+                } else
 #pragma unroll
                 for (int mp = 0; mp < 4; ++mp) {
                     const f32x4 w = *reinterpret_cast<const f32x4*>(loc_w + (mp * TM + L.lane) * 4);
@@ -601,7 +741,9 @@ __global__ __launch_bounds__(256, NEO_TPP_WPS) void k_tp_mlp_hpp(TpMlpHDev m, co
         }
         range_commit(L, m.flags);
         const long gv = tile0 + pt;
-        const long gi = tp::launch_point(gv, N, R, CULL ? 0 : sc.quad, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
+        long gi;            // rows past P hold P - 1's point there and are not written
+        if constexpr (ROW_POINT) gi = row_point[pt];
+        else gi = tp::launch_point(gv, N, R, CULL ? 0 : sc.quad, sc.grid_w, sc.grid_first, sc.grid_pw, sc.grid_ph);
         if (part == 0 && gv < P) {
             if constexpr (DENS)
                 out[gi] = make_float4(0.0f, 0.0f, 0.0f, density_act(raw_sigma));

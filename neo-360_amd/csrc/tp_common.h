@@ -153,7 +153,8 @@ __device__ __forceinline__ void point_setup_row(const Scratch& S, int tid, long 
                                                 const float* __restrict__ viewdirs, const float* __restrict__ tvals,
                                                 const float* __restrict__ far_arr, uint32_t* __restrict__ flags,
                                                 bool t_shared = false, int grid_w = 0, long grid_first = 0, int pw = 3, int ph = 3,
-                                                const int* __restrict__ cull_map = nullptr, int quad = 0) {
+                                                const int* __restrict__ cull_map = nullptr, int quad = 0,
+                                                long* row_point = nullptr) {
     float* pe_world = S.pe_world;
     float* feat_world = S.feat_world;
     float* vdir_world = S.vdir_world;
@@ -161,6 +162,7 @@ __device__ __forceinline__ void point_setup_row(const Scratch& S, int tid, long 
         long g = tile0 + tid;
         if (g >= P) g = P - 1;
         g = launch_point(g, N, R, quad, grid_w, grid_first, pw, ph);   // quad order (TpScene::quad), then the ray-patch order
+        if (row_point) row_point[tid] = g;                       // kept for the kernel's closing block: the row of `out` (rows past P: P - 1's, not written)
         const int row = (int)(g / N);                            // ray of the launch: the row of tvals and of the output
         const int s = (int)(g - (long)row * N);
         const int ray = cull_map ? cull_map[row] : row;          // compact launch: the caller's ray behind that row
@@ -229,9 +231,10 @@ __device__ __forceinline__ void point_setup(const Scratch& S, int tid, long tile
                                             const float* __restrict__ viewdirs, const float* __restrict__ tvals,
                                             const float* __restrict__ far_arr, uint32_t* __restrict__ flags,
                                             bool t_shared = false, int grid_w = 0, long grid_first = 0, int pw = 3, int ph = 3,
-                                            const int* __restrict__ cull_map = nullptr, int quad = 0) {
+                                            const int* __restrict__ cull_map = nullptr, int quad = 0,
+                                            long* row_point = nullptr) {
     if (tid < TM)
-        point_setup_row<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, t_shared, grid_w, grid_first, pw, ph, cull_map, quad);
+        point_setup_row<PE_C>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, far_arr, flags, t_shared, grid_w, grid_first, pw, ph, cull_map, quad, row_point);
 }
 
 // ---- per-view descriptors (all 4 waves; lane = row) ---------------------------------------------------
@@ -245,7 +248,8 @@ __device__ __forceinline__ void point_setup(const Scratch& S, int tid, long tile
 template <int LOC_TEXEL_BYTES = 2048, bool DIRS = true, int PL_TEXEL_BYTES = 128 * 4, class PutDir>
 // pl_base_texels: added to this wave's tri-plane texel indices (mlp_tp_hpp.hip keeps the four projected maps in ONE buffer
 // and addresses them from one base pointer; 0 for every other caller).
-__device__ __forceinline__ void view_descriptors(const Scratch& S, const LaneCtx& L, const TpScene& sc,
+// Returns whether this lane's row carries a weighted tap in this wave's map (the work list of mlp_tp_hpp.hip).
+__device__ __forceinline__ bool view_descriptors(const Scratch& S, const LaneCtx& L, const TpScene& sc,
                                                  const float* rot, const float* trn, int v, PutDir put_dir,
                                                  int pl_base_texels = 0) {
     int* loc_off = S.loc_off; float* loc_w = S.loc_w; int* pl_off = S.pl_off; float* pl_w = S.pl_w;
@@ -292,7 +296,8 @@ __device__ __forceinline__ void view_descriptors(const Scratch& S, const LaneCtx
                 dst_off[p * 4 + k] = (int)((uint32_t)(base + t.off[k]) * (uint32_t)texel_bytes);   // byte offset mod 2^32
                 dst_w[p * 4 + k] = t.w[k];
             }
-            if constexpr (!DIRS) return;
+            const bool weighted = t.w[0] != 0.0f || t.w[1] != 0.0f || t.w[2] != 0.0f || t.w[3] != 0.0f;
+            if constexpr (!DIRS) return weighted;
             // view-direction encoding in this view's camera frame; wave q takes octave q
             const float dx = vdir_world[p * 4], dy = vdir_world[p * 4 + 1], dz = vdir_world[p * 4 + 2];
             const float dc[3] = {rot[0] * dx + rot[1] * dy + rot[2] * dz, rot[3] * dx + rot[4] * dy + rot[5] * dz,
@@ -312,6 +317,7 @@ __device__ __forceinline__ void view_descriptors(const Scratch& S, const LaneCtx
 #pragma unroll
                 for (int f = 27; f < 32; ++f) put_dir(p, f, 0.0f);
             }
+            return weighted;
         }
 }
 
