@@ -476,7 +476,7 @@ int neo_tp_render_decomposed(neo_ctx* ctx, const float* rays_o, const float* ray
  * neo_tp_set_occupancy copies `bits` [device, G^3 / 8 bytes] into context-owned memory; bits == NULL removes the grid.
  * neo_tp_set_scene removes it as well: a grid describes one scene (and its source poses and weights, which the library cannot
  * check).  neo_tp_set_skip_window: rays per window of neo_tp_render_skipping, 1 .. 65536, 0 = the default (4096); a window bounds
- * the extra workspace at (64 + 128) bytes per (ray, sample) of one window.  Results do not depend on it. */
+ * the extra workspace at (68 + 128) bytes per (ray, sample) of one window.  Results do not depend on it. */
 int neo_tp_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, void* stream);
 int neo_tp_set_skip_window(neo_ctx* ctx, int rays);
 
@@ -594,6 +594,61 @@ int neo_tp_render_accelerated(neo_ctx* ctx, const float* rays_o, const float* ra
  * stop == N).  The kernel is the frame's.  R == 0 is a valid call.  Touches no context-owned memory. */
 int neo_tp_termination_stops(neo_ctx* ctx, const float* rgbsigma, const float* t, const float* rays_d, const float* t_far, int R, int N,
                              float eps, int segment, int* stop, float* trans, void* stream);
+
+/* MARCHING FRAME: the one driver behind neo_tp_render_terminating (use_grid == 0) and neo_tp_render_accelerated (use_grid != 0), with
+ * one more switch: outside != 0 carries the early termination through the OUTSIDE-sphere march of the rays whose background runs.
+ * OUTSIDE STOP RULE.  For a ray r whose background runs - a survivor of the cull !(bg_lambda_0 < eps) || !(bg_lambda_1 < eps), which
+ * stays exactly as it is - a level's N outside-sphere samples are cut into SEGMENTS of `segment` samples, `segment` the call's value,
+ * a positive multiple of 64; the last segment may be shorter.  The samples are s = 1/r DESCENDING, as neo_composite mode 2 reads
+ * them.  carry_b is mode 2's fp64 product in front of sample b, formed with its own lines: delta_i = s_i - s_{i+1}, the last one
+ * 1e10, no |d| factor, keep = (1 - alpha(sigma * delta)) + 1e-10f, the 64-lane inclusive product scan in fp64, carry *= the round's
+ * last lane.  The RUNNING VALUE at a boundary b (a multiple of `segment`) is v_b = bg_lambda_level[r] * (float)carry_b: one fp32
+ * multiply of the level's RETURNED lambda with the background transmittance that the composite assigns to sample b, bit for bit.  It
+ * is the factor with which everything at or behind b reaches the pixel.  Segment 0 always runs.  Segment k >= 1 runs iff every
+ * earlier boundary b satisfied !(v_b < eps) - a negation, so a NaN keeps marching.  bg_stop[r] = the leading samples evaluated: N or
+ * a boundary; 0 for a culled ray.  bg_value[r] = v at the stop (with bg_stop == N: bg_lambda * (float)(the product over all N
+ * samples)); 0 for a culled ray.  A row at or behind the stop is NOT evaluated and is (0, 0, 0, 0); mode 2 gives it weight exactly 0
+ * and leaves the product unchanged, because alpha(0 * delta) = 0 - also for the last delta 1e10 - and 1.0f + 1e-10f == 1.0f.  The
+ * evaluated samples are a prefix, so their weights are bitwise those of the call with outside == 0.
+ * LEVELS.  Level 1 follows the rule.  Level 0 follows it only with coarse != 0: its weights feed the level-1 outside resampling, so
+ * stopping it moves positions, and NO bound is claimed for that mode (as for the inside `coarse`).  A level that does not follow the
+ * rule is the compact launch of neo_tp_render_culled: bg_stop = N for a survivor.
+ * eps == 0 stops nothing (v >= 0 or NaN): all twelve outputs are bitwise neo_tp_render's.  outside == 0: every output is bitwise
+ * neo_tp_render_accelerated's (use_grid != 0) or neo_tp_render_terminating's (use_grid == 0), launch for launch.
+ * BOUND (coarse == 0, level 1), against the SAME call with outside == 0.  The foreground of both levels runs first and reads nothing
+ * of the background: fg_rgb, fg_acc, bg_lambda, the inside stop and the cull set are bitwise equal in the two calls; so are the
+ * level-0 outside weights and therefore the level-1 outside positions.  Let a ray's level-1 outside march stop at b, lam = its
+ * bg_lambda_1, T_b = carry_b.  With T_{i+1} = T_i (1 - alpha_i + 1e-10), a weight is w_i = alpha_i T_i = T_i - T_{i+1} + 1e-10 T_i,
+ * so the skipped weights sum to at most T_b (1 + N 1e-10).  Colours lie in (-0.001, 1.001); s in [0, 1].  v_b carries two fp32
+ * roundings (the conversion of carry_b and the multiply), so lam T_b <= v_b (1 + 2^-24)^2 < eps (1 + 2^-23) for normal v_b.  Hence
+ * |rgb change| = lam |sum_skipped w_i c_i| < 1.001 (1 + N 1e-10)(1 + 2^-23) eps < 1.0011 eps per channel and |depth change| <=
+ * lam sum_skipped w_i s_i < 1.0000002 eps in real arithmetic.  The tests assert 1.003 eps for both: the margin 0.0019 eps covers
+ * the fp32 rounding of the two sums being compared (about 3e-7 lam) wherever eps > 2e-4 lam, as in the BOUND of the inside rule.
+ * A ray whose outside march never stops is bitwise the ray of the call with outside == 0.
+ * On the device the march runs on the COMPACT background rows of the culled frame (row k belongs to the k-th survivor; the count is
+ * a device word): per window and segment the alive rows are compacted on the running value, their samples of the segment go
+ * through the outside evaluator's compact launch as single points carrying the ray's origin, direction and far, and scatter into
+ * zero-filled rows.  Windows: skip_window x N_level / segment rows, as for the inside march; results do not depend on them.  The
+ * composites, the resampling, the merges, the flags and the lanes are the culled frame's.  No call synchronises the device.
+ * samples0 / samples1 (may be NULL, and any pointer in them): neo_tp_accel_samples' fields, then bg_stop (R) int32, bg_value (R) and
+ * bg_rows (R,N_level,4), the level's outside-sphere rows dense by ray (zero rows for culled rays and behind bg_stop).  kept (may be
+ * NULL): int64[4] on the device, the evaluated samples inside the sphere per level, then outside the sphere per level (= the sums of
+ * stop and of bg_stop).  survivors_out: the rays whose background ran. */
+typedef struct {
+    float* fg_t; float* fg_w; float* bg_s; int* stop; uint8_t* fg_keep; float* fg_rows;
+    int* bg_stop; float* bg_value; float* bg_rows;
+} neo_tp_march_samples;
+int neo_tp_render_marching(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                           const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                           const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps, int segment, int coarse,
+                           int use_grid, int outside, const neo_tp_march_samples* samples0, const neo_tp_march_samples* samples1,
+                           long long* kept, int* survivors_out, void* stream);
+
+/* The OUTSIDE STOP RULE on caller rows: rgbsigma (R,N,4), s (R,N) descending, bg_lambda (R) -> stop (R) int32, the samples a march
+ * over these rows evaluates (every row is treated as a ray whose background runs), and value (R), the running value at the stop.
+ * The kernel is the frame's.  R == 0 is a valid call.  Touches no context-owned memory. */
+int neo_tp_termination_stops_outside(neo_ctx* ctx, const float* rgbsigma, const float* s, const float* bg_lambda, int R, int N,
+                                     float eps, int segment, int* stop, float* value, void* stream);
 
 /* ---- scene encoder: pillar stage -------------------------------------------------------- */
 /* Weights of the pillar stage of GridEncoder (models/neo360/encoder_tp_fusion_conv.py:263-279, :364-373).

@@ -66,6 +66,10 @@ class TpAccelSamples(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("fg_t", "fg_w", "bg_s", "stop", "fg_keep", "fg_rows")]
 
 
+class TpMarchSamples(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("fg_t", "fg_w", "bg_s", "stop", "fg_keep", "fg_rows", "bg_stop", "bg_value", "bg_rows")]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares
 SIGNATURES = {
     "neo_abi_version": (_i, []),
@@ -136,6 +140,10 @@ SIGNATURES = {
                                        ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), _f, _i, _i,
                                        ctypes.POINTER(TpAccelSamples), ctypes.POINTER(TpAccelSamples), _vp, _vp, _vp]),
     "neo_tp_termination_stops": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "neo_tp_render_marching": (_i, [_vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _i, _i,
+                                    ctypes.POINTER(TpLevelOut), ctypes.POINTER(TpLevelOut), _f, _i, _i, _i, _i,
+                                    ctypes.POINTER(TpMarchSamples), ctypes.POINTER(TpMarchSamples), _vp, _vp, _vp]),
+    "neo_tp_termination_stops_outside": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
     "neo_enc_upload": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_enc_floorplans": (_i, [_vp, _vp, _i, _i, _i, _f, _f, c_float_p, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "neo_enc_train_tape_floats": (ctypes.c_long, [_i, _i, _i, _i]),

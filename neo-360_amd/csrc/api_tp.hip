@@ -198,7 +198,7 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
 }
 
 // Rays per window of the skipping frame (neo_tp_set_skip_window replaces it).  A window bounds the extra workspace: a compact row
-// is 64 B in W[12] and 128 B in the direction-sum table, so 4096 rays x 385 samples are 1.58 M rows = 101 MB + 202 MB, whatever
+// is 68 B in W[12] and 128 B in the direction-sum table, so 4096 rays x 385 samples are 1.58 M rows = 107 MB + 202 MB, whatever
 // the frame's size; the frame's 75 windows per level cost 5 small launches each.
 constexpr int SKIP_WINDOW_DEFAULT = 4096;
 
@@ -302,6 +302,62 @@ int tp_eval_accelerated(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, in
                         float* fg_out, float eps, int segment, const TpTermState& st, int win, const uint32_t* bits, int G,
                         long long* kept) {
     return tp_eval_terminating(ctx, f, a, level, fg_t, far, N, fg_out, eps, segment, st, win, kept, bits, G);
+}
+
+// Per-row state of an outside-sphere march in W[13], by COMPACT background row (it follows the inside marches of both levels, whose
+// TpTermState is dead by then): [carry fp64 R | lam_c fp32 R | alive fp32 R | value fp32 R | stop int R | the alive compaction of one
+// window].  alive is what the compaction reads: 1 in front of segment 0, then the running value; -1 behind the survivor count.
+struct TpOutState {
+    double* carry;
+    float *lam_c, *alive, *value;
+    int *stop, *cws;
+    static size_t bytes(size_t r, int win) { return r * 24 + neo::cull_ws_ints(win) * sizeof(int); }
+    void carve(void* base, size_t r) {
+        carry = static_cast<double*>(base);
+        lam_c = reinterpret_cast<float*>(carry + r);
+        alive = lam_c + r;
+        value = alive + r;
+        stop = reinterpret_cast<int*>(value + r);
+        cws = stop + r;
+    }
+};
+
+// The outside-sphere evaluation of one level of a marching frame (neo_tp_render_marching with `outside`; include/neo360_hip.h:
+// OUTSIDE STOP RULE) into zero-filled COMPACT rows bg_out: tp_eval_terminating's window and segment loop on the compact background
+// rows of the culled frame.  map / count: the frame's survivors; lam: the level's dense lambdas; bg_s: the level's positions, row k
+// at bg_s + k N (level 0: R equal rows).  The survivor count lives on the device, so the windows cover all R rows and every launch
+// behind the count finds no alive row.  ot.stop: samples marched per compact row; *kept: their sum.
+int tp_eval_outside(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* bg_s, const float* far, int N,
+                    float* bg_out, const float* lam, const int* map, const int* count, float eps, int segment, const TpOutState& ot,
+                    int win, long long* kept, bool dens) {
+    hipStream_t s = f.s;
+    const int seg = std::min(segment, N);
+    const size_t cap = static_cast<size_t>(win) * seg;
+    if (ctx->ws[12].reserve(neo::occ_rows_bytes(cap))) return NEO_ERR_NOMEM;
+    neo::OccRows w;
+    w.carve(ctx->ws[12].p, cap);
+    HIP_TRY(hipMemsetAsync(bg_out, 0, static_cast<size_t>(a.R) * N * 16, s));
+    neo::launch_tout_init(lam, map, count, a.R, ot.lam_c, ot.alive, ot.value, ot.stop, 0, kept, 0, s);
+    neo::launch_occ_iota(w.iota, static_cast<int>(cap), s);
+    for (int k0 = 0; k0 < a.R; k0 += win) {
+        const int rows = std::min(win, a.R - k0);
+        for (int b0 = 0; b0 < N; b0 += segment) {
+            const int len = std::min(segment, N - b0);
+            const int P = rows * len;
+            neo::launch_cull_compact(ot.alive + k0, ot.alive + k0, rows, eps, ot.cws, nullptr, s);
+            const int* map_w = neo::cull_map_of(ot.cws, rows);
+            const int* count_w = neo::cull_count_of(ot.cws, rows);
+            neo::launch_tout_emit(a.rays_o, a.rays_d, a.viewdirs, far, bg_s, N, map, map_w, count_w, k0, rows, a.R, N, b0, len, a.chunk, w,
+                                  kept, s);
+            if (int rc = tp_launch(ctx, ctx->tp[2 + level], f.sc, f.views, w.o, w.d, w.v, w.t, w.far, P, 1, a.chunk, w.out, s, w.iota,
+                                   w.count, dens))
+                return rc;
+            neo::launch_term_scatter(w, P, bg_out, s);
+            neo::launch_tout_advance(bg_out, bg_s, N, N, b0, b0 + len, segment, eps, map_w, count_w, rows, k0, ot.lam_c, ot.carry, ot.value,
+                                     ot.alive, ot.stop, s);
+        }
+    }
+    return NEO_OK;
 }
 
 // may the level-0 launches of a frame render be density-only?  Yes when the caller takes none of the level's colours or depth
@@ -738,10 +794,15 @@ int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d,
 // still let light through) in which the inside-sphere march of level 1 - with `coarse` also of level 0 - stops by the STOP RULE.
 // The one driver of neo_tp_render_terminating (use_occ = false: an installed grid is not read, bits stays NULL and every launch below
 // is that call's own) and of neo_tp_render_accelerated (use_occ = true: with a grid installed the marches also obey the KEEP RULE -
-// tp_eval_accelerated - and a level 0 without `coarse` is tp_eval_skipping).  The caller has entered the context.
+// tp_eval_accelerated - and a level 0 without `coarse` is tp_eval_skipping).  `outside` (neo_tp_render_marching only): the
+// outside-sphere march of level 1 - with `coarse` also of level 0 - obeys the OUTSIDE STOP RULE (tp_eval_outside) instead of the
+// culled frame's compact launch.  kept: int64[2], the inside counters; kept_out (may be NULL): int64[2], the outside ones.  With
+// outside == false, kept_out == NULL and no bg_stop / bg_value / bg_rows asked for, every launch below is the parent's.  The caller
+// has entered the context.
 static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
-                              float eps, int segment, int coarse, const neo_tp_accel_samples* samples0,
-                              const neo_tp_accel_samples* samples1, long long* kept, int* survivors_out, bool use_occ) {
+                              float eps, int segment, int coarse, const neo_tp_march_samples* samples0,
+                              const neo_tp_march_samples* samples1, long long* kept, long long* kept_out, int* survivors_out,
+                              bool use_occ, bool outside) {
     const float *rays_o = a.rays_o, *rays_d = a.rays_d, *viewdirs = a.viewdirs;
     const int R = a.R, chunk = a.chunk, n_fine = a.n_fine;
     TpFrame::Own own;
@@ -753,6 +814,7 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
     if (f.empty) {
         if (survivors_out) HIP_TRY(hipMemsetAsync(survivors_out, 0, sizeof(int), s));
         if (kept) HIP_TRY(hipMemsetAsync(kept, 0, 2 * sizeof(long long), s));
+        if (kept_out) HIP_TRY(hipMemsetAsync(kept_out, 0, 2 * sizeof(long long), s));
         return NEO_OK;
     }
     const int N0 = f.N0, N1 = f.N1;
@@ -780,11 +842,13 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
         REQUIRE(r * N1 <= 2147483647UL - 1024, "too many points for 32-bit indices");
     TpDenseRows rows;
     if (rows.reserve(W, r, N0, N1) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)) ||
-        W[13].reserve(std::max(TpTermState::bytes(r, win_max, candidates), skip_keep)))
+        W[13].reserve(std::max({TpTermState::bytes(r, win_max, candidates), skip_keep, TpOutState::bytes(r, win_max)})))
         return NEO_ERR_NOMEM;
     auto [far, fg_t0, bg_s0, fg_out, bg_out, fg_w0, bg_w0, fg_t1, bg_s1] = rows;
     TpTermState st;
     st.carve(W[13].p, r, win_max);
+    TpOutState ot;      // the same bytes, read only after the inside marches of both levels are done
+    ot.carve(W[13].p, r);
     float* scratch = W[9].as<float>();    // as neo_tp_render_culled
     float* c_bg_rgb = scratch + r * 18;
     float* c_bg_depth = scratch + r * 21;
@@ -797,7 +861,7 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
     neo::launch_tp_level0(far, f.edges, R, N0, f.near, fg_t0, bg_s0, s);
     const bool sigma0 = level0_sigma_only(level0);
     const neo_tp_level_out* los[2] = {level0, level1};
-    const neo_tp_accel_samples* sos[2] = {samples0, samples1};
+    const neo_tp_march_samples* sos[2] = {samples0, samples1};
     struct LevelFg { float* fg_rgb; float* fg_depth; float* fg_acc; float* lam; float* bg_rgb; } L[2];
     for (int level = 0; level < 2; ++level) {
         const neo_tp_level_out* lo = los[level];
@@ -809,7 +873,7 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
     for (int level = 0; level < 2; ++level) {
         const int N = level == 0 ? N0 : N1;
         const float* fg_t = level == 0 ? fg_t0 : fg_t1;
-        const neo_tp_accel_samples* so = sos[level];
+        const neo_tp_march_samples* so = sos[level];
         const bool dens = level == 0 && sigma0;
         uint8_t* fg_keep = use_occ && so ? so->fg_keep : nullptr;       // the KEEP RULE on the whole row, behind the stops as well
         if (level == 1 || coarse) {
@@ -841,15 +905,44 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
 
     neo::launch_cull_compact(L[0].lam, L[1].lam, R, eps, cws, survivors_out, s);
 
-    // background on the survivors, exactly as neo_tp_render_culled
-    if (int rc = tp_launch(ctx, ctx->tp[2], sc, views, rays_o, rays_d, viewdirs, bg_s0, far, R, N0, chunk, bg_out, s, map, count, sigma0)) return rc;
+    // One level's outside-sphere rows into the compact bg_out.  A level that follows the OUTSIDE STOP RULE marches (tp_eval_outside);
+    // any other is neo_tp_render_culled's compact launch, and only a caller of the outside outputs pays for more: the counter, and
+    // the rule's own kernel run to the end of the row (eps = 0 stops nothing) for stop = N and the running value there.
+    auto background = [&](int level, const float* bg_s, int N, bool dens) -> int {
+        const neo_tp_march_samples* so = sos[level];
+        long long* kept_l = kept_out ? kept_out + level : nullptr;
+        if (outside && (level == 1 || coarse)) {
+            if (int rc = tp_eval_outside(ctx, f, a, level, bg_s, rows.far, N, rows.bg_out, L[level].lam, map, count, eps, segment, ot,
+                                         win_of[level], kept_l, dens))
+                return rc;
+        } else {
+            if (int rc = tp_launch(ctx, ctx->tp[2 + level], sc, views, rays_o, rays_d, viewdirs, bg_s, rows.far, R, N, chunk, rows.bg_out, s, map,
+                                   count, dens))
+                return rc;
+            const bool value = so && so->bg_value;
+            if (kept_l || value || (so && so->bg_stop))
+                neo::launch_tout_init(L[level].lam, map, count, R, value ? ot.lam_c : nullptr, nullptr, value ? ot.value : nullptr, ot.stop,
+                                      N, kept_l, N, s);
+            if (value)
+                neo::launch_tout_advance(rows.bg_out, bg_s, N, N, 0, N, segment, 0.0f, nullptr, count, R, 0, ot.lam_c, nullptr, ot.value, nullptr,
+                                         ot.stop, s);
+        }
+        if (so) {
+            neo::launch_tout_by_slot(ot.stop, ot.value, slot, R, so->bg_stop, so->bg_value, s);
+            if (so->bg_rows) neo::launch_term_rows_by_slot(rows.bg_out, slot, R, N * 4, so->bg_rows, s);
+        }
+        return NEO_OK;
+    };
+
+    // background on the survivors, in neo_tp_render_culled's order
+    if (int rc = background(0, bg_s0, N0, sigma0)) return rc;
     neo::launch_composite(2, bg_out, bg_s0, N0, nullptr, nullptr, R, N0, 0, sigma0 ? nullptr : c_bg_rgb, nullptr,
                           sigma0 ? nullptr : c_bg_depth, bg_w0, nullptr, s, count);
     if (neo::launch_resample(bg_s0, N0, bg_w0, f.u, 0, R, N0, n_fine, 1, bg_s1, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
     if (level0 && (level0->rgb || level0->depth || level0->bg_rgb))
         neo::launch_tp_merge_culled(L[0].fg_rgb, L[0].fg_depth, L[0].lam, c_bg_rgb, c_bg_depth, slot, R, level0->rgb, level0->depth,
                                     L[0].bg_rgb, s);
-    if (int rc = tp_launch(ctx, ctx->tp[3], sc, views, rays_o, rays_d, viewdirs, bg_s1, far, R, N1, chunk, bg_out, s, map, count)) return rc;
+    if (int rc = background(1, bg_s1, N1, false)) return rc;
     neo::launch_composite(2, bg_out, bg_s1, N1, nullptr, nullptr, R, N1, 0, c_bg_rgb, nullptr, c_bg_depth, nullptr, nullptr, s, count);
     if (level1 && (level1->rgb || level1->depth || level1->bg_rgb))
         neo::launch_tp_merge_culled(L[1].fg_rgb, L[1].fg_depth, L[1].lam, c_bg_rgb, c_bg_depth, slot, R, level1->rgb, level1->depth,
@@ -867,12 +960,13 @@ int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* ra
                               int* survivors_out, void* stream) {
     ENTER(ctx);
     const neo_tp_term_samples* given[2] = {samples0, samples1};
-    neo_tp_accel_samples so[2];
+    neo_tp_march_samples so[2];
     for (int l = 0; l < 2; ++l)
-        if (given[l]) so[l] = {given[l]->fg_t, given[l]->fg_w, given[l]->bg_s, given[l]->stop, nullptr, given[l]->fg_rows};
+        if (given[l])
+            so[l] = {given[l]->fg_t, given[l]->fg_w, given[l]->bg_s, given[l]->stop, nullptr, given[l]->fg_rows, nullptr, nullptr, nullptr};
     return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
-                              level1, eps, segment, coarse, samples0 ? &so[0] : nullptr, samples1 ? &so[1] : nullptr, kept,
-                              survivors_out, false);
+                              level1, eps, segment, coarse, samples0 ? &so[0] : nullptr, samples1 ? &so[1] : nullptr, kept, nullptr,
+                              survivors_out, false, false);
 }
 
 // Occupancy skipping and early termination together (include/neo360_hip.h: ACCELERATED FRAME): the driver above with the grid read.
@@ -882,8 +976,28 @@ int neo_tp_render_accelerated(neo_ctx* ctx, const float* rays_o, const float* ra
                               const neo_tp_accel_samples* samples0, const neo_tp_accel_samples* samples1, long long* kept,
                               int* survivors_out, void* stream) {
     ENTER(ctx);
+    const neo_tp_accel_samples* given[2] = {samples0, samples1};
+    neo_tp_march_samples so[2];
+    for (int l = 0; l < 2; ++l)
+        if (given[l])
+            so[l] = {given[l]->fg_t, given[l]->fg_w, given[l]->bg_s, given[l]->stop, given[l]->fg_keep, given[l]->fg_rows, nullptr, nullptr,
+                     nullptr};
     return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
-                              level1, eps, segment, coarse, samples0, samples1, kept, survivors_out, true);
+                              level1, eps, segment, coarse, samples0 ? &so[0] : nullptr, samples1 ? &so[1] : nullptr, kept, nullptr,
+                              survivors_out, true, false);
+}
+
+// The driver itself (include/neo360_hip.h: MARCHING FRAME): use_grid chooses between the two calls above, `outside` adds the OUTSIDE
+// STOP RULE; kept is int64[4], inside then outside per level.
+int neo_tp_render_marching(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                           const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                           const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps, int segment, int coarse,
+                           int use_grid, int outside, const neo_tp_march_samples* samples0, const neo_tp_march_samples* samples1,
+                           long long* kept, int* survivors_out, void* stream) {
+    ENTER(ctx);
+    return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
+                              level1, eps, segment, coarse, samples0, samples1, kept, kept ? kept + 2 : nullptr, survivors_out,
+                              use_grid != 0, outside != 0);
 }
 
 // Object-level render: the two inside-sphere MLPs between a caller-given per-ray interval, on the rays that have one.

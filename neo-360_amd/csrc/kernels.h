@@ -433,9 +433,10 @@ void launch_occ_keep(const float* rays_o, const float* rays_d, const float* t, i
                      hipStream_t s);
 // One window's compact rows, `cap` of them, in one buffer of occ_rows_bytes(cap): row k is ONE kept point - the origin, direction and
 // t of its ray, the view direction of its quirk-Q1 ray, dst = its point index in the window - and out its (rgb, sigma) row; iota =
-// the identity map of the evaluator's compact launch; count the device word; totals the compaction's per-workgroup sums.
+// the identity map of the evaluator's compact launch; count the device word; totals the compaction's per-workgroup sums.  far: the
+// ray's sphere exit, which only the outside-sphere evaluators read (terminate_outside.hip fills it; the inside paths leave it alone).
 struct OccRows {
-    float *out, *o, *d, *v, *t;
+    float *out, *o, *d, *v, *t, *far;
     int *dst, *iota, *count, *totals;
     void carve(void* base, size_t cap);
 };
@@ -467,6 +468,27 @@ void launch_term_advance(const float* rgbsigma, const float* t, const float* ray
                          int* stop, hipStream_t s);
 // dst (R,N) = src_c row slot[ray], zeros where slot[ray] < 0
 void launch_term_rows_by_slot(const float* src_c, const int* slot, int R, int N, float* dst, hipStream_t s);
+
+// terminate_outside.hip - the outside-sphere march of neo_tp_render_marching (include/neo360_hip.h: OUTSIDE STOP RULE) on the COMPACT
+// background rows of the culled frame: row k belongs to ray map[k], k < *count.
+// per compact row k < R: lam_c = lam[map[k]], alive = 1 and stop = stop_value where k < *count; alive = -1 (dead at every eps >= 0),
+// stop = 0 and lam_c = 0 behind the count; value = 0; *kept (may be null) = kept_per_row x *count.  lam_c / alive / value may be null.
+void launch_tout_init(const float* lam, const int* map, const int* count, int R, float* lam_c, float* alive, float* value, int* stop,
+                      int stop_value, long long* kept, long long kept_per_row, hipStream_t s);
+// the point rows (OccRows with far) of samples b0 .. b0 + len - 1 of compact rows k0 + map_w[kk], kk < *count_w <= rows: origin,
+// direction and far of ray map[k], s = s_rows[k s_stride + j], the view direction of the quirk-Q1 ray of the dense launch of the
+// level's full N on the DENSE ray index, dst = k N + j; *w.count = *count_w len, also added to *kept_sum when not null
+void launch_tout_emit(const float* rays_o, const float* rays_d, const float* viewdirs, const float* far, const float* s_rows,
+                      long s_stride, const int* map, const int* map_w, const int* count_w, int k0, int rows, int R, int N, int b0, int len,
+                      int chunk, const OccRows& w, long long* kept_sum, hipStream_t s);
+// the OUTSIDE STOP RULE over samples b0 .. b_end - 1 (whole segments) of rows k0 + map_w[kk], kk < *count_w (map_w / count_w null:
+// rows 0 .. n_rows - 1): carry (fp64 per row; may be null when b0 == 0 and nothing continues), value = lam_c[k] (float)carry at the
+// stop, also written to alive when not null, stop = samples marched
+void launch_tout_advance(const float* rgbsigma, const float* s_rows, long s_stride, int N, int b0, int b_end, int segment, float eps,
+                         const int* map_w, const int* count_w, int n_rows, int k0, const float* lam_c, double* carry, float* value,
+                         float* alive, int* stop, hipStream_t s);
+// dense by ray through the slot table: stop (R) / value (R) = the compact entry at slot[ray], 0 where slot[ray] < 0; either may be null
+void launch_tout_by_slot(const int* stop_c, const float* value_c, const int* slot, int R, int* stop, float* value, hipStream_t s);
 
 // accelerate.hip - the segment launch of neo_tp_render_accelerated: launch_term_emit restricted to the samples that the KEEP RULE keeps
 // The candidates are launch_term_emit's rows (sample b0 + p % len of ray r0 + map[p / len], p < *alive len); keep (rays x len bytes)

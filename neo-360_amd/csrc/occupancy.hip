@@ -156,10 +156,11 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_from_sigma(const float* __res
 void OccRows::carve(void* base, size_t cap) {
     float* f = static_cast<float*>(base);
     out = f, o = f + cap * 4, d = f + cap * 7, v = f + cap * 10, t = f + cap * 13;      // the float4 rows first: 16-byte aligned
-    int* i = reinterpret_cast<int*>(f + cap * 14);
+    far = f + cap * 14;
+    int* i = reinterpret_cast<int*>(f + cap * 15);
     dst = i, iota = i + cap, count = i + 2 * cap, totals = count + 1;
 }
-size_t occ_rows_bytes(size_t cap) { return cap * 64 + (1 + (size_t)occ_blocks((long)cap)) * sizeof(int); }
+size_t occ_rows_bytes(size_t cap) { return cap * 68 + (1 + (size_t)occ_blocks((long)cap)) * sizeof(int); }
 
 void launch_occ_keep(const float* rays_o, const float* rays_d, const float* t, int R, int N, const uint32_t* bits, int G, uint8_t* keep,
                      hipStream_t s) {

@@ -7,7 +7,7 @@
 //   tp_march_compact    the two-level inside-sphere march on compact rows under a device count (neo_tp_render_objects, every
 //                       window of neo_tp_render_instances).
 //
-// neo_tp_render_culled and neo_tp_render_terminating / neo_tp_render_accelerated (one driver, tp_render_marching in api_tp.hip) have
+// neo_tp_render_culled and neo_tp_render_terminating / neo_tp_render_accelerated / neo_tp_render_marching (one driver, tp_render_marching in api_tp.hip) have
 // a launch order of their own - the foreground of both levels first - and take the preamble and the dense row layout only.
 #pragma once
 #include "ctx.h"

@@ -471,6 +471,8 @@ class NeRF_TP(_HipModule):
         self.last_terminate_survivors = None # int32 device tensor: rays of that call whose background ran
         self.last_accel_kept = None          # int64[2] device tensor: evaluated inside-sphere samples per level of the last render_accelerated call
         self.last_accel_survivors = None     # int32 device tensor: rays of that call whose background ran
+        self.last_march_kept = None          # int64[4] device tensor: evaluated samples inside / outside the sphere per level of the last render_marching call
+        self.last_march_survivors = None     # int32 device tensor: rays of that call whose background ran
 
     @property
     def cull_background(self):
@@ -1293,6 +1295,81 @@ class NeRF_TP(_HipModule):
         out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
         if return_samples:
             names = ("fg_t", "fg_w", "bg_s", "stop", "fg_keep") + (("fg_rows",) if return_samples == "rows" else ())
+            out.append([tuple(t[k] for k in names) for t in levels])
+        return out
+
+    # ---- early termination carried through the outside-sphere march ------------------------------------------------------------
+
+    @torch.no_grad()
+    def render_marching(self, rays, eps, chunk=None, segment=64, coarse=False, outside=True, grid=True, return_samples=False,
+                        fine_only=False):
+        """The driver behind `render_terminating` (grid=False) and `render_accelerated` (grid=True) with the early termination
+        carried through the OUTSIDE-sphere march (neo_tp_render_marching; include/neo360_hip.h: OUTSIDE STOP RULE).  With
+        outside=True a ray whose background runs - the cull of those two calls, unchanged - marches its level-1 outside samples in
+        segments of `segment`: segment 0 always, segment k >= 1 iff at every earlier boundary b the running value bg_lambda *
+        (float)carry_b (`ops.termination_stops_outside`: one fp32 multiply of the level's returned lambda with the outside
+        composite's own transmittance in front of sample b) was not below eps.  A sample behind bg_stop is not evaluated: its row is
+        zero and its weight exactly 0.  Level 0 follows the rule only with coarse=True, which moves the level-1 outside positions: no
+        bound is claimed for that mode.
+
+        outside=False is bitwise `render_accelerated` (grid=True) or `render_terminating` (grid=False); eps = 0 is bitwise
+        `forward(..., out_depth=True)` (with no grid read).  With coarse=False, against the same call with outside=False: the
+        foreground outputs, the inside stops and the cull set are bitwise equal, a ray whose outside march never stops is bitwise
+        equal, and a stopped ray's level-1 rgb and depth differ by less than 1.003 * eps.  ValueError, before any device access, for
+        eps outside [0, 1) or NaN, or a segment that is not a positive multiple of 64; NeoError when grid=True and the installed
+        grid belongs to another context.
+
+        Returns the two level tuples of `forward(..., out_depth=True)` (fine_only=True: None for level 0); with return_samples a
+        third element holds per level `render_accelerated`'s tuple (fg_t, fg_w, bg_s, stop, fg_keep) followed by bg_stop (B,) int32
+        (0 for a culled ray) and bg_value (B,), the running value at the stop (0 for a culled ray) - and, with
+        return_samples="rows", fg_rows (B,N,4) and bg_rows (B,N,4) behind them (zero rows for culled rays).
+        `self.last_march_kept` (int64[4]: evaluated samples inside the sphere per level, then outside the sphere per level) and
+        `self.last_march_survivors` (int32: rays whose background ran) stay on the device; nothing is read back."""
+        eps, segment = ops._check_termination(eps, segment, "render_marching")
+        call = self._frame_call(rays, chunk, use_grid=True)
+        B, dev = call.B, call.dev
+        levels = []
+        counts = []
+
+        def launch():
+            ctx = call.ctx
+            if grid and self._occupancy is not None and self._occ_ctx is not ctx:
+                raise _lib.NeoError("the occupancy grid does not belong to this scene and device: install it again")
+            self._set_mode(ctx, "_skip_window", "neo_tp_set_skip_window", int(self.skip_window or 0))
+            structs, sample_structs = [], []
+            for level, n in enumerate(call.n):
+                if level == 0 and fine_only:
+                    t, struct = {}, None
+                else:
+                    t, struct = self._level_out(B, dev)
+                structs.append(struct)
+                if return_samples:
+                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev),
+                             stop=torch.empty(B, dtype=torch.int32, device=dev),
+                             # grid=False: nothing is skipped and the library writes no mask
+                             fg_keep=(torch.empty if grid else torch.ones)(B, n, dtype=torch.bool, device=dev),
+                             bg_stop=torch.empty(B, dtype=torch.int32, device=dev), bg_value=torch.empty(B, device=dev))
+                    if return_samples == "rows":
+                        t["fg_rows"] = torch.empty(B, n, 4, device=dev)
+                        t["bg_rows"] = torch.empty(B, n, 4, device=dev)
+                    sample_structs.append(_lib.TpMarchSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpMarchSamples._fields_)))
+                else:
+                    sample_structs.append(None)
+                levels.append(t)
+            counts.append(torch.empty(4, dtype=torch.int64, device=dev))
+            counts.append(torch.empty((), dtype=torch.int32, device=dev))
+            _lib.check(ctx.lib.neo_tp_render_marching(
+                *call.ray_args, *call.frame_args, *(ctypes.byref(x) if x is not None else None for x in structs), eps, segment,
+                int(bool(coarse)), int(bool(grid)), int(bool(outside)),
+                *(ctypes.byref(x) if x is not None else None for x in sample_structs), counts[0].data_ptr(), counts[1].data_ptr(),
+                ctx.stream()))
+            self._after_call(ctx)
+            return [v for t in levels for v in t.values()] + counts
+        call.run(launch)
+        self.last_march_kept, self.last_march_survivors = counts
+        out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
+        if return_samples:
+            names = ("fg_t", "fg_w", "bg_s", "stop", "fg_keep", "bg_stop", "bg_value") + (("fg_rows", "bg_rows") if return_samples == "rows" else ())
             out.append([tuple(t[k] for k in names) for t in levels])
         return out
 

@@ -617,3 +617,31 @@ def termination_stops(rgbsigma, t, rays_d, t_far, eps, segment=64, ctx=None):
     _lib.check(ctx.lib.neo_tp_termination_stops(ctx.handle, ptr(rgbsigma), ptr(t), ptr(rays_d), ptr(t_far), B, N, eps, segment,
                                                 stop.data_ptr(), trans.data_ptr(), ctx.stream()))
     return stop, trans
+
+
+@torch.no_grad()
+def termination_stops_outside(rgbsigma, s, bg_lambda, eps, segment=64, ctx=None):
+    """The OUTSIDE STOP RULE of `NeRF_TP.render_marching` on caller rows (neo_tp_termination_stops_outside): rgbsigma (B,N,4) and
+    s (B,N) on the GPU - what `eval_mlp` returns for the outside-sphere samples of a level and the descending 1/r positions the
+    outside-sphere `composite` (mode 2) reads - and bg_lambda (B,) or (B,1), the level's foreground leftover.  The N samples are cut
+    into segments of `segment` (a positive multiple of 64); a march evaluates segment 0, and segment k >= 1 iff at every earlier
+    boundary b the running value v_b = bg_lambda * (float)carry_b - one fp32 multiply with the composite's own background
+    transmittance in front of sample b - was not below eps (a NaN keeps marching).  Every row counts as a ray whose background runs.
+    Returns (stop (B,) int32, the leading samples such a march evaluates, and value (B,) float32, v at the stop).
+    stop.sum() / (B N) is the share of a level's outside-sphere work the rule would keep: the tool to measure it on trained weights
+    without the frame call."""
+    eps, segment = _check_termination(eps, segment, "termination_stops_outside")
+    if not isinstance(s, torch.Tensor) or s.dim() != 2 or not s.is_floating_point() or s.shape[1] < 1:
+        raise ValueError("termination_stops_outside: s must be a floating-point (B, N) tensor, N >= 1")
+    B, N = s.shape
+    if not isinstance(rgbsigma, torch.Tensor) or tuple(rgbsigma.shape) != (B, N, 4) or rgbsigma.device != s.device:
+        raise ValueError("termination_stops_outside: rgbsigma must be a (%d, %d, 4) tensor on the device of s" % (B, N))
+    if not isinstance(bg_lambda, torch.Tensor) or tuple(bg_lambda.shape) not in ((B,), (B, 1)) or bg_lambda.device != s.device:
+        raise ValueError("termination_stops_outside: bg_lambda must be a (%d,) or (%d, 1) tensor on the device of s" % (B, B))
+    rgbsigma, s, bg_lambda = f32(rgbsigma, "rgbsigma"), f32(s, "s"), f32(bg_lambda.reshape(B), "bg_lambda")
+    ctx = _ctx(s, ctx)
+    stop = torch.empty(B, dtype=torch.int32, device=s.device)
+    value = torch.empty(B, device=s.device)
+    _lib.check(ctx.lib.neo_tp_termination_stops_outside(ctx.handle, ptr(rgbsigma), ptr(s), ptr(bg_lambda), B, N, eps, segment,
+                                                        stop.data_ptr(), value.data_ptr(), ctx.stream()))
+    return stop, value

@@ -407,6 +407,34 @@ def render_accelerated_rays(model, batch, eps, chunk=1024, segment=64, coarse=Fa
 
 
 @torch.no_grad()
+def render_marching_rays(model, batch, eps, chunk=1024, segment=64, coarse=False, outside=True, grid=True, check=True,
+                         on_range="retry_f32"):
+    """Frame of a NeRF_TP module with early ray termination inside AND outside the sphere: the fine level of
+    `model.render_marching(batch, eps, ...)` on every ray of `batch` in one library call, with the reference chunk size passed down.
+    Returns dict(rgb (R,3), depth (R,), acc (R,)) plus `kept_fraction`, a (2,) float64 DEVICE tensor - the share of inside-sphere
+    samples evaluated at level 0 and level 1 - `kept_fraction_outside`, the same for the outside-sphere samples (over ALL rays: a
+    culled ray keeps none), and `culled_fraction`, a float64 DEVICE scalar - the share of rays whose outside-sphere half did not run
+    (reading any of them synchronises, the call does not) - and `target` / `instance_mask` passed through.  outside=False is
+    render_accelerated_rays (grid=True) or render_terminating_rays (grid=False); with eps = 0 and no grid rgb / depth are bitwise
+    render_rays_test's.  check / on_range: the flag read, range-guard retry and latch of render_rays_test (the same code path)."""
+    if not isinstance(model, models.NeRF_TP):
+        raise TypeError("render_marching_rays renders NeRF_TP modules, got %r" % type(model))
+
+    def once():
+        res = model.render_marching(batch, eps, chunk=chunk, segment=segment, coarse=coarse, outside=outside, grid=grid)
+        fine = res[1]
+        R = fine[0].shape[0]
+        n0 = model.num_coarse_samples + 1
+        kept = model.last_march_kept.double()          # scalar divisors travel as kernel arguments: no copy, no wait
+        per = (float(max(R * n0, 1)), float(max(R * (n0 + model.num_fine_samples), 1)))
+        frac = torch.stack([kept[0] / per[0], kept[1] / per[1]])
+        frac_out = torch.stack([kept[2] / per[0], kept[3] / per[1]])
+        culled = 1.0 - model.last_march_survivors.double() / float(max(R, 1))
+        return dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=frac, kept_fraction_outside=frac_out, culled_fraction=culled)
+    return _render_guarded(model, batch, once, check, on_range)
+
+
+@torch.no_grad()
 def render_frame_sharded(model, batch, world, rank, chunk=1024, white_bkgd=False, near=0.2, far=3.0, group=None,
                          gather=True, train_frac=1.0, n_rays=None, out=None, reuse=False, check=True, always_gather=False,
                          info=None, image_width=None):
