@@ -1,11 +1,11 @@
 // Occupancy skipping and early ray termination TOGETHER (neo_tp_render_accelerated): the point list of one segment of a terminating
 // march holds only the samples that the installed occupancy grid keeps.  This file holds the one device-side piece that neither
-// parent has - a fused classify + compact over the CANDIDATES of a segment launch; the driver is tp_eval_accelerated (api_tp.hip),
-// and everything else of a segment (k_term_scatter, k_term_advance on rows in which a skipped sample is a zero row) is terminate.hip's.
+// parent has - a fused classify + compact over the CANDIDATES of a segment launch; the driver is tp_eval_march with a grid (api_tp.hip),
+// and everything else of a segment (k_march_scatter, k_march_advance on rows in which a skipped sample is a zero row) is march.hip's.
 //
 // CANDIDATES.  One window (rays r0 .. of the frame's R), one segment (samples b0 .. b0 + len - 1 of the level's N).  The alive rays
 // come from launch_cull_compact on the running transmittance: map[k], k < *alive (a device word), ascending.  Candidate
-// p < *alive len is sample j = b0 + p % len of ray r0 + map[p / len] - k_term_emit's row order.
+// p < *alive len is sample j = b0 + p % len of ray r0 + map[p / len] - k_march_emit's row order.
 //
 //   k_acc_keep   the totals launch of compact.h on candidates: a workgroup owns 1024 consecutive candidates in the 4 x 256 layout
 //                of k_occ_keep, applies occ_keep_point (the KEEP RULE) to x = o + t d of each, writes the keep byte and its kept count;
@@ -19,6 +19,7 @@
 // totals are 0 and so is the count.  No atomics, no spinning: the int64 counter is bumped by that one thread, behind the previous
 // segment in stream order.
 #include "common.h"
+#include "march.h"
 #include "occ_points.h"
 #include "tp_frame.h"
 

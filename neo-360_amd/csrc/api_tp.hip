@@ -1,5 +1,6 @@
 // NeO-360 (NeRF_TP) entry points of the C ABI: weight / scene upload and the
 // two-level, two-region render (neo360/model.py:266-581).
+#include "march.h"
 #include "tp_frame.h"
 
 #include <algorithm>
@@ -232,129 +233,77 @@ int tp_eval_skipping(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int l
     return NEO_OK;
 }
 
-// Per-ray state of a terminating level in W[13]: [carry fp64 R | trans fp32 R | stop int R | the alive compaction of one window |
-// with a grid (neo_tp_render_accelerated): one keep byte per candidate of one segment launch]
-struct TpTermState {
+// Per-row state of one region's march in W[13] (march.h: a row is a ray inside the sphere, a COMPACT background row outside):
+// inside  [carry fp64 R | alive fp32 R | stop int R | the alive compaction of one window | with a grid: one keep byte per candidate of
+//          one segment launch];
+// outside [carry fp64 R | lam_c fp32 R | alive fp32 R | value fp32 R | stop int R | the alive compaction of one window].
+// alive is what the compaction reads: 1 in front of segment 0, then the running value; outside, -1 behind the survivor count.  The
+// outside march follows the inside marches of both levels, whose state is dead by then: the two carvings share the bytes.
+struct TpMarchState {
     double* carry;
-    float* trans;
-    int* stop;
-    int* cws;
+    float *lam_c, *alive, *value;      // lam_c, value: outside only (null inside)
+    int *stop, *cws;
     uint8_t* keep;
-    static size_t bytes(size_t r, int win, size_t candidates = 0) { return r * 16 + neo::cull_ws_ints(win) * sizeof(int) + candidates; }
-    void carve(void* base, size_t r, int win = 0) {
+    static size_t bytes(bool outside, size_t r, int win, size_t candidates = 0) {
+        return r * (outside ? 24 : 16) + neo::cull_ws_ints(win) * sizeof(int) + candidates;
+    }
+    void carve(void* base, bool outside, size_t r, int win) {
         carry = static_cast<double*>(base);
-        trans = reinterpret_cast<float*>(carry + r);
-        stop = reinterpret_cast<int*>(trans + r);
+        float* f = reinterpret_cast<float*>(carry + r);
+        lam_c = outside ? f : nullptr;
+        alive = outside ? f + r : f;
+        value = outside ? f + 2 * r : nullptr;
+        stop = reinterpret_cast<int*>(alive + (outside ? 2 : 1) * r);
         cws = stop + r;
         keep = reinterpret_cast<uint8_t*>(cws + neo::cull_ws_ints(win));
     }
 };
 
-// The inside-sphere evaluation of one level of a terminating frame (neo_tp_render_terminating; include/neo360_hip.h: STOP RULE) into
-// zero-filled dense rows.  Per window of rays and per segment: compact the alive rays (launch_cull_compact on the running
-// transmittance: !(trans < eps), ascending ray order, the count on the device), emit their point rows of the segment, ONE compact
-// launch of the level's evaluator on single points (as tp_eval_skipping), scatter, advance.  A point list has at most
-// skip_window x N rows - the bound, the buffer (W[12]) and the knob of the skipping frame - so a window holds skip_window N / segment
-// rays.  st.stop: samples marched per ray; *kept: their sum.  bits / G (tp_eval_accelerated below; NULL here): the emit step keeps
-// only the samples that the grid keeps, and *kept counts those.
-int tp_eval_terminating(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* fg_t, const float* far, int N,
-                        float* fg_out, float eps, int segment, const TpTermState& st, int win, long long* kept,
-                        const uint32_t* bits = nullptr, int G = 0) {
+// One region's evaluation of one level of a marching frame (include/neo360_hip.h: STOP RULE, OUTSIDE STOP RULE) into zero-filled
+// rows `out`.  Per window of rows and per segment: compact the alive rows (launch_cull_compact on the running value: !(alive < eps),
+// ascending order, the count on the device), emit their point rows of the segment, ONE compact launch of the level's evaluator on
+// single points (as tp_eval_skipping), scatter, advance.  A point list has at most skip_window x N rows - the bound, the buffer
+// (W[12]) and the knob of the skipping frame - so a window holds skip_window N / segment rows.  st.stop: samples marched per row;
+// *kept: their sum.
+//   inside  (map, count, lam NULL): rows are the frame's rays, pos = the level's dense fg_t.  bits / G (neo_tp_render_accelerated with
+//           a grid; NULL otherwise): the emit step is the fused classify + compact of accelerate.hip over the segment's candidates, so
+//           only the samples that the grid keeps are evaluated and counted.  A skipped sample stays a zero row, which is what the
+//           advance and the composite read: the stops are the STOP RULE on the masked rows.
+//   outside (map / count: the frame's survivors; lam: the level's dense lambdas): rows are the compact background rows of the culled
+//           frame, pos row k at pos + k N (level 0: R equal rows).  The survivor count lives on the device, so the windows cover all R
+//           rows and every launch behind the count finds no alive row.
+int tp_eval_march(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, bool outside, int level, const float* pos, const float* far,
+                  int N, float* out, const float* lam, const int* map, const int* count, float eps, int segment, const TpMarchState& st,
+                  int win, long long* kept, bool dens, const uint32_t* bits, int G) {
     hipStream_t s = f.s;
     const int seg = std::min(segment, N);
     const size_t cap = static_cast<size_t>(win) * seg;
     if (ctx->ws[12].reserve(neo::occ_rows_bytes(cap))) return NEO_ERR_NOMEM;
     neo::OccRows w;
     w.carve(ctx->ws[12].p, cap);
-    HIP_TRY(hipMemsetAsync(fg_out, 0, static_cast<size_t>(a.R) * N * 16, s));
-    neo::launch_term_init(st.trans, st.stop, a.R, 0, kept, 0, s);
-    neo::launch_occ_iota(w.iota, static_cast<int>(cap), s);
-    for (int r0 = 0; r0 < a.R; r0 += win) {
-        const int rays = std::min(win, a.R - r0);
-        for (int b0 = 0; b0 < N; b0 += segment) {
-            const int len = std::min(segment, N - b0);
-            const int P = rays * len;
-            neo::launch_cull_compact(st.trans + r0, st.trans + r0, rays, eps, st.cws, nullptr, s);
-            const int* map_w = neo::cull_map_of(st.cws, rays);      // the workspace's layout follows the window's ray count
-            const int* count_w = neo::cull_count_of(st.cws, rays);
-            if (bits)
-                neo::launch_acc_compact(a.rays_o, a.rays_d, a.viewdirs, fg_t, map_w, count_w, r0, rays, a.R, N, b0, len, a.chunk, bits, G,
-                                        st.keep, w, kept, s);
-            else
-                neo::launch_term_emit(a.rays_o, a.rays_d, a.viewdirs, fg_t, map_w, count_w, r0, rays, a.R, N, b0, len, a.chunk, w, kept, s);
-            if (int rc = tp_launch(ctx, ctx->tp[level], f.sc, f.views, w.o, w.d, w.v, w.t, nullptr, P, 1, a.chunk, w.out, s, w.iota, w.count))
-                return rc;
-            neo::launch_term_scatter(w, P, fg_out, s);
-            neo::launch_term_advance(fg_out, fg_t, a.rays_d, far, N, b0, b0 + len, segment, eps, map_w, count_w, rays, r0, st.carry,
-                                     st.trans, st.stop, s);
-        }
-    }
-    return NEO_OK;
-}
-
-// tp_eval_terminating on the samples that the grid `bits` keeps (neo_tp_render_accelerated; include/neo360_hip.h: ACCELERATED FRAME):
-// the window and segment loop above - ONE loop, not a copy - whose emit step is the fused classify + compact of accelerate.hip over
-// the segment's candidates.  A skipped sample stays a zero row of the zero-filled dense rows, which is what k_term_advance and the
-// composite read: the stops are the STOP RULE on the masked rows.  The workgroup-total prefix of the compaction is linear in the
-// workgroups of ONE segment launch, at most skip_window x N / 1024 of them - the bound of tp_eval_skipping's windows.  bits == NULL
-// (no grid): the terminating path itself, launch for launch.  *kept: the evaluated samples.
-int tp_eval_accelerated(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* fg_t, const float* far, int N,
-                        float* fg_out, float eps, int segment, const TpTermState& st, int win, const uint32_t* bits, int G,
-                        long long* kept) {
-    return tp_eval_terminating(ctx, f, a, level, fg_t, far, N, fg_out, eps, segment, st, win, kept, bits, G);
-}
-
-// Per-row state of an outside-sphere march in W[13], by COMPACT background row (it follows the inside marches of both levels, whose
-// TpTermState is dead by then): [carry fp64 R | lam_c fp32 R | alive fp32 R | value fp32 R | stop int R | the alive compaction of one
-// window].  alive is what the compaction reads: 1 in front of segment 0, then the running value; -1 behind the survivor count.
-struct TpOutState {
-    double* carry;
-    float *lam_c, *alive, *value;
-    int *stop, *cws;
-    static size_t bytes(size_t r, int win) { return r * 24 + neo::cull_ws_ints(win) * sizeof(int); }
-    void carve(void* base, size_t r) {
-        carry = static_cast<double*>(base);
-        lam_c = reinterpret_cast<float*>(carry + r);
-        alive = lam_c + r;
-        value = alive + r;
-        stop = reinterpret_cast<int*>(value + r);
-        cws = stop + r;
-    }
-};
-
-// The outside-sphere evaluation of one level of a marching frame (neo_tp_render_marching with `outside`; include/neo360_hip.h:
-// OUTSIDE STOP RULE) into zero-filled COMPACT rows bg_out: tp_eval_terminating's window and segment loop on the compact background
-// rows of the culled frame.  map / count: the frame's survivors; lam: the level's dense lambdas; bg_s: the level's positions, row k
-// at bg_s + k N (level 0: R equal rows).  The survivor count lives on the device, so the windows cover all R rows and every launch
-// behind the count finds no alive row.  ot.stop: samples marched per compact row; *kept: their sum.
-int tp_eval_outside(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* bg_s, const float* far, int N,
-                    float* bg_out, const float* lam, const int* map, const int* count, float eps, int segment, const TpOutState& ot,
-                    int win, long long* kept, bool dens) {
-    hipStream_t s = f.s;
-    const int seg = std::min(segment, N);
-    const size_t cap = static_cast<size_t>(win) * seg;
-    if (ctx->ws[12].reserve(neo::occ_rows_bytes(cap))) return NEO_ERR_NOMEM;
-    neo::OccRows w;
-    w.carve(ctx->ws[12].p, cap);
-    HIP_TRY(hipMemsetAsync(bg_out, 0, static_cast<size_t>(a.R) * N * 16, s));
-    neo::launch_tout_init(lam, map, count, a.R, ot.lam_c, ot.alive, ot.value, ot.stop, 0, kept, 0, s);
+    HIP_TRY(hipMemsetAsync(out, 0, static_cast<size_t>(a.R) * N * 16, s));
+    neo::launch_march_init(lam, map, count, a.R, st.lam_c, st.alive, st.value, st.stop, 0, kept, 0, s);
     neo::launch_occ_iota(w.iota, static_cast<int>(cap), s);
     for (int k0 = 0; k0 < a.R; k0 += win) {
         const int rows = std::min(win, a.R - k0);
         for (int b0 = 0; b0 < N; b0 += segment) {
             const int len = std::min(segment, N - b0);
             const int P = rows * len;
-            neo::launch_cull_compact(ot.alive + k0, ot.alive + k0, rows, eps, ot.cws, nullptr, s);
-            const int* map_w = neo::cull_map_of(ot.cws, rows);
-            const int* count_w = neo::cull_count_of(ot.cws, rows);
-            neo::launch_tout_emit(a.rays_o, a.rays_d, a.viewdirs, far, bg_s, N, map, map_w, count_w, k0, rows, a.R, N, b0, len, a.chunk, w,
-                                  kept, s);
-            if (int rc = tp_launch(ctx, ctx->tp[2 + level], f.sc, f.views, w.o, w.d, w.v, w.t, w.far, P, 1, a.chunk, w.out, s, w.iota,
-                                   w.count, dens))
+            neo::launch_cull_compact(st.alive + k0, st.alive + k0, rows, eps, st.cws, nullptr, s);
+            const int* map_w = neo::cull_map_of(st.cws, rows);      // the workspace's layout follows the window's row count
+            const int* count_w = neo::cull_count_of(st.cws, rows);
+            if (bits)
+                neo::launch_acc_compact(a.rays_o, a.rays_d, a.viewdirs, pos, map_w, count_w, k0, rows, a.R, N, b0, len, a.chunk, bits, G,
+                                        st.keep, w, kept, s);
+            else
+                neo::launch_march_emit(a.rays_o, a.rays_d, a.viewdirs, outside ? far : nullptr, pos, N, map, map_w, count_w, k0, rows, a.R,
+                                       N, b0, len, a.chunk, w, kept, s);
+            if (int rc = tp_launch(ctx, ctx->tp[(outside ? 2 : 0) + level], f.sc, f.views, w.o, w.d, w.v, w.t, outside ? w.far : nullptr, P,
+                                   1, a.chunk, w.out, s, w.iota, w.count, dens))
                 return rc;
-            neo::launch_term_scatter(w, P, bg_out, s);
-            neo::launch_tout_advance(bg_out, bg_s, N, N, b0, b0 + len, segment, eps, map_w, count_w, rows, k0, ot.lam_c, ot.carry, ot.value,
-                                     ot.alive, ot.stop, s);
+            neo::launch_march_scatter(w, P, out, s);
+            neo::launch_march_advance(outside, out, pos, N, a.rays_d, far, st.lam_c, N, b0, b0 + len, segment, eps, map_w, count_w, rows, k0,
+                                      st.carry, st.value, st.alive, st.stop, s);
         }
     }
     return NEO_OK;
@@ -716,99 +665,43 @@ int neo_tp_extras(neo_ctx* ctx, const float* fg_t, const float* fg_w, const floa
     return check_launch();
 }
 
-int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
-                         const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
-                         int white_bkgd, const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps,
-                         int* survivors_out, void* stream) {
-    ENTER(ctx);
-    (void)white_bkgd;  // as neo_tp_render
-    const TpFrameArgs a{rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream};
-    TpFrame::Own own;
-    if (!(eps > 0.0f && eps < 1.0f)) own.after_counts = "eps must lie in (0, 1)";
-    TpFrame f;      // the foreground launches keep the ray-patch order; compact launches drop it (tp_launch)
-    if (int rc = f.begin(ctx, a, true, true, own)) return rc;
-    hipStream_t s = f.s;
-    if (f.empty) {
-        if (survivors_out) HIP_TRY(hipMemsetAsync(survivors_out, 0, sizeof(int), s));
-        return NEO_OK;
-    }
-    const int N0 = f.N0, N1 = f.N1;
-    const neo::TpScene& sc = f.sc;
-    const neo::TpViews& views = f.views;
+// What an entry point asks of tp_render_marching beyond the frame's arguments.
+struct TpMarchOptions {
+    const char* after_counts;      // the entry point's own eps / segment check (TpFrame::Own), or NULL
+    bool stop_inside;              // false (neo_tp_render_culled): no level follows the STOP RULE inside the sphere
+    bool use_occ;                  // an installed occupancy grid is read (the KEEP RULE)
+    bool outside;                  // the outside-sphere march follows the OUTSIDE STOP RULE
+};
 
-    // workspaces: the dense layout (W[0..8]); W[9] holds the per-ray foreground results of BOTH levels (they are merged only after
-    // the background has run) and the compact background results, W[10] the compaction's map / slot / count
-    auto* W = ctx->ws;
-    const size_t r = static_cast<size_t>(R);
-    TpDenseRows rows;
-    if (rows.reserve(W, r, N0, N1) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)))
-        return NEO_ERR_NOMEM;
-    // bg_s0 is the same row for every ray (k_tp_level0): its first `count` rows ARE the compact level-0 rows; bg_out, bg_w0 and
-    // bg_s1 are compact: row k belongs to ray map[k]
-    auto [far, fg_t0, bg_s0, fg_out, bg_out, fg_w0, bg_w0, fg_t1, bg_s1] = rows;
-    float* scratch = W[9].as<float>();    // per level: fg_rgb(3) fg_depth fg_acc lambda bg_rgb(3) = 9 floats a ray; then compact bg_rgb(3) bg_depth, reused
-    float* c_bg_rgb = scratch + r * 18;
-    float* c_bg_depth = scratch + r * 21;
-    int* cws = W[10].as<int>();
-    const int* map = neo::cull_map_of(cws, R);
-    const int* slot = neo::cull_slot_of(cws, R);
-    const int* count = neo::cull_count_of(cws, R);
-
-    neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);       // sphere-miss assertions: every ray, culled or not
-    neo::launch_tp_level0(far, f.edges, R, N0, f.near, fg_t0, bg_s0, s);
-    const bool sigma0 = level0_sigma_only(level0);     // as neo_tp_render: density-only level-0 launches, no level-0 colour / depth
-    struct LevelFg { float* fg_rgb; float* fg_depth; float* fg_acc; float* lam; float* bg_rgb; } L[2];
-    for (int level = 0; level < 2; ++level) {
-        const neo_tp_level_out* lo = level == 0 ? level0 : level1;
-        float* b = scratch + r * 9 * level;
-        L[level] = {(lo && lo->fg_rgb) ? lo->fg_rgb : b, b + r * 3, (lo && lo->fg_acc) ? lo->fg_acc : b + r * 4,
-                    (lo && lo->bg_lambda) ? lo->bg_lambda : b + r * 5, lo ? lo->bg_rgb : nullptr};
-    }
-    // foreground of both levels first: nothing in a ray's background half feeds its foreground half
-    if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, fg_t0, nullptr, R, N0, chunk, fg_out, s, nullptr, nullptr, sigma0)) return rc;
-    neo::launch_composite(1, fg_out, fg_t0, N0, rays_d, far, R, N0, 0, sigma0 ? nullptr : L[0].fg_rgb, L[0].fg_acc,
-                          sigma0 ? nullptr : L[0].fg_depth, fg_w0, L[0].lam, s);
-    if (neo::launch_resample(fg_t0, N0, fg_w0, f.u, 0, R, N0, n_fine, 0, fg_t1, s)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
-    if (int rc = tp_launch(ctx, ctx->tp[1], sc, views, rays_o, rays_d, viewdirs, fg_t1, nullptr, R, N1, chunk, fg_out, s)) return rc;
-    neo::launch_composite(1, fg_out, fg_t1, N1, rays_d, far, R, N1, 0, L[1].fg_rgb, L[1].fg_acc, L[1].fg_depth, nullptr, L[1].lam, s);
-
-    neo::launch_cull_compact(L[0].lam, L[1].lam, R, eps, cws, survivors_out, s);
-
-    // background on the survivors: grids sized for R, every kernel takes its row count from the device word
-    if (int rc = tp_launch(ctx, ctx->tp[2], sc, views, rays_o, rays_d, viewdirs, bg_s0, far, R, N0, chunk, bg_out, s, map, count, sigma0)) return rc;
-    neo::launch_composite(2, bg_out, bg_s0, N0, nullptr, nullptr, R, N0, 0, sigma0 ? nullptr : c_bg_rgb, nullptr,
-                          sigma0 ? nullptr : c_bg_depth, bg_w0, nullptr, s, count);
-    if (neo::launch_resample(bg_s0, N0, bg_w0, f.u, 0, R, N0, n_fine, 1, bg_s1, s, count)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
-    if (level0 && (level0->rgb || level0->depth || level0->bg_rgb))
-        neo::launch_tp_merge_culled(L[0].fg_rgb, L[0].fg_depth, L[0].lam, c_bg_rgb, c_bg_depth, slot, R, level0->rgb, level0->depth,
-                                    L[0].bg_rgb, s);
-    if (int rc = tp_launch(ctx, ctx->tp[3], sc, views, rays_o, rays_d, viewdirs, bg_s1, far, R, N1, chunk, bg_out, s, map, count)) return rc;
-    neo::launch_composite(2, bg_out, bg_s1, N1, nullptr, nullptr, R, N1, 0, c_bg_rgb, nullptr, c_bg_depth, nullptr, nullptr, s, count);
-    if (level1 && (level1->rgb || level1->depth || level1->bg_rgb))
-        neo::launch_tp_merge_culled(L[1].fg_rgb, L[1].fg_depth, L[1].lam, c_bg_rgb, c_bg_depth, slot, R, level1->rgb, level1->depth,
-                                    L[1].bg_rgb, s);
-    return check_launch();
+// the eps / segment check of the three marching entry points
+static const char* march_arg_check(float eps, int segment) {
+    if (!(eps >= 0.0f && eps < 1.0f)) return "eps must lie in [0, 1)";
+    if (!(segment >= 64 && segment % 64 == 0)) return "segment must be a positive multiple of 64";
+    return nullptr;
 }
 
-// Early ray termination: neo_tp_render_culled's launch order (the foreground of both levels first, the background on the rays that
-// still let light through) in which the inside-sphere march of level 1 - with `coarse` also of level 0 - stops by the STOP RULE.
-// The one driver of neo_tp_render_terminating (use_occ = false: an installed grid is not read, bits stays NULL and every launch below
-// is that call's own) and of neo_tp_render_accelerated (use_occ = true: with a grid installed the marches also obey the KEEP RULE -
-// tp_eval_accelerated - and a level 0 without `coarse` is tp_eval_skipping).  `outside` (neo_tp_render_marching only): the
-// outside-sphere march of level 1 - with `coarse` also of level 0 - obeys the OUTSIDE STOP RULE (tp_eval_outside) instead of the
-// culled frame's compact launch.  kept: int64[2], the inside counters; kept_out (may be NULL): int64[2], the outside ones.  With
-// outside == false, kept_out == NULL and no bg_stop / bg_value / bg_rows asked for, every launch below is the parent's.  The caller
-// has entered the context.
+// The one driver of the culled and the marching frames: the foreground of both levels first (nothing in a ray's background half
+// feeds its foreground half), then the background on the rays that still let light through (launch_cull_compact on the two
+// bg_lambda; grids sized for R, every kernel takes its row count from the device word).
+//   stop_inside = false   neo_tp_render_culled: both foreground levels are dense launches with the ray-patch order, the background
+//                         is the compact launch; no march state, no point rows (W[12] / W[13] are not touched), no sample copies;
+//   stop_inside = true    the inside-sphere march of level 1 - with `coarse` also of level 0 - stops by the STOP RULE (tp_eval_march).
+//                         use_occ = false (neo_tp_render_terminating): an installed grid is not read, bits stays NULL.  use_occ =
+//                         true (neo_tp_render_accelerated): with a grid installed the marches also obey the KEEP RULE, and a level 0
+//                         without `coarse` is tp_eval_skipping.  `outside` (neo_tp_render_marching only): the outside-sphere march of
+//                         level 1 - with `coarse` also of level 0 - obeys the OUTSIDE STOP RULE instead of the compact launch.
+// kept: int64[2], the inside counters; kept_out (may be NULL): int64[2], the outside ones.  A level that does not march costs only
+// what its caller asks for.  The caller has entered the context.
 static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_level_out* level0, const neo_tp_level_out* level1,
                               float eps, int segment, int coarse, const neo_tp_march_samples* samples0,
                               const neo_tp_march_samples* samples1, long long* kept, long long* kept_out, int* survivors_out,
-                              bool use_occ, bool outside) {
+                              const TpMarchOptions& o) {
     const float *rays_o = a.rays_o, *rays_d = a.rays_d, *viewdirs = a.viewdirs;
     const int R = a.R, chunk = a.chunk, n_fine = a.n_fine;
+    const bool use_occ = o.use_occ, outside = o.outside;
     TpFrame::Own own;
-    if (!(eps >= 0.0f && eps < 1.0f)) own.after_counts = "eps must lie in [0, 1)";
-    else if (!(segment >= 64 && segment % 64 == 0)) own.after_counts = "segment must be a positive multiple of 64";
-    TpFrame f;      // a dense level-0 launch keeps the ray-patch order; compact launches drop it (tp_launch)
+    own.after_counts = o.after_counts;
+    TpFrame f;      // a dense launch keeps the ray-patch order; compact launches drop it (tp_launch)
     if (int rc = f.begin(ctx, a, true, true, own)) return rc;
     hipStream_t s = f.s;
     if (f.empty) {
@@ -821,35 +714,44 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
     const neo::TpScene& sc = f.sc;
     const neo::TpViews& views = f.views;
     const size_t r = static_cast<size_t>(R);
-    REQUIRE(r * N1 <= 2147483647UL, "too many points for 32-bit indices");
 
-    // workspaces: neo_tp_render_culled's (W[0..10]), the point rows of one segment launch in W[12], the per-ray march state in W[13]
+    // workspaces: the dense layout (W[0..8]); W[9] holds the per-ray foreground results of BOTH levels (they are merged only after
+    // the background has run) and the compact background results, W[10] the compaction's map / slot / count; a march adds the
+    // point rows of one segment launch in W[12] and the per-row march state in W[13]
     auto* W = ctx->ws;
-    const int skip_window = ctx->skip_window > 0 ? ctx->skip_window : SKIP_WINDOW_DEFAULT;
-    const int win_of[2] = {static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N0 / segment))),
-                           static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N1 / segment)))};
-    REQUIRE(static_cast<size_t>(std::max(win_of[0], win_of[1])) * std::min(segment, N1) * 3 <= 2147483647UL,
-            "skip window too large for 32-bit indices");
-    // with a grid: one keep byte per candidate of a segment launch behind the march state, and room for the keep window that a
-    // level 0 without `coarse` (tp_eval_skipping) puts at the front of W[13] before the state is initialised - reserved here, so that
-    // nothing re-allocates under the state
-    const uint32_t* bits = use_occ && ctx->occ_G ? ctx->occ_bits.as<uint32_t>() : nullptr;
-    const int G = bits ? ctx->occ_G : 0;
-    const int win_max = std::max(win_of[0], win_of[1]);
-    const size_t candidates = bits ? static_cast<size_t>(win_max) * std::min(segment, N1) : 0;
-    const size_t skip_keep = bits && !coarse ? static_cast<size_t>(std::min(skip_window, R)) * N0 : 0;
-    if (bits || (use_occ && ((samples0 && samples0->fg_keep) || (samples1 && samples1->fg_keep))))
-        REQUIRE(r * N1 <= 2147483647UL - 1024, "too many points for 32-bit indices");
+    int win_of[2] = {0, 0};
+    const uint32_t* bits = nullptr;
+    int G = 0;
+    TpMarchState st{}, ot{};      // inside by ray; outside by compact row: the same bytes, read only after the inside marches are done
+    if (o.stop_inside) {
+        REQUIRE(r * N1 <= 2147483647UL, "too many points for 32-bit indices");
+        const int skip_window = ctx->skip_window > 0 ? ctx->skip_window : SKIP_WINDOW_DEFAULT;
+        win_of[0] = static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N0 / segment)));
+        win_of[1] = static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N1 / segment)));
+        const int win_max = std::max(win_of[0], win_of[1]);
+        REQUIRE(static_cast<size_t>(win_max) * std::min(segment, N1) * 3 <= 2147483647UL, "skip window too large for 32-bit indices");
+        // with a grid: one keep byte per candidate of a segment launch behind the march state, and room for the keep window that a
+        // level 0 without `coarse` (tp_eval_skipping) puts at the front of W[13] before the state is initialised - reserved here, so
+        // that nothing re-allocates under the state
+        if (use_occ && ctx->occ_G) {
+            bits = ctx->occ_bits.as<uint32_t>();
+            G = ctx->occ_G;
+        }
+        const size_t candidates = bits ? static_cast<size_t>(win_max) * std::min(segment, N1) : 0;
+        const size_t skip_keep = bits && !coarse ? static_cast<size_t>(std::min(skip_window, R)) * N0 : 0;
+        if (bits || (use_occ && ((samples0 && samples0->fg_keep) || (samples1 && samples1->fg_keep))))
+            REQUIRE(r * N1 <= 2147483647UL - 1024, "too many points for 32-bit indices");
+        if (W[13].reserve(std::max({TpMarchState::bytes(false, r, win_max, candidates), skip_keep, TpMarchState::bytes(true, r, win_max)})))
+            return NEO_ERR_NOMEM;
+        st.carve(W[13].p, false, r, win_max);
+        ot.carve(W[13].p, true, r, win_max);
+    }
     TpDenseRows rows;
-    if (rows.reserve(W, r, N0, N1) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int)) ||
-        W[13].reserve(std::max({TpTermState::bytes(r, win_max, candidates), skip_keep, TpOutState::bytes(r, win_max)})))
-        return NEO_ERR_NOMEM;
+    if (rows.reserve(W, r, N0, N1) || W[9].reserve(r * 24 * 4) || W[10].reserve(neo::cull_ws_ints(R) * sizeof(int))) return NEO_ERR_NOMEM;
+    // bg_s0 is the same row for every ray (k_tp_level0): its first `count` rows ARE the compact level-0 rows; bg_out, bg_w0 and
+    // bg_s1 are compact: row k belongs to ray map[k]
     auto [far, fg_t0, bg_s0, fg_out, bg_out, fg_w0, bg_w0, fg_t1, bg_s1] = rows;
-    TpTermState st;
-    st.carve(W[13].p, r, win_max);
-    TpOutState ot;      // the same bytes, read only after the inside marches of both levels are done
-    ot.carve(W[13].p, r);
-    float* scratch = W[9].as<float>();    // as neo_tp_render_culled
+    float* scratch = W[9].as<float>();    // per level: fg_rgb(3) fg_depth fg_acc lambda bg_rgb(3) = 9 floats a ray; then compact bg_rgb(3) bg_depth, reused
     float* c_bg_rgb = scratch + r * 18;
     float* c_bg_depth = scratch + r * 21;
     int* cws = W[10].as<int>();
@@ -859,7 +761,7 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
 
     neo::launch_sphere(rays_o, rays_d, R, far, nullptr, ctx->flags, s);       // sphere-miss assertions: every ray, stopped, culled or not
     neo::launch_tp_level0(far, f.edges, R, N0, f.near, fg_t0, bg_s0, s);
-    const bool sigma0 = level0_sigma_only(level0);
+    const bool sigma0 = level0_sigma_only(level0);     // as neo_tp_render: density-only level-0 launches, no level-0 colour / depth
     const neo_tp_level_out* los[2] = {level0, level1};
     const neo_tp_march_samples* sos[2] = {samples0, samples1};
     struct LevelFg { float* fg_rgb; float* fg_depth; float* fg_acc; float* lam; float* bg_rgb; } L[2];
@@ -876,17 +778,17 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
         const neo_tp_march_samples* so = sos[level];
         const bool dens = level == 0 && sigma0;
         uint8_t* fg_keep = use_occ && so ? so->fg_keep : nullptr;       // the KEEP RULE on the whole row, behind the stops as well
-        if (level == 1 || coarse) {
-            if (int rc = tp_eval_accelerated(ctx, f, a, level, fg_t, far, N, fg_out, eps, segment, st, win_of[level], bits, G,
-                                             kept ? kept + level : nullptr))
+        if (o.stop_inside && (level == 1 || coarse)) {
+            if (int rc = tp_eval_march(ctx, f, a, false, level, fg_t, far, N, fg_out, nullptr, nullptr, nullptr, eps, segment, st,
+                                       win_of[level], kept ? kept + level : nullptr, false, bits, G))
                 return rc;
         } else if (bits) {      // the grid alone: neo_tp_render_skipping's level 0 (it may use the front of W[13]: before the init)
             if (int rc = tp_eval_skipping(ctx, f, a, 0, fg_t, N, fg_out, fg_keep, kept)) return rc;
-            neo::launch_term_init(nullptr, st.stop, R, N, nullptr, 0, s);
+            neo::launch_march_init(nullptr, nullptr, nullptr, R, nullptr, nullptr, nullptr, st.stop, N, nullptr, 0, s);
             fg_keep = nullptr;
         } else {
-            if (int rc = tp_launch(ctx, ctx->tp[0], sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
-            neo::launch_term_init(nullptr, st.stop, R, N, kept, static_cast<long long>(r) * N, s);
+            if (int rc = tp_launch(ctx, ctx->tp[level], sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
+            if (o.stop_inside) neo::launch_march_init(nullptr, nullptr, nullptr, R, nullptr, nullptr, nullptr, st.stop, N, kept, N, s);
         }
         float* fg_w = level == 0 ? fg_w0 : (so ? so->fg_w : nullptr);
         neo::launch_composite(1, fg_out, fg_t, N, rays_d, far, R, N, 0, dens ? nullptr : L[level].fg_rgb, L[level].fg_acc,
@@ -905,15 +807,15 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
 
     neo::launch_cull_compact(L[0].lam, L[1].lam, R, eps, cws, survivors_out, s);
 
-    // One level's outside-sphere rows into the compact bg_out.  A level that follows the OUTSIDE STOP RULE marches (tp_eval_outside);
-    // any other is neo_tp_render_culled's compact launch, and only a caller of the outside outputs pays for more: the counter, and
+    // One level's outside-sphere rows into the compact bg_out.  A level that follows the OUTSIDE STOP RULE marches (tp_eval_march);
+    // any other is the culled frame's compact launch, and only a caller of the outside outputs pays for more: the counter, and
     // the rule's own kernel run to the end of the row (eps = 0 stops nothing) for stop = N and the running value there.
     auto background = [&](int level, const float* bg_s, int N, bool dens) -> int {
         const neo_tp_march_samples* so = sos[level];
         long long* kept_l = kept_out ? kept_out + level : nullptr;
         if (outside && (level == 1 || coarse)) {
-            if (int rc = tp_eval_outside(ctx, f, a, level, bg_s, rows.far, N, rows.bg_out, L[level].lam, map, count, eps, segment, ot,
-                                         win_of[level], kept_l, dens))
+            if (int rc = tp_eval_march(ctx, f, a, true, level, bg_s, rows.far, N, rows.bg_out, L[level].lam, map, count, eps, segment, ot,
+                                       win_of[level], kept_l, dens, nullptr, 0))
                 return rc;
         } else {
             if (int rc = tp_launch(ctx, ctx->tp[2 + level], sc, views, rays_o, rays_d, viewdirs, bg_s, rows.far, R, N, chunk, rows.bg_out, s, map,
@@ -921,20 +823,20 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
                 return rc;
             const bool value = so && so->bg_value;
             if (kept_l || value || (so && so->bg_stop))
-                neo::launch_tout_init(L[level].lam, map, count, R, value ? ot.lam_c : nullptr, nullptr, value ? ot.value : nullptr, ot.stop,
-                                      N, kept_l, N, s);
+                neo::launch_march_init(L[level].lam, map, count, R, value ? ot.lam_c : nullptr, nullptr, value ? ot.value : nullptr, ot.stop,
+                                       N, kept_l, N, s);
             if (value)
-                neo::launch_tout_advance(rows.bg_out, bg_s, N, N, 0, N, segment, 0.0f, nullptr, count, R, 0, ot.lam_c, nullptr, ot.value, nullptr,
-                                         ot.stop, s);
+                neo::launch_march_advance(true, rows.bg_out, bg_s, N, nullptr, nullptr, ot.lam_c, N, 0, N, segment, 0.0f, nullptr, count, R, 0,
+                                          nullptr, ot.value, nullptr, ot.stop, s);
         }
         if (so) {
-            neo::launch_tout_by_slot(ot.stop, ot.value, slot, R, so->bg_stop, so->bg_value, s);
-            if (so->bg_rows) neo::launch_term_rows_by_slot(rows.bg_out, slot, R, N * 4, so->bg_rows, s);
+            neo::launch_march_by_slot(ot.stop, ot.value, slot, R, so->bg_stop, so->bg_value, s);
+            if (so->bg_rows) neo::launch_march_rows_by_slot(rows.bg_out, slot, R, N * 4, so->bg_rows, s);
         }
         return NEO_OK;
     };
 
-    // background on the survivors, in neo_tp_render_culled's order
+    // background on the survivors
     if (int rc = background(0, bg_s0, N0, sigma0)) return rc;
     neo::launch_composite(2, bg_out, bg_s0, N0, nullptr, nullptr, R, N0, 0, sigma0 ? nullptr : c_bg_rgb, nullptr,
                           sigma0 ? nullptr : c_bg_depth, bg_w0, nullptr, s, count);
@@ -949,8 +851,21 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
                                     L[1].bg_rgb, s);
     // bg_s: level 0 is one row for every ray (k_tp_level0); level 1 exists for the survivors only: a culled ray's row is zero
     if (samples0 && samples0->bg_s) HIP_TRY(hipMemcpyAsync(samples0->bg_s, bg_s0, r * N0 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (samples1 && samples1->bg_s) neo::launch_term_rows_by_slot(bg_s1, slot, R, N1, samples1->bg_s, s);
+    if (samples1 && samples1->bg_s) neo::launch_march_rows_by_slot(bg_s1, slot, R, N1, samples1->bg_s, s);
     return check_launch();
+}
+
+// the dense foreground of both levels, the background on the rays whose bg_lambda is not below eps at both: the driver with nothing
+// stopped
+int neo_tp_render_culled(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                         const float* src_poses, int NV, float focal, float cx, float cy, int n_coarse, int n_fine,
+                         int white_bkgd, const neo_tp_level_out* level0, const neo_tp_level_out* level1, float eps,
+                         int* survivors_out, void* stream) {
+    ENTER(ctx);
+    (void)white_bkgd;  // as neo_tp_render
+    return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
+                              level1, eps, 0, 0, nullptr, nullptr, nullptr, nullptr, survivors_out,
+                              {eps > 0.0f && eps < 1.0f ? nullptr : "eps must lie in (0, 1)", false, false, false});
 }
 
 int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
@@ -966,7 +881,7 @@ int neo_tp_render_terminating(neo_ctx* ctx, const float* rays_o, const float* ra
             so[l] = {given[l]->fg_t, given[l]->fg_w, given[l]->bg_s, given[l]->stop, nullptr, given[l]->fg_rows, nullptr, nullptr, nullptr};
     return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
                               level1, eps, segment, coarse, samples0 ? &so[0] : nullptr, samples1 ? &so[1] : nullptr, kept, nullptr,
-                              survivors_out, false, false);
+                              survivors_out, {march_arg_check(eps, segment), true, false, false});
 }
 
 // Occupancy skipping and early termination together (include/neo360_hip.h: ACCELERATED FRAME): the driver above with the grid read.
@@ -984,7 +899,7 @@ int neo_tp_render_accelerated(neo_ctx* ctx, const float* rays_o, const float* ra
                      nullptr};
     return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
                               level1, eps, segment, coarse, samples0 ? &so[0] : nullptr, samples1 ? &so[1] : nullptr, kept, nullptr,
-                              survivors_out, true, false);
+                              survivors_out, {march_arg_check(eps, segment), true, true, false});
 }
 
 // The driver itself (include/neo360_hip.h: MARCHING FRAME): use_grid chooses between the two calls above, `outside` adds the OUTSIDE
@@ -997,7 +912,7 @@ int neo_tp_render_marching(neo_ctx* ctx, const float* rays_o, const float* rays_
     ENTER(ctx);
     return tp_render_marching(ctx, {rays_o, rays_d, viewdirs, R, chunk, src_poses, NV, focal, cx, cy, n_coarse, n_fine, stream}, level0,
                               level1, eps, segment, coarse, samples0, samples1, kept, kept ? kept + 2 : nullptr, survivors_out,
-                              use_grid != 0, outside != 0);
+                              {march_arg_check(eps, segment), true, use_grid != 0, outside != 0});
 }
 
 // Object-level render: the two inside-sphere MLPs between a caller-given per-ray interval, on the rays that have one.

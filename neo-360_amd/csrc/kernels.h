@@ -434,7 +434,7 @@ void launch_occ_keep(const float* rays_o, const float* rays_d, const float* t, i
 // One window's compact rows, `cap` of them, in one buffer of occ_rows_bytes(cap): row k is ONE kept point - the origin, direction and
 // t of its ray, the view direction of its quirk-Q1 ray, dst = its point index in the window - and out its (rgb, sigma) row; iota =
 // the identity map of the evaluator's compact launch; count the device word; totals the compaction's per-workgroup sums.  far: the
-// ray's sphere exit, which only the outside-sphere evaluators read (terminate_outside.hip fills it; the inside paths leave it alone).
+// ray's sphere exit, which only the outside-sphere evaluators read (march.hip fills it there; the inside paths leave it alone).
 struct OccRows {
     float *out, *o, *d, *v, *t, *far;
     int *dst, *iota, *count, *totals;
@@ -451,51 +451,5 @@ void launch_occ_compact(const float* rays_o, const float* rays_d, const float* v
 void launch_occ_scatter(const uint8_t* keep_win, int P, const OccRows& w, float* out_win, hipStream_t s);
 // sigma (G probes)^3 activated densities -> G^3 / 32 words: any probe > threshold, dilation, unit-sphere clip
 void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s);
-
-// terminate.hip - early ray termination of neo_tp_render_terminating (include/neo360_hip.h: STOP RULE)
-// trans (may be null) = 1, stop = stop_value for R rays; *kept (may be null) = kept_value
-void launch_term_init(float* trans, int* stop, int R, int stop_value, long long* kept, long long kept_value, hipStream_t s);
-// the point rows (OccRows, as launch_occ_compact leaves them; dst = the point's index in the level's dense (R,N) rows) of samples
-// b0 .. b0 + len - 1 of rays r0 + map[k], k < *count <= rays; *w.count = *count len, also added to *kept_sum when not null
-void launch_term_emit(const float* rays_o, const float* rays_d, const float* viewdirs, const float* t, const int* map, const int* count,
-                      int r0, int rays, int R, int N, int b0, int len, int chunk, const OccRows& w, long long* kept_sum, hipStream_t s);
-// out[w.dst[p]] = w.out[p] for p < *w.count; P: the host's bound of the row count
-void launch_term_scatter(const OccRows& w, long P, float* out, hipStream_t s);
-// the STOP RULE over samples b0 .. b_end - 1 (whole segments) of rays r0 + map[k], k < *count (map / count null: rays 0 .. n_rays - 1):
-// carry (fp64 per ray; may be null when b0 == 0 and nothing continues), trans = (float)carry at the stop, stop = samples marched
-void launch_term_advance(const float* rgbsigma, const float* t, const float* rays_d, const float* t_far, int N, int b0, int b_end,
-                         int segment, float eps, const int* map, const int* count, int n_rays, int r0, double* carry, float* trans,
-                         int* stop, hipStream_t s);
-// dst (R,N) = src_c row slot[ray], zeros where slot[ray] < 0
-void launch_term_rows_by_slot(const float* src_c, const int* slot, int R, int N, float* dst, hipStream_t s);
-
-// terminate_outside.hip - the outside-sphere march of neo_tp_render_marching (include/neo360_hip.h: OUTSIDE STOP RULE) on the COMPACT
-// background rows of the culled frame: row k belongs to ray map[k], k < *count.
-// per compact row k < R: lam_c = lam[map[k]], alive = 1 and stop = stop_value where k < *count; alive = -1 (dead at every eps >= 0),
-// stop = 0 and lam_c = 0 behind the count; value = 0; *kept (may be null) = kept_per_row x *count.  lam_c / alive / value may be null.
-void launch_tout_init(const float* lam, const int* map, const int* count, int R, float* lam_c, float* alive, float* value, int* stop,
-                      int stop_value, long long* kept, long long kept_per_row, hipStream_t s);
-// the point rows (OccRows with far) of samples b0 .. b0 + len - 1 of compact rows k0 + map_w[kk], kk < *count_w <= rows: origin,
-// direction and far of ray map[k], s = s_rows[k s_stride + j], the view direction of the quirk-Q1 ray of the dense launch of the
-// level's full N on the DENSE ray index, dst = k N + j; *w.count = *count_w len, also added to *kept_sum when not null
-void launch_tout_emit(const float* rays_o, const float* rays_d, const float* viewdirs, const float* far, const float* s_rows,
-                      long s_stride, const int* map, const int* map_w, const int* count_w, int k0, int rows, int R, int N, int b0, int len,
-                      int chunk, const OccRows& w, long long* kept_sum, hipStream_t s);
-// the OUTSIDE STOP RULE over samples b0 .. b_end - 1 (whole segments) of rows k0 + map_w[kk], kk < *count_w (map_w / count_w null:
-// rows 0 .. n_rows - 1): carry (fp64 per row; may be null when b0 == 0 and nothing continues), value = lam_c[k] (float)carry at the
-// stop, also written to alive when not null, stop = samples marched
-void launch_tout_advance(const float* rgbsigma, const float* s_rows, long s_stride, int N, int b0, int b_end, int segment, float eps,
-                         const int* map_w, const int* count_w, int n_rows, int k0, const float* lam_c, double* carry, float* value,
-                         float* alive, int* stop, hipStream_t s);
-// dense by ray through the slot table: stop (R) / value (R) = the compact entry at slot[ray], 0 where slot[ray] < 0; either may be null
-void launch_tout_by_slot(const int* stop_c, const float* value_c, const int* slot, int R, int* stop, float* value, hipStream_t s);
-
-// accelerate.hip - the segment launch of neo_tp_render_accelerated: launch_term_emit restricted to the samples that the KEEP RULE keeps
-// The candidates are launch_term_emit's rows (sample b0 + p % len of ray r0 + map[p / len], p < *alive len); keep (rays x len bytes)
-// receives their keep bytes, w.totals the per-workgroup sums, and the kept ones leave point rows as launch_term_emit's, in ascending
-// candidate order; *w.count = their number, also added to *kept_sum when not null.  Two launches, no atomics.
-void launch_acc_compact(const float* rays_o, const float* rays_d, const float* viewdirs, const float* t, const int* map, const int* alive,
-                        int r0, int rays, int R, int N, int b0, int len, int chunk, const uint32_t* bits, int G, uint8_t* keep,
-                        const OccRows& w, long long* kept_sum, hipStream_t s);
 
 }  // namespace neo

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "composite_round.h"
 #include "kernels.h"
 
 namespace neo {
@@ -85,30 +86,11 @@ __global__ __launch_bounds__(256) void k_composite(int mode, const float4* __res
         if (valid) {
             ti = tr[i];
             c = cs[i];
-            float delta;
-            if (i < N - 1) {
-                const float tn = tr[i + 1];
-                delta = mode == 2 ? ti - tn : tn - ti;
-            } else {
-                delta = mode == 1 ? far - ti : 1e10f;
-            }
-            if (mode != 2) delta = delta * dnorm;
-            alpha = alpha_of(c.w * delta);
+            alpha = composite_alpha(mode, tr, i, N, ti, c.w, far, dnorm);
         }
-        const float keep = valid ? (1.0f - alpha) + 1e-10f : 1.0f;
-        // inclusive product scan in fp64
-        double incl = (double)keep;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl = up * incl;
-        }
-        double excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.0;
         // per-element rounding to fp32 mirrors storing the fp32 cumprod tensor
-        const float trans = (float)(carry * excl);
+        const float trans = (float)transmittance_round(alpha, valid, lane, carry);
         const float w = alpha * trans;
-        carry = carry * __shfl(incl, 63, 64);
         if (valid) {
             if (w_out) w_out[(long)ray * N + i] = w;
             s_r += w * c.x; s_g += w * c.y; s_b += w * c.z;

@@ -7,8 +7,10 @@
 //   tp_march_compact    the two-level inside-sphere march on compact rows under a device count (neo_tp_render_objects, every
 //                       window of neo_tp_render_instances).
 //
-// neo_tp_render_culled and neo_tp_render_terminating / neo_tp_render_accelerated / neo_tp_render_marching (one driver, tp_render_marching in api_tp.hip) have
-// a launch order of their own - the foreground of both levels first - and take the preamble and the dense row layout only.
+// neo_tp_render_culled, neo_tp_render_terminating, neo_tp_render_accelerated and neo_tp_render_marching share one driver of their own,
+// tp_render_marching in api_tp.hip, with a launch order of its own - the foreground of both levels first, then the background on the
+// rays that still let light through; it takes the preamble and the dense row layout only.  Where a level marches, the driver calls
+// tp_eval_march (one window x segment loop for both regions; march.h has the region table).
 #pragma once
 #include "ctx.h"
 

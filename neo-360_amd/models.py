@@ -1128,42 +1128,70 @@ class NeRF_TP(_HipModule):
         `self.last_skip_kept` (int64[2], on the device) holds the kept samples per level; nothing is read back."""
         if self._occupancy is None:
             raise _lib.NeoError("no occupancy grid installed: call set_occupancy(...) or build_occupancy(...) first")
+        out, (self.last_skip_kept,) = self._render_march(
+            "neo_tp_render_skipping", rays, chunk, _lib.TpSkipSamples, ("fg_t", "fg_w", "bg_s", "fg_keep"), ("fg_rows",), (), 2,
+            survivors=False, check_grid="required", return_samples=return_samples)
+        return out
+
+    _MARCH_PER_RAY = dict(stop=torch.int32, bg_stop=torch.int32, bg_value=torch.float32)
+
+    def _render_march(self, entry, rays, chunk, struct_cls, names, rows_names, extra_args, n_kept, survivors=True, check_grid=False,
+                      keep_written=True, fine_only=False, return_samples=False):
+        """The marshalling behind `render_skipping`, `render_terminating`, `render_accelerated` and `render_marching`: one call of the
+        library's `entry` (ray and frame arguments, the two level structs, `extra_args`, the two `struct_cls` sample structs, the
+        counters, the stream).  names / rows_names: the sample rows of return_samples / return_samples="rows", in tuple order -
+        (B,) for a `_MARCH_PER_RAY` name, (B,N,4) for a rows name, bool for fg_keep (all ones unless keep_written), else (B,N).
+        check_grid: NeoError for a grid installed on another context - "required": also for none at all.  Returns the public
+        method's result and the device counters: int64[n_kept], and with `survivors` the int32 survivor count."""
         call = self._frame_call(rays, chunk, use_grid=True)
         B, dev = call.B, call.dev
         levels = []
-        kept = []
+        counts = []
+        if return_samples == "rows":
+            names = names + rows_names
+
+        def rows(k, n):
+            if k in self._MARCH_PER_RAY:
+                return torch.empty(B, dtype=self._MARCH_PER_RAY[k], device=dev)
+            if k == "fg_keep":      # a call that reads no grid skips nothing and the library writes no mask
+                return (torch.empty if keep_written else torch.ones)(B, n, dtype=torch.bool, device=dev)
+            return torch.empty((B, n, 4) if k in rows_names else (B, n), device=dev)
+
+        def byref(structs):
+            return (ctypes.byref(x) if x is not None else None for x in structs)
 
         def launch():
             ctx = call.ctx
-            if self._occupancy is None or self._occ_ctx is not ctx:
+            foreign = self._occupancy is not None and self._occ_ctx is not ctx
+            if check_grid and (foreign or (check_grid == "required" and self._occupancy is None)):
                 raise _lib.NeoError("the occupancy grid does not belong to this scene and device: install it again")
             self._set_mode(ctx, "_skip_window", "neo_tp_set_skip_window", int(self.skip_window or 0))
             structs, sample_structs = [], []
-            for n in call.n:
-                t, struct = self._level_out(B, dev)
+            for level, n in enumerate(call.n):
+                if level == 0 and fine_only:
+                    t, struct = {}, None
+                else:
+                    t, struct = self._level_out(B, dev)
                 structs.append(struct)
                 if return_samples:
-                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev),
-                             fg_keep=torch.empty(B, n, dtype=torch.bool, device=dev))
-                    if return_samples == "rows":
-                        t["fg_rows"] = torch.empty(B, n, 4, device=dev)
-                    sample_structs.append(_lib.TpSkipSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpSkipSamples._fields_)))
+                    t.update((k, rows(k, n)) for k in names)
+                    sample_structs.append(struct_cls(*(t[k].data_ptr() if k in t else None for k, _ in struct_cls._fields_)))
                 else:
                     sample_structs.append(None)
                 levels.append(t)
-            kept.append(torch.empty(2, dtype=torch.int64, device=dev))
-            _lib.check(ctx.lib.neo_tp_render_skipping(
-                *call.ray_args, *call.frame_args, ctypes.byref(structs[0]), ctypes.byref(structs[1]),
-                *(ctypes.byref(x) if x is not None else None for x in sample_structs), kept[0].data_ptr(), ctx.stream()))
+            counts.append(torch.empty(n_kept, dtype=torch.int64, device=dev))
+            if survivors:
+                counts.append(torch.empty((), dtype=torch.int32, device=dev))
+            _lib.check(getattr(ctx.lib, entry)(
+                *call.ray_args, *call.frame_args, *byref(structs), *extra_args, *byref(sample_structs),
+                *(c.data_ptr() for c in counts), ctx.stream()))
             self._after_call(ctx)
-            return [v for t in levels for v in t.values()] + kept
+            return [v for t in levels for v in t.values()] + counts
         call.run(launch)
-        self.last_skip_kept = kept[0]
-        out = [self._level_tuple(t) for t in levels]
+        out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
         if return_samples:
-            names = ("fg_t", "fg_w", "bg_s", "fg_keep") + (("fg_rows",) if return_samples == "rows" else ())
             out.append([tuple(t[k] for k in names) for t in levels])
-        return out
+        return out, counts
 
     # ---- early ray termination -----------------------------------------------------------------------------------------------
 
@@ -1192,44 +1220,9 @@ class NeRF_TP(_HipModule):
         `self.last_terminate_kept` (int64[2]: evaluated inside-sphere samples per level) and `self.last_terminate_survivors`
         (int32: rays whose background ran) stay on the device; nothing is read back."""
         eps, segment = ops._check_termination(eps, segment, "render_terminating")
-        call = self._frame_call(rays, chunk, use_grid=True)
-        B, dev = call.B, call.dev
-        levels = []
-        counts = []
-
-        def launch():
-            ctx = call.ctx
-            self._set_mode(ctx, "_skip_window", "neo_tp_set_skip_window", int(self.skip_window or 0))
-            structs, sample_structs = [], []
-            for level, n in enumerate(call.n):
-                if level == 0 and fine_only:
-                    t, struct = {}, None
-                else:
-                    t, struct = self._level_out(B, dev)
-                structs.append(struct)
-                if return_samples:
-                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev),
-                             stop=torch.empty(B, dtype=torch.int32, device=dev))
-                    if return_samples == "rows":
-                        t["fg_rows"] = torch.empty(B, n, 4, device=dev)
-                    sample_structs.append(_lib.TpTermSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpTermSamples._fields_)))
-                else:
-                    sample_structs.append(None)
-                levels.append(t)
-            counts.append(torch.empty(2, dtype=torch.int64, device=dev))
-            counts.append(torch.empty((), dtype=torch.int32, device=dev))
-            _lib.check(ctx.lib.neo_tp_render_terminating(
-                *call.ray_args, *call.frame_args, *(ctypes.byref(x) if x is not None else None for x in structs), eps, segment,
-                int(bool(coarse)), *(ctypes.byref(x) if x is not None else None for x in sample_structs), counts[0].data_ptr(),
-                counts[1].data_ptr(), ctx.stream()))
-            self._after_call(ctx)
-            return [v for t in levels for v in t.values()] + counts
-        call.run(launch)
-        self.last_terminate_kept, self.last_terminate_survivors = counts
-        out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
-        if return_samples:
-            names = ("fg_t", "fg_w", "bg_s", "stop") + (("fg_rows",) if return_samples == "rows" else ())
-            out.append([tuple(t[k] for k in names) for t in levels])
+        out, (self.last_terminate_kept, self.last_terminate_survivors) = self._render_march(
+            "neo_tp_render_terminating", rays, chunk, _lib.TpTermSamples, ("fg_t", "fg_w", "bg_s", "stop"), ("fg_rows",),
+            (eps, segment, int(bool(coarse))), 2, fine_only=fine_only, return_samples=return_samples)
         return out
 
     # ---- occupancy skipping and early termination together ---------------------------------------------------------------------
@@ -1256,46 +1249,9 @@ class NeRF_TP(_HipModule):
         behind them.  `self.last_accel_kept` (int64[2]: evaluated inside-sphere samples per level) and `self.last_accel_survivors`
         (int32: rays whose background ran) stay on the device; nothing is read back."""
         eps, segment = ops._check_termination(eps, segment, "render_accelerated")
-        call = self._frame_call(rays, chunk, use_grid=True)
-        B, dev = call.B, call.dev
-        levels = []
-        counts = []
-
-        def launch():
-            ctx = call.ctx
-            if self._occupancy is not None and self._occ_ctx is not ctx:
-                raise _lib.NeoError("the occupancy grid does not belong to this scene and device: install it again")
-            self._set_mode(ctx, "_skip_window", "neo_tp_set_skip_window", int(self.skip_window or 0))
-            structs, sample_structs = [], []
-            for level, n in enumerate(call.n):
-                if level == 0 and fine_only:
-                    t, struct = {}, None
-                else:
-                    t, struct = self._level_out(B, dev)
-                structs.append(struct)
-                if return_samples:
-                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev),
-                             stop=torch.empty(B, dtype=torch.int32, device=dev), fg_keep=torch.empty(B, n, dtype=torch.bool, device=dev))
-                    if return_samples == "rows":
-                        t["fg_rows"] = torch.empty(B, n, 4, device=dev)
-                    sample_structs.append(_lib.TpAccelSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpAccelSamples._fields_)))
-                else:
-                    sample_structs.append(None)
-                levels.append(t)
-            counts.append(torch.empty(2, dtype=torch.int64, device=dev))
-            counts.append(torch.empty((), dtype=torch.int32, device=dev))
-            _lib.check(ctx.lib.neo_tp_render_accelerated(
-                *call.ray_args, *call.frame_args, *(ctypes.byref(x) if x is not None else None for x in structs), eps, segment,
-                int(bool(coarse)), *(ctypes.byref(x) if x is not None else None for x in sample_structs), counts[0].data_ptr(),
-                counts[1].data_ptr(), ctx.stream()))
-            self._after_call(ctx)
-            return [v for t in levels for v in t.values()] + counts
-        call.run(launch)
-        self.last_accel_kept, self.last_accel_survivors = counts
-        out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
-        if return_samples:
-            names = ("fg_t", "fg_w", "bg_s", "stop", "fg_keep") + (("fg_rows",) if return_samples == "rows" else ())
-            out.append([tuple(t[k] for k in names) for t in levels])
+        out, (self.last_accel_kept, self.last_accel_survivors) = self._render_march(
+            "neo_tp_render_accelerated", rays, chunk, _lib.TpAccelSamples, ("fg_t", "fg_w", "bg_s", "stop", "fg_keep"), ("fg_rows",),
+            (eps, segment, int(bool(coarse))), 2, check_grid=True, fine_only=fine_only, return_samples=return_samples)
         return out
 
     # ---- early termination carried through the outside-sphere march ------------------------------------------------------------
@@ -1326,51 +1282,11 @@ class NeRF_TP(_HipModule):
         `self.last_march_kept` (int64[4]: evaluated samples inside the sphere per level, then outside the sphere per level) and
         `self.last_march_survivors` (int32: rays whose background ran) stay on the device; nothing is read back."""
         eps, segment = ops._check_termination(eps, segment, "render_marching")
-        call = self._frame_call(rays, chunk, use_grid=True)
-        B, dev = call.B, call.dev
-        levels = []
-        counts = []
-
-        def launch():
-            ctx = call.ctx
-            if grid and self._occupancy is not None and self._occ_ctx is not ctx:
-                raise _lib.NeoError("the occupancy grid does not belong to this scene and device: install it again")
-            self._set_mode(ctx, "_skip_window", "neo_tp_set_skip_window", int(self.skip_window or 0))
-            structs, sample_structs = [], []
-            for level, n in enumerate(call.n):
-                if level == 0 and fine_only:
-                    t, struct = {}, None
-                else:
-                    t, struct = self._level_out(B, dev)
-                structs.append(struct)
-                if return_samples:
-                    t.update(fg_t=torch.empty(B, n, device=dev), fg_w=torch.empty(B, n, device=dev), bg_s=torch.empty(B, n, device=dev),
-                             stop=torch.empty(B, dtype=torch.int32, device=dev),
-                             # grid=False: nothing is skipped and the library writes no mask
-                             fg_keep=(torch.empty if grid else torch.ones)(B, n, dtype=torch.bool, device=dev),
-                             bg_stop=torch.empty(B, dtype=torch.int32, device=dev), bg_value=torch.empty(B, device=dev))
-                    if return_samples == "rows":
-                        t["fg_rows"] = torch.empty(B, n, 4, device=dev)
-                        t["bg_rows"] = torch.empty(B, n, 4, device=dev)
-                    sample_structs.append(_lib.TpMarchSamples(*(t[k].data_ptr() if k in t else None for k, _ in _lib.TpMarchSamples._fields_)))
-                else:
-                    sample_structs.append(None)
-                levels.append(t)
-            counts.append(torch.empty(4, dtype=torch.int64, device=dev))
-            counts.append(torch.empty((), dtype=torch.int32, device=dev))
-            _lib.check(ctx.lib.neo_tp_render_marching(
-                *call.ray_args, *call.frame_args, *(ctypes.byref(x) if x is not None else None for x in structs), eps, segment,
-                int(bool(coarse)), int(bool(grid)), int(bool(outside)),
-                *(ctypes.byref(x) if x is not None else None for x in sample_structs), counts[0].data_ptr(), counts[1].data_ptr(),
-                ctx.stream()))
-            self._after_call(ctx)
-            return [v for t in levels for v in t.values()] + counts
-        call.run(launch)
-        self.last_march_kept, self.last_march_survivors = counts
-        out = [None if (level == 0 and fine_only) else self._level_tuple(t) for level, t in enumerate(levels)]
-        if return_samples:
-            names = ("fg_t", "fg_w", "bg_s", "stop", "fg_keep", "bg_stop", "bg_value") + (("fg_rows", "bg_rows") if return_samples == "rows" else ())
-            out.append([tuple(t[k] for k in names) for t in levels])
+        out, (self.last_march_kept, self.last_march_survivors) = self._render_march(
+            "neo_tp_render_marching", rays, chunk, _lib.TpMarchSamples,
+            ("fg_t", "fg_w", "bg_s", "stop", "fg_keep", "bg_stop", "bg_value"), ("fg_rows", "bg_rows"),
+            (eps, segment, int(bool(coarse)), int(bool(grid)), int(bool(outside))), 4, check_grid=bool(grid), keep_written=bool(grid),
+            fine_only=fine_only, return_samples=return_samples)
         return out
 
 

@@ -337,6 +337,23 @@ def render_decomposed_rays(model, batch, RTs=None, chunk=1024, check=True, on_ra
     return _render_guarded(model, batch, once, check, on_range)
 
 
+def _march_result(model, fine, kept, survivors=None):
+    """The dict of the skipping / marching frame wrappers from the fine level tuple and the call's device counters: rgb, depth, acc,
+    `kept_fraction` (kept[0:2] over the inside-sphere samples of each level), with a 4-entry `kept` also `kept_fraction_outside`
+    (kept[2:4] over the same counts), with `survivors` also `culled_fraction`.  No host read, no sync: the scalar divisors travel as
+    kernel arguments."""
+    R = fine[0].shape[0]
+    n0 = model.num_coarse_samples + 1
+    per = (float(max(R * n0, 1)), float(max(R * (n0 + model.num_fine_samples), 1)))
+    kept = kept.double()
+    out = dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=torch.stack([kept[0] / per[0], kept[1] / per[1]]))
+    if kept.shape[0] == 4:
+        out["kept_fraction_outside"] = torch.stack([kept[2] / per[0], kept[3] / per[1]])
+    if survivors is not None:
+        out["culled_fraction"] = 1.0 - survivors.double() / float(max(R, 1))
+    return out
+
+
 @torch.no_grad()
 def render_skipping_rays(model, batch, chunk=1024, check=True, on_range="retry_f32"):
     """Frame of a NeRF_TP module with empty space skipped: the fine level of `model.render_skipping` (which needs an occupancy
@@ -350,12 +367,7 @@ def render_skipping_rays(model, batch, chunk=1024, check=True, on_range="retry_f
 
     def once():
         res = model.render_skipping(batch, chunk=chunk)
-        fine = res[1]
-        R = fine[0].shape[0]
-        n0 = model.num_coarse_samples + 1
-        kept = model.last_skip_kept.double()          # scalar divisors travel as kernel arguments: no copy, no wait
-        frac = torch.stack([kept[0] / float(max(R * n0, 1)), kept[1] / float(max(R * (n0 + model.num_fine_samples), 1))])
-        return dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=frac)
+        return _march_result(model, res[1], model.last_skip_kept)
     return _render_guarded(model, batch, once, check, on_range)
 
 
@@ -372,13 +384,7 @@ def render_terminating_rays(model, batch, eps, chunk=1024, segment=64, coarse=Fa
 
     def once():
         res = model.render_terminating(batch, eps, chunk=chunk, segment=segment, coarse=coarse)
-        fine = res[1]
-        R = fine[0].shape[0]
-        n0 = model.num_coarse_samples + 1
-        kept = model.last_terminate_kept.double()          # scalar divisors travel as kernel arguments: no copy, no wait
-        frac = torch.stack([kept[0] / float(max(R * n0, 1)), kept[1] / float(max(R * (n0 + model.num_fine_samples), 1))])
-        culled = 1.0 - model.last_terminate_survivors.double() / float(max(R, 1))
-        return dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=frac, culled_fraction=culled)
+        return _march_result(model, res[1], model.last_terminate_kept, model.last_terminate_survivors)
     return _render_guarded(model, batch, once, check, on_range)
 
 
@@ -396,13 +402,7 @@ def render_accelerated_rays(model, batch, eps, chunk=1024, segment=64, coarse=Fa
 
     def once():
         res = model.render_accelerated(batch, eps, chunk=chunk, segment=segment, coarse=coarse)
-        fine = res[1]
-        R = fine[0].shape[0]
-        n0 = model.num_coarse_samples + 1
-        kept = model.last_accel_kept.double()          # scalar divisors travel as kernel arguments: no copy, no wait
-        frac = torch.stack([kept[0] / float(max(R * n0, 1)), kept[1] / float(max(R * (n0 + model.num_fine_samples), 1))])
-        culled = 1.0 - model.last_accel_survivors.double() / float(max(R, 1))
-        return dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=frac, culled_fraction=culled)
+        return _march_result(model, res[1], model.last_accel_kept, model.last_accel_survivors)
     return _render_guarded(model, batch, once, check, on_range)
 
 
@@ -422,15 +422,7 @@ def render_marching_rays(model, batch, eps, chunk=1024, segment=64, coarse=False
 
     def once():
         res = model.render_marching(batch, eps, chunk=chunk, segment=segment, coarse=coarse, outside=outside, grid=grid)
-        fine = res[1]
-        R = fine[0].shape[0]
-        n0 = model.num_coarse_samples + 1
-        kept = model.last_march_kept.double()          # scalar divisors travel as kernel arguments: no copy, no wait
-        per = (float(max(R * n0, 1)), float(max(R * (n0 + model.num_fine_samples), 1)))
-        frac = torch.stack([kept[0] / per[0], kept[1] / per[1]])
-        frac_out = torch.stack([kept[2] / per[0], kept[3] / per[1]])
-        culled = 1.0 - model.last_march_survivors.double() / float(max(R, 1))
-        return dict(rgb=fine[0], depth=fine[5], acc=fine[3], kept_fraction=frac, kept_fraction_outside=frac_out, culled_fraction=culled)
+        return _march_result(model, res[1], model.last_march_kept, model.last_march_survivors)
     return _render_guarded(model, batch, once, check, on_range)
 
 
