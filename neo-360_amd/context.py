@@ -10,27 +10,118 @@ from . import _lib
 _contexts = {}
 
 
-def _require_gpu(t, name):
+class NeoDeviceError(_lib.NeoError, ValueError):
+    """A tensor on the wrong device: a NeoError as ever (there is no CPU fallback), and a ValueError like every other breach of
+    a tensor contract."""
+
+
+def _require_gpu(t, name, exc=_lib.NeoError):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
     if not t.is_cuda:
-        raise _lib.NeoError(
+        raise exc(
             "%s is on %s: the neo360_amd path runs only on a ROCm device (there is no CPU fallback)" % (name, t.device))
 
 
+ALIGN = 16      # bytes: the widest load the kernels make through a pointer of the C ABI (float4)
+FLOATS = (torch.float32, torch.float64, torch.float16, torch.bfloat16)
+
+
+def _shape_text(shapes):
+    """'(7, 3) or (7,)': tuples as Python prints them, '*' for an extent that may be anything."""
+    return " or ".join("(%s%s)" % (", ".join("*" if e is None else str(int(e)) for e in s), "," if len(s) == 1 else "") for s in shapes)
+
+
+def _shape_fits(shape, want):
+    return len(shape) == len(want) and all(w is None or int(w) == int(e) for e, w in zip(shape, want))
+
+
+def _readable(t, dtype):
+    """t as a dense tensor of `dtype` whose first byte sits on a 16-byte boundary; t itself when it already is one."""
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    if not t.is_contiguous():
+        t = t.contiguous()
+    if t.data_ptr() % ALIGN:
+        t = t.clone(memory_format=torch.contiguous_format)      # a fresh allocation: the allocators align far beyond 16 bytes
+    return t
+
+
+def dense(t, name, shape=None, dtypes=FLOATS, to=torch.float32, device=None, on_device=True):
+    """The tensor contract of an entry point, applied to one argument: the dense, `to`-typed, 16-byte-aligned tensor the library
+    may read.  It is `t` itself when t already is that (same object: the callers' identity-keyed caches keep working), a copy
+    otherwise - of a strided, expanded, transposed or misaligned view, or of another accepted dtype; `t` is never written.
+
+    shape: the expected shape with the caller's symbolic extents already resolved - a tuple whose None entries accept any
+    extent, or a list of such tuples (alternatives, e.g. [(R,), (R, 1)]); None checks no shape.  dtypes: the accepted dtypes
+    (default: every floating-point type; pass e.g. (torch.int32,) with to=torch.int32 for an index table).  device: the device
+    the tensor must be on besides being a ROCm device (the device of the tensor that defines the call's sizes).
+    Raises TypeError for a non-tensor, ValueError("<name> must have shape ..., got ...") for a wrong rank or extent,
+    ValueError for a dtype outside `dtypes` or another device, and NeoDeviceError (a NeoError and a ValueError) for a tensor that
+    is on no ROCm device.  on_device=False switches the device requirements off: for a small table the wrapper reads on the host
+    (camera poses), and for the CPU tests of this function."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype not in dtypes:
+        kind = ("a floating-point" if all(d.is_floating_point for d in dtypes) else
+                "a bool" if tuple(dtypes) == (torch.bool,) else "an integer (%s)" % ", ".join(str(d) for d in dtypes))
+        raise ValueError("%s must be %s tensor, got %r" % (name, kind, t.dtype))
+    if shape is not None:
+        shapes = [tuple(shape)] if isinstance(shape, tuple) else [tuple(s) for s in shape]
+        if not any(_shape_fits(t.shape, s) for s in shapes):
+            raise ValueError("%s must have shape %s, got %s" % (name, _shape_text(shapes), tuple(t.shape)))
+    if on_device:
+        _require_gpu(t, name, NeoDeviceError)
+        if device is not None and t.device != device:
+            raise ValueError("%s must be on %s, got %s" % (name, device, t.device))
+    return _readable(t, to)
+
+
+def owned_output(t, name, shape, dtype=torch.float32, device=None, on_device=True):
+    """A caller-owned output (`out=`, `reuse=`): the library writes THROUGH it, so nothing is converted - a tensor of another
+    shape, dtype or device, a strided view or a misaligned one is refused with ValueError (TypeError for a non-tensor)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if not _shape_fits(t.shape, tuple(shape)):
+        raise ValueError("%s must have shape %s, got %s" % (name, _shape_text([tuple(shape)]), tuple(t.shape)))
+    if t.dtype != dtype:
+        raise ValueError("%s must be a %s tensor (it is written in place), got %r" % (name, dtype, t.dtype))
+    if on_device:
+        _require_gpu(t, name, NeoDeviceError)
+        if device is not None and t.device != device:
+            raise ValueError("%s must be on %s, got %s" % (name, device, t.device))
+    if not t.is_contiguous() or t.data_ptr() % ALIGN:
+        raise ValueError("%s must be a dense, 16-byte-aligned tensor (it is written in place, never through a copy), got strides %s "
+                         "at offset %d" % (name, tuple(t.stride()), t.storage_offset()))
+    return t
+
+
+def ray_rows(rays, keys=("rays_o", "rays_d", "viewdirs"), on_device=True):
+    """The (B,3) per-ray tensors of a batch as the library reads them, in the order of `keys`: rays["rays_o"] defines B and the
+    device, every other one must be (B,3) on that device (ValueError otherwise); any float dtype, any strides.  on_device=False:
+    shapes and dtype classes only (a frame helper that hands the batch on to a module call, which checks the device)."""
+    first = dense(rays["rays_o"], "rays_o", (None, 3), on_device=on_device)
+    conv = {"rays_o": first}
+    for k in keys:
+        if k != "rays_o":
+            conv[k] = dense(rays[k], k, (first.shape[0], 3), device=first.device if on_device else None, on_device=on_device)
+    return tuple(conv[k] for k in keys)
+
+
+def radii_shapes(B):
+    """Pixel radii of B rays: (B,1) as the reference's batches carry them, (B,), or the (1,B) row render._slice cuts."""
+    return [(B, 1), (B,), (1, B)]
+
+
 def f32(t, name="tensor"):
-    """Dense fp32 device tensor (copies only if needed)."""
+    """Dense, 16-byte-aligned fp32 device tensor (copies only if needed)."""
     _require_gpu(t, name)
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
+    return _readable(t, torch.float32)
 
 
 def f64(t, name="tensor"):
     _require_gpu(t, name)
-    if t.dtype != torch.float64:
-        t = t.double()
-    return t.contiguous()
+    return _readable(t, torch.float64)
 
 
 def ptr(t):

@@ -39,6 +39,7 @@ import torch.nn as nn
 
 from . import _lib
 from .context import f32, ptr, ptr_table
+from .context import dense
 from .models import _HipModule, _fingerprint
 
 
@@ -164,9 +165,10 @@ class GridEncoder(_HipModule):
     @torch.no_grad()
     def floorplans(self, latent, poses, focal, c, image_wh):
         """The pillar stage alone: latent (NV,512,Hf,Wf), poses (NV,4,4) c2w, focal (NV,), c (NV,2) (view 0's are used
-        for every view, encoder_tp_fusion_conv.py:491-493), image_wh = (W,H) of the encoded images.  Returns the
+        for every view, encoder_tp_fusion_conv.py:491-493), image_wh = (W,H) of the encoded images.  The latent defines NV; the
+        cameras are checked against it (ValueError) and read on the host; any float dtype, any strides.  Returns the
         channels-last floor-plans (yz (NV,G1,G2,512), xz (NV,G0,G2,512), xy (NV,G0,G1,512))."""
-        latent = f32(latent, "latent")
+        latent = _pillar_inputs(latent, poses, focal, c)
         dev = latent.device
         NV, C, Hf, Wf = latent.shape
         if C != self.LATENT:
@@ -204,6 +206,7 @@ class GridEncoder(_HipModule):
     def forward(self, images, poses, focal, c):
         """GridEncoder.forward (encoder_tp_fusion_conv.py:472-597): images (NV,3,H,W) -> three (NV,128,120,160) planes
         in the reference's return order (xz, xy, yz).  Leaves the pixel-aligned latent in `spatial_encoder.latent`."""
+        images = dense(images, "images", (None, None, None, None))      # any float dtype, any strides; the cameras: floorplans
         NV, _, H, W = images.shape
         self.spatial_encoder(images)
         latent = self.spatial_encoder.latent
@@ -213,6 +216,16 @@ class GridEncoder(_HipModule):
             yz, xz, xy = self.floorplans(latent, poses, focal, c, (W, H))
         nchw = lambda t: t.permute(0, 3, 1, 2)
         return self.floorplan_convnet_xz(nchw(xz)), self.floorplan_convnet_xy(nchw(xy)), self.floorplan_convnet_yz(nchw(yz))
+
+
+def _pillar_inputs(latent, poses, focal, c):
+    """The tensor contract of the pillar stage: latent (NV,C,Hf,Wf) on the device defines NV (any float dtype, any strides);
+    poses (NV,4,4), focal (NV,) and c (NV,2) are read on the host and may live anywhere.  Returns the latent as the library reads it."""
+    latent = dense(latent, "latent", (None, None, None, None))
+    nv = latent.shape[0]
+    for name, t, shape in (("poses", poses, (nv, 4, 4)), ("focal", focal, (nv,)), ("c", c, (nv, 2))):
+        dense(t, name, shape, on_device=False)
+    return latent
 
 
 def _camera_args(poses, focal, c):
@@ -232,7 +245,7 @@ class _PillarStage(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, enc, cams, latent, *params):
         poses, focal, c, image_wh = cams
-        latent32 = f32(latent.detach(), "latent")
+        latent32 = _pillar_inputs(latent.detach(), poses, focal, c)
         dev = latent32.device
         NV, C, Hf, Wf = latent32.shape
         if C != enc.LATENT:

@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .context import CallOverlap, f32, new_context, ptr, ptr_table
+from .context import CallOverlap, dense, f32, new_context, ptr, ptr_table
+from .context import radii_shapes as _radii_shapes, ray_rows as _ray_rows
 
 
 def _xavier_linear(n_in, n_out, xavier=True):
@@ -28,6 +29,11 @@ def _xavier_linear(n_in, n_out, xavier=True):
     if xavier:
         nn.init.xavier_uniform_(layer.weight)
     return layer
+
+
+def _sample_rows(t, name, rays_o):
+    """Caller sample positions (B,N) of a stage-level call: they define N, the rays define B."""
+    return dense(t, name, (rays_o.shape[0], None), device=rays_o.device)
 
 
 def _fingerprint(tensors):
@@ -334,7 +340,8 @@ class NeRF(_HipModule):
         return (self.coarse_mlp, self.fine_mlp)
 
     def forward(self, rays, randomized, white_bkgd, near, far, seed=None):
-        """Returns [(rgb (B,3), acc (B,), depth (B,))] * 2, as the reference.  randomized=True (stratified samples, random
+        """rays["rays_o"] (B,3) defines B; rays["rays_d"], rays["viewdirs"] (B,3): any float dtype, any strides.
+        Returns [(rgb (B,3), acc (B,), depth (B,))] * 2, as the reference.  randomized=True (stratified samples, random
         quantiles, `noise_std`) or a call that wants gradients (`_wants_grad`: the reference's training_step,
         vanilla_nerf/model.py:281-283) runs on the differentiable operators of training.py (nerf_render_train: NeRFMLP
         with a native backward, samplers on the counter-based generator, compositing with a native backward);
@@ -347,9 +354,7 @@ class NeRF(_HipModule):
 
     def _forward_fused(self, rays, white_bkgd, near, far):
         raw = (rays["rays_o"], rays["viewdirs"], rays["rays_d"])
-        rays_o = f32(raw[0], "rays_o")
-        viewdirs = f32(raw[1], "viewdirs")
-        rays_d = f32(raw[2], "rays_d")
+        rays_o, viewdirs, rays_d = _ray_rows(rays, ("rays_o", "viewdirs", "rays_d"))
         dev = rays_o.device
         ctx = self._context(dev)
         self._sync_weights(ctx)
@@ -372,8 +377,10 @@ class NeRF(_HipModule):
     @torch.no_grad()
     def eval_mlp(self, level, rays_o, dirs, t):
         """Stage-level access for parity tests: pos_enc + MLP + activations at
-        points o + t*dirs.  t (B,N) -> (B,N,4) = (rgb, sigma)."""
-        rays_o, dirs, t = f32(rays_o), f32(dirs), f32(t)
+        points o + t*dirs.  rays_o (B,3) defines B, dirs (B,3), t (B,N) defines N -> (B,N,4) = (rgb, sigma)."""
+        rays_o = dense(rays_o, "rays_o", (None, 3))
+        dirs = dense(dirs, "dirs", (rays_o.shape[0], 3), device=rays_o.device)
+        t = _sample_rows(t, "t", rays_o)
         ctx = self._context(rays_o.device)
         self._sync_weights(ctx)
         B, N = t.shape
@@ -503,7 +510,9 @@ class NeRF_TP(_HipModule):
     def set_scene(self, plane_xz, plane_xy, plane_yz, latent, image_wh, preproject=None, _source=None):
         """Scene features in the reference's layout: planes (NV,128,Hp,Wp), latent
         (NV,512,Hf,Wf), image_wh = (W,H) of the source images the latent was encoded from
-        (neo360/model.py:267-269).  Re-laid out channels-last on the device, once.
+        (neo360/model.py:267-269).  Re-laid out channels-last on the device, once.  plane_xz defines NV, the plane size and the
+        device; the other two planes must have its shape and the latent its NV (ValueError); any float dtype, any strides (a
+        permuted view is read by value).  The channel counts the evaluators need (128 / 512) are the library's check (NeoError).
         preproject (None = keep `self.preproject`): see that attribute."""
         src = _source if _source is not None else (plane_xz, plane_xy, plane_yz, latent)
         # the device copy is about to change: until the upload below has succeeded NO tensor set matches it
@@ -515,8 +524,10 @@ class NeRF_TP(_HipModule):
                                       # an upload from anywhere else (a training step's gather_features) must not leave an eval key behind
         if preproject is not None:
             self.preproject = int(preproject) if (preproject in (2, 3) and preproject is not True) else bool(preproject)
-        planes = [f32(p, "plane") for p in (plane_xz, plane_xy, plane_yz)]
-        latent = f32(latent, "latent")
+        # plane_xz defines (NV, Cw, Hp, Wp) and the device: the other planes must repeat it, the latent must hold the same NV views
+        first = dense(plane_xz, "plane_xz", (None, None, None, None))
+        planes = [first] + [dense(p, k, tuple(first.shape), device=first.device) for k, p in (("plane_xy", plane_xy), ("plane_yz", plane_yz))]
+        latent = dense(latent, "latent", (first.shape[0], None, None, None), device=first.device)
         ctx = self._context(latent.device)
         NV, Cw, Hp, Wp = planes[0].shape
         _, Cl, Hf, Wf = latent.shape
@@ -587,10 +598,11 @@ class NeRF_TP(_HipModule):
         """Stage-level access for parity tests: feature lookups + pos_enc + NeRFPPMLP +
         activations of one region at given sample positions.  slot 0/1 = fg coarse/fine
         (tvals = t), 2/3 = bg coarse/fine (tvals = descending inverse radius, needs far).
+        rays["rays_o"] (B,3) defines B, rays["rays_d"] / rays["viewdirs"] (B,3), tvals (B,N) defines N, far (B,) or (B,1).
         Returns (B,N,4) = (rgb, sigma)."""
-        rays_o, rays_d, viewdirs = f32(rays["rays_o"]), f32(rays["rays_d"]), f32(rays["viewdirs"])
-        tvals = f32(tvals, "tvals")
-        far = f32(far, "far") if far is not None else None
+        rays_o, rays_d, viewdirs = _ray_rows(rays)
+        tvals = _sample_rows(tvals, "tvals", rays_o)
+        far = dense(far, "far", [(rays_o.shape[0],), (rays_o.shape[0], 1)], device=rays_o.device) if far is not None else None
         ctx = self._context(rays_o.device)
         self._ensure_scene(rays, rays_o.device)
         self._sync_weights(ctx)
@@ -621,7 +633,7 @@ class NeRF_TP(_HipModule):
         torch's CPU generator, so torch.manual_seed makes runs repeatable)."""
         if self.density_noise != 0.0 and randomized:
             raise _lib.NeoError("density_noise is applied by the operator chain (training.tp_render_train), not by the fused call")
-        rays_o, rays_d, viewdirs = f32(rays["rays_o"], "rays_o"), f32(rays["rays_d"], "rays_d"), f32(rays["viewdirs"], "viewdirs")
+        rays_o, rays_d, viewdirs = _ray_rows(rays)
         dev = rays_o.device
         ctx = self._context(dev)
         self._ensure_scene(rays, dev)
@@ -1305,7 +1317,7 @@ class _TpFrameCall:
     def __init__(self, net, rays, chunk, use_grid):
         self.net, self.batch, self.use_grid = net, rays, use_grid
         self.raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
-        self.rays = (f32(self.raw[0], "rays_o"), f32(self.raw[1], "rays_d"), f32(self.raw[2], "viewdirs"))
+        self.rays = _ray_rows(rays)        # rays_o defines B; rays_d / viewdirs of another batch are refused here
         self.dev = self.rays[0].device
         self.B = self.rays[0].shape[0]
         self.chunk = int(chunk or max(self.B, 1))
@@ -1406,8 +1418,9 @@ class PixelNeRF(_HipModule):
         """latent (NV,512,Hf,Wf) as the reference's SpatialEncoder leaves it in `.latent`; image_wh = (W,H) of
         the source images (model_pixel.py:176-177).  Re-laid out channels-last on the device, once.  The module keeps a weak
         reference to the tensor: a differentiable forward sends the latent's gradient there."""
-        self._latent_src = weakref.ref(latent)
-        latent = f32(latent, "latent")
+        src = latent
+        latent = dense(latent, "latent", (None, None, None, None))
+        self._latent_src = weakref.ref(src)
         ctx = self._context(latent.device)
         NV, Cl, Hf, Wf = latent.shape
         _lib.check(ctx.lib.neo_pix_set_scene(ctx.handle, ptr(latent), NV, Cl, Hf, Wf, float(image_wh[0]),
@@ -1435,9 +1448,10 @@ class PixelNeRF(_HipModule):
     @torch.no_grad()
     def eval_mlp(self, slot, rays, tvals, chunk=None):
         """Stage-level access for parity tests: latent lookups + pos_enc + MLP + activations at sample
-        positions tvals (B,N) along rays_d.  Returns (B,N,4) = (sigmoid rgb, relu sigma)."""
-        rays_o, rays_d, viewdirs = f32(rays["rays_o"]), f32(rays["rays_d"]), f32(rays["viewdirs"])
-        tvals = f32(tvals, "tvals")
+        positions tvals (B,N) along rays_d.  rays["rays_o"] (B,3) defines B, rays["rays_d"] / rays["viewdirs"] (B,3), tvals
+        defines N.  Returns (B,N,4) = (sigmoid rgb, relu sigma)."""
+        rays_o, rays_d, viewdirs = _ray_rows(rays)
+        tvals = _sample_rows(tvals, "tvals", rays_o)
         ctx = self._context(rays_o.device)
         self._ensure_scene(rays)
         self._sync_weights(ctx)
@@ -1501,9 +1515,7 @@ class PixelNeRF(_HipModule):
 
     def _forward_fused(self, rays, white_bkgd, near, far, chunk=None):
         raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
-        rays_o = f32(raw[0], "rays_o")
-        rays_d = f32(raw[1], "rays_d")
-        viewdirs = f32(raw[2], "viewdirs")
+        rays_o, rays_d, viewdirs = _ray_rows(rays)
         dev = rays_o.device
         ctx = self._context(dev)
         self._ensure_scene(rays)
@@ -1629,8 +1641,8 @@ class MipNeRF360(_HipModule):
 
     def _forward_fused(self, batch, train_frac, near, far):
         raw = (batch["rays_o"], batch["rays_d"], batch["viewdirs"], batch["radii"])
-        rays_o, rays_d = f32(raw[0], "rays_o"), f32(raw[1], "rays_d")
-        viewdirs, radii = f32(raw[2], "viewdirs"), f32(raw[3], "radii")
+        rays_o, rays_d, viewdirs = _ray_rows(batch)
+        radii = dense(raw[3], "radii", _radii_shapes(rays_o.shape[0]), device=rays_o.device)
         dev = rays_o.device
         ctx = self._context(dev)
         self._sync_weights(ctx)
@@ -1663,9 +1675,13 @@ class MipNeRF360(_HipModule):
 
     @torch.no_grad()
     def eval_mlp(self, slot, batch, tdist):
-        """Stage-level access: cast_rays + MLP for the intervals of tdist (B,n+1) -> (B,n,4) = (rgb, density)."""
-        rays_o, rays_d = f32(batch["rays_o"]), f32(batch["rays_d"])
-        viewdirs, radii, tdist = f32(batch["viewdirs"]), f32(batch["radii"]), f32(tdist)
+        """Stage-level access: cast_rays + MLP for the intervals of tdist (B,n+1) -> (B,n,4) = (rgb, density).
+        batch["rays_o"] (B,3) defines B; rays_d, viewdirs (B,3), radii (B,1), (B,) or (1,B); tdist defines n."""
+        rays_o, rays_d, viewdirs = _ray_rows(batch)
+        radii = dense(batch["radii"], "radii", _radii_shapes(rays_o.shape[0]), device=rays_o.device)
+        tdist = _sample_rows(tdist, "tdist", rays_o)
+        if tdist.shape[1] < 2:
+            raise ValueError("tdist must have shape (%d, n + 1) with n >= 1, got %s" % (rays_o.shape[0], tuple(tdist.shape)))
         ctx = self._context(rays_o.device)
         self._sync_weights(ctx)
         B, n1 = tdist.shape

@@ -6,7 +6,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .context import f32, f64, get_context, ptr
+from .context import dense, f32, f64, get_context, owned_output, ptr
 
 
 def _ctx(t, ctx):
@@ -16,16 +16,20 @@ def _ctx(t, ctx):
 def get_ray_directions_and_rays(H, W, focal, c2w, ctx=None, device="cuda", ray_range=None, out=None):
     """datasets/ray_utils.py:84-104 + :133-176 in one kernel.
     c2w: (3,4) or (4,4) array-like (host).  Returns rays_o, viewdirs, rays_d (n,3), radii (n,) for the whole frame
-    (n = H W) or for rays [lo, hi) of it when ray_range = (lo, hi) (a rank's shard).  `out`: tensors to write into
-    (e.g. the previous frame's, so a render loop allocates nothing)."""
+    (n = H W) or for rays [lo, hi) of it when ray_range = (lo, hi) (a rank's shard).  `out`: the four tensors to write into
+    (e.g. the previous frame's, so a render loop allocates nothing): dense, 16-byte-aligned fp32 tensors of exactly these
+    shapes on the context's device - anything else is refused (ValueError / TypeError), nothing is written through a copy."""
     ctx = ctx if ctx is not None else get_context(device)
     dev = ctx.device
     pose = torch.as_tensor(c2w, dtype=torch.float32, device="cpu")[:3, :4].contiguous()
     host = (ctypes.c_float * 12)(*pose.reshape(-1).tolist())
     lo, hi = ray_range if ray_range is not None else (0, H * W)
     n = hi - lo
-    if out is not None and out[0].shape[0] == n:
-        rays_o, viewdirs, rays_d, radii = out
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            raise ValueError("out must be the four tensors (rays_o, viewdirs, rays_d, radii)")
+        rays_o, viewdirs, rays_d, radii = (owned_output(t, "out[%d] (%s)" % (i, k), sh, device=dev) for i, (t, k, sh) in enumerate(
+            zip(out, ("rays_o", "viewdirs", "rays_d", "radii"), ((n, 3), (n, 3), (n, 3), (n,)))))
         _lib.note_external_write()      # same tensor objects, same version counters, new contents
     else:
         rays_o = torch.empty(n, 3, device=dev)
@@ -37,10 +41,16 @@ def get_ray_directions_and_rays(H, W, focal, c2w, ctx=None, device="cuda", ray_r
     return rays_o, viewdirs, rays_d, radii
 
 
+def _ray_pair(a, name_a, b, name_b, to=torch.float32):
+    """Two (R,3) ray tensors of one call: `a` defines R and the device, `b` must match it."""
+    a = dense(a, name_a, (None, 3), to=to)
+    return a, dense(b, name_b, (a.shape[0], 3), to=to, device=a.device)
+
+
 def bbox_intersection_batch(bounds, rays_o, rays_d, ctx=None):
     """datasets/ray_utils.py:17-31 (float64).  bounds (2,3) host array-like; rays in the
-    box frame, (R,3) float64 device tensors.  Returns hit (uint8), tmin, tmax (float64)."""
-    rays_o, rays_d = f64(rays_o, "rays_o"), f64(rays_d, "rays_d")
+    box frame, (R,3) device tensors (rays_o defines R; any float dtype and any strides, read as float64).  Returns hit (uint8), tmin, tmax (float64)."""
+    rays_o, rays_d = _ray_pair(rays_o, "rays_o", rays_d, "rays_d", torch.float64)
     ctx = _ctx(rays_o, ctx)
     R = rays_o.shape[0]
     b = torch.as_tensor(bounds, dtype=torch.float64, device="cpu").reshape(6)
@@ -74,10 +84,10 @@ def _box_tables(RTs):
 def sample_rays_in_bbox(RTs, rays_o, view_dirs, ctx=None, return_per_box=False):
     """models/neo360/helper.py:359-373 (with get_object_rays_in_bbox :348-357 and get_rays_in_bbox :333-346 inside):
     RTs = dict(R=[3x3 or 9], T=[3], s=[(2,3) bounds]) per object; rays are moved into every box frame in float64,
-    slab-tested, and merged with 0 as the "no hit" sentinel.  rays_o / view_dirs: (R,3) device tensors (any float
-    dtype; the reference's NumPy arrays are promoted to float64 the same way).  Returns all_near (R,1), all_far (R,1)
+    slab-tested, and merged with 0 as the "no hit" sentinel.  rays_o / view_dirs: (R,3) device tensors (rays_o defines R; any
+    strides, any float dtype; the reference's NumPy arrays are promoted to float64 the same way).  Returns all_near (R,1), all_far (R,1)
     float32 and bbox_mask (R,1) bool, as the reference; with return_per_box also the per-box hit masks (n,R)."""
-    rays_o, view_dirs = f64(rays_o, "rays_o"), f64(view_dirs, "view_dirs")
+    rays_o, view_dirs = _ray_pair(rays_o, "rays_o", view_dirs, "view_dirs", torch.float64)
     ctx = _ctx(rays_o, ctx)
     R = rays_o.shape[0]
     n, hm, hb = _box_tables(RTs)
@@ -107,7 +117,7 @@ def sample_rays_in_bbox_list(RTs, rays_o, view_dirs, ctx=None):
     sample_rays_in_bbox, the same float64 transform and slab test.  Returns all_near (K,R,1), all_far (K,R,1) float32 with the
     reference's 0 = "no hit" sentinel (its stacked shape) and hit (K,R) bool - the reference's third value is a leftover of its
     loop, ours is the mask.  K = 0 returns empty tensors.  What `NeRF_TP.render_instances` takes as near_inst / far_inst."""
-    rays_o, view_dirs = f64(rays_o, "rays_o"), f64(view_dirs, "view_dirs")
+    rays_o, view_dirs = _ray_pair(rays_o, "rays_o", view_dirs, "view_dirs", torch.float64)
     ctx = _ctx(rays_o, ctx)
     R = rays_o.shape[0]
     n, hm, hb = _box_tables(RTs)
@@ -122,9 +132,9 @@ def sample_rays_in_bbox_list(RTs, rays_o, view_dirs, ctx=None):
 
 
 def intersect_sphere(rays_o, rays_d, ctx=None, check=True):
-    """models/neo360/helper.py:253-273.  Returns far (R,1) and the per-ray hit mask (uint8).
+    """models/neo360/helper.py:253-273.  rays_o (R,3) defines R, rays_d (R,3); any float dtype, any strides.  Returns far (R,1) and the per-ray hit mask (uint8).
     Raises AssertionError like the reference when a ray misses the unit sphere."""
-    rays_o, rays_d = f32(rays_o, "rays_o"), f32(rays_d, "rays_d")
+    rays_o, rays_d = _ray_pair(rays_o, "rays_o", rays_d, "rays_d")
     ctx = _ctx(rays_o, ctx)
     R = rays_o.shape[0]
     far = torch.empty(R, 1, device=rays_o.device)
@@ -136,8 +146,10 @@ def intersect_sphere(rays_o, rays_d, ctx=None, check=True):
 
 
 def pos_enc(x, min_deg, max_deg, ctx=None):
-    """neo360/helper.py:121-125 == vanilla_nerf/helper.py:445-449."""
-    x = f32(x, "x")
+    """neo360/helper.py:121-125 == vanilla_nerf/helper.py:445-449.  x (..., C), any float dtype, any strides."""
+    if isinstance(x, torch.Tensor) and x.dim() < 1:
+        raise ValueError("x must have shape (..., C), got %s" % (tuple(x.shape),))
+    x = dense(x, "x")
     ctx = _ctx(x, ctx)
     C = x.shape[-1]
     n = x.numel() // C
@@ -148,25 +160,38 @@ def pos_enc(x, min_deg, max_deg, ctx=None):
 
 def resample(t_prev, weights, n_new, descending=False, ctx=None):
     """sorted_piecewise_constant_pdf + the sort of sample_pdf, with the callers'
-    slicing (bins = midpoints of t_prev, pdf weights = weights[:,1:-1])."""
-    t_prev, weights = f32(t_prev, "t_prev"), f32(weights, "weights")
-    ctx = _ctx(t_prev, ctx)
+    slicing (bins = midpoints of t_prev, pdf weights = weights[:,1:-1]).  t_prev (R,n) defines R and n, weights (R,n);
+    any float dtype, any strides.  Returns (R, n + n_new)."""
+    t_prev = dense(t_prev, "t_prev", (None, None))
     R, n_prev = t_prev.shape
+    weights = dense(weights, "weights", (R, n_prev), device=t_prev.device)
+    ctx = _ctx(t_prev, ctx)
     out = torch.empty(R, n_prev + n_new, device=t_prev.device)
     _lib.check(ctx.lib.neo_resample(ctx.handle, ptr(t_prev), ptr(weights), R, n_prev, n_new, int(descending),
                                     ptr(out), ctx.stream()))
     return out
 
 
+def _composite_args(mode, rgbsigma, t, rays_d, t_far):
+    """The tensor contract of neo_composite, shared with training.composite: t (R,N) defines R, N and the device; rgbsigma
+    (R,N,4); rays_d (R,3), read by modes 0 and 1 and required there; t_far (R,) or (R,1), read by mode 1 and required there.
+    What a mode does not read is still checked when given; a missing one is the library's error (NeoError), as before."""
+    t = dense(t, "t", (None, None))
+    R, N = t.shape
+    rgbsigma = dense(rgbsigma, "rgbsigma", (R, N, 4), device=t.device)
+    rays_d = dense(rays_d, "rays_d", (R, 3), device=t.device) if rays_d is not None else None
+    t_far = dense(t_far, "t_far", [(R,), (R, 1)], device=t.device) if t_far is not None else None
+    return rgbsigma, t, rays_d, t_far
+
+
 def composite(mode, rgbsigma, t, rays_d=None, t_far=None, white_bkgd=False, ctx=None):
-    """volumetric_rendering; mode 0 vanilla, 1 NeO-360 inside, 2 NeO-360 outside.
+    """volumetric_rendering; mode 0 vanilla, 1 NeO-360 inside, 2 NeO-360 outside.  t (R,N) defines R and N; rgbsigma (R,N,4),
+    rays_d (R,3) (modes 0, 1), t_far (R,) or (R,1) (mode 1); any float dtype, any strides.
     Returns dict(rgb, acc, depth, weights, bg_lambda)."""
-    rgbsigma, t = f32(rgbsigma, "rgbsigma"), f32(t, "t")
+    rgbsigma, t, rays_d, t_far = _composite_args(mode, rgbsigma, t, rays_d, t_far)
     ctx = _ctx(t, ctx)
     R, N = t.shape
     dev = t.device
-    rays_d = f32(rays_d, "rays_d") if rays_d is not None else None
-    t_far = f32(t_far, "t_far") if t_far is not None else None
     rgb = torch.empty(R, 3, device=dev)
     acc = torch.empty(R, device=dev)
     depth = torch.empty(R, device=dev)
@@ -179,10 +204,12 @@ def composite(mode, rgbsigma, t, rays_d=None, t_far=None, white_bkgd=False, ctx=
 
 
 def mip_resample(s_prev, w_prev, n, near, far, dilate=False, dilation=0.0, anneal=1.0, ctx=None):
-    """One Mip-NeRF 360 proposal-resampling step (mipnerf360/model.py:258-310).  Returns sdist, tdist (R,n+1)."""
-    s_prev, w_prev = f32(s_prev, "s_prev"), f32(w_prev, "w_prev")
-    ctx = _ctx(s_prev, ctx)
+    """One Mip-NeRF 360 proposal-resampling step (mipnerf360/model.py:258-310).  w_prev (R,n_prev) defines R and n_prev,
+    s_prev (R,n_prev+1); any float dtype, any strides.  Returns sdist, tdist (R,n+1)."""
+    w_prev = dense(w_prev, "w_prev", (None, None))
     R, n_prev = w_prev.shape
+    s_prev = dense(s_prev, "s_prev", (R, n_prev + 1), device=w_prev.device)
+    ctx = _ctx(s_prev, ctx)
     sdist = torch.empty(R, n + 1, device=s_prev.device)
     tdist = torch.empty(R, n + 1, device=s_prev.device)
     _lib.check(ctx.lib.neo_mip_resample(ctx.handle, ptr(s_prev), ptr(w_prev), R, n_prev, int(bool(dilate)),
@@ -192,10 +219,15 @@ def mip_resample(s_prev, w_prev, n, near, far, dilate=False, dilation=0.0, annea
 
 
 def mip_composite(rgbdens, tdist, rays_d, bg=1.0, ctx=None):
-    """compute_alpha_weights(opaque_background=True) + volumetric_rendering (mipnerf360/helper.py:246-274)."""
-    rgbdens, tdist, rays_d = f32(rgbdens), f32(tdist), f32(rays_d)
-    ctx = _ctx(tdist, ctx)
+    """compute_alpha_weights(opaque_background=True) + volumetric_rendering (mipnerf360/helper.py:246-274).
+    tdist (R,n+1) defines R and n, rgbdens (R,n,4), rays_d (R,3); any float dtype, any strides.  Returns weights (R,n), rgb (R,3)."""
+    tdist = dense(tdist, "tdist", (None, None))
     R, n1 = tdist.shape
+    if n1 < 1:
+        raise ValueError("tdist must have shape (R, n + 1), got %s" % (tuple(tdist.shape),))
+    rgbdens = dense(rgbdens, "rgbdens", (R, n1 - 1, 4), device=tdist.device)
+    rays_d = dense(rays_d, "rays_d", (R, 3), device=tdist.device)
+    ctx = _ctx(tdist, ctx)
     w = torch.empty(R, n1 - 1, device=tdist.device)
     rgb = torch.empty(R, 3, device=tdist.device)
     _lib.check(ctx.lib.neo_mip_composite(ctx.handle, ptr(rgbdens), ptr(tdist), ptr(rays_d), R, n1 - 1, float(bg), ptr(w),
@@ -208,7 +240,7 @@ _QUANTILES = {}     # (device, quantiles) -> the fp32 device table neo_mip_extra
 
 def _quantile_table(u, dev):
     if isinstance(u, torch.Tensor):
-        return f32(u.reshape(-1), "u")
+        return dense(u.reshape(-1), "u", device=dev)
     key = (dev, tuple(float(x) for x in u))
     tab = _QUANTILES.get(key)
     if tab is None:
@@ -224,10 +256,14 @@ def mip_extras(edges, w, u=(0.05, 0.5, 0.95), near=0.0, far=0.0, ctx=None):
     (helper.py:196-222).  near == far == 0: edges are metric distances; otherwise edges are sdist and t = s_to_t(edges) for that near /
     far, formed inside the kernel.  u: up to 8 ascending quantiles in [0, 1], a sequence (its device table is kept) or an fp32 device
     tensor.  No gradients: training.mip_expected_distance is the differentiable (acc, distance_mean)."""
-    edges, w = f32(edges, "edges"), f32(w, "w")
+    edges, w = dense(edges, "edges"), dense(w, "w")
+    if edges.dim() < 1 or w.dim() < 1:
+        raise ValueError("edges must have shape (..., n + 1) and w (..., n), got %s %s" % (tuple(edges.shape), tuple(w.shape)))
     n = w.shape[-1]
     if edges.shape[-1] != n + 1 or edges.shape[:-1] != w.shape[:-1]:
         raise ValueError("edges must hold one more entry per row than w, got %s %s" % (tuple(edges.shape), tuple(w.shape)))
+    if edges.device != w.device:
+        raise ValueError("edges must be on %s, got %s" % (w.device, edges.device))
     ctx = _ctx(w, ctx)
     e2, w2 = edges.reshape(-1, n + 1), w.reshape(-1, n)
     R, dev = w2.shape[0], w.device
@@ -353,6 +389,13 @@ def edit_table(K, density_scale=None, tint=None):
     return out[0], out[1]
 
 
+def _floating(who, *named):
+    """ValueError for an integer or bool tensor where samples are meant (the conversion to fp32 would hide the mix-up)."""
+    for name, v in named:
+        if not v.is_floating_point():
+            raise ValueError("%s: %s must be a floating-point tensor, got %r" % (who, name, v.dtype))
+
+
 @torch.no_grad()
 def edit_rgbsigma(rgbsigma, t, near_inst, far_inst, density_scale=None, tint=None, ctx=None):
     """The edit of `NeRF_TP.render_edited` on caller rows (neo_tp_edit_rows): an edited COPY of rgbsigma (R,N,4) at the sample rows
@@ -365,6 +408,7 @@ def edit_rgbsigma(rgbsigma, t, near_inst, far_inst, density_scale=None, tint=Non
     R, N = t.shape
     if not isinstance(rgbsigma, torch.Tensor) or tuple(rgbsigma.shape) != (R, N, 4) or rgbsigma.device != t.device:
         raise ValueError("rgbsigma must be a (%d, %d, 4) tensor on the device of t" % (R, N))
+    _floating("edit_rgbsigma", ("t", t), ("rgbsigma", rgbsigma))
     K = _edit_bounds(near_inst, far_inst, R, t.device, "edit_rgbsigma")
     scale, tints = edit_table(K, density_scale, tint)
     near_c, far_c = _edit_rows(near_inst, far_inst, K, R)
@@ -453,7 +497,8 @@ def _layer_struct(layers, L):
 @torch.no_grad()
 def composite_layers(rgbsigma, t, rays_d, t_far, layers, ctx=None):
     """`composite(1, ...)` with up to 32 per-ray layers spliced into the ray (neo_composite_layers; the LAYER RECURRENCE of
-    include/neo360_hip.h).  layers: dict(key (L,R) ray parameters, rgb (L,R,3) premultiplied colours, acc (L,R) opacities, depth
+    include/neo360_hip.h).  t (R,N) defines R and N; rgbsigma (R,N,4), rays_d (R,3), t_far (R,) or (R,1): any float dtype, any
+    strides.  layers: dict(key (L,R) ray parameters, rgb (L,R,3) premultiplied colours, acc (L,R) opacities, depth
     (L,R) premultiplied depths) or None.  A layer is valid iff its key is finite and its acc > 0; valid layers act in ascending key
     (ties: lower index) as slabs with keep = max(1 - acc, 0) placed before the first sample at or beyond their key.
     Returns dict(rgb, acc, depth, weights, bg_lambda, visibility (L,R)); `weights` are the scene's own (those of `composite`), and
@@ -463,8 +508,9 @@ def composite_layers(rgbsigma, t, rays_d, t_far, layers, ctx=None):
     R, N = t.shape
     dev = t.device
     L = _layer_rows(layers, R, dev, "composite_layers")
-    rgbsigma, t = f32(rgbsigma, "rgbsigma"), f32(t, "t")
-    rays_d, t_far = f32(rays_d, "rays_d"), f32(t_far, "t_far")
+    rgbsigma, t, rays_d, t_far = _composite_args(1, rgbsigma, t, rays_d, t_far)
+    if rays_d is None or t_far is None:
+        raise ValueError("composite_layers: rays_d must have shape (%d, 3) and t_far (%d,) or (%d, 1), got None" % (R, R, R))
     ctx = _ctx(t, ctx)
     rows, struct = _layer_struct(layers, L)
     rgb = torch.empty(R, 3, device=dev)
@@ -532,6 +578,7 @@ def occupancy_keep(occ, rays_o, rays_d, t, ctx=None):
             raise ValueError("occupancy_keep: %s must be a (%d, 3) tensor on the device of t" % (name, B))
     if N < 1:
         raise ValueError("occupancy_keep: at least one sample per ray")
+    _floating("occupancy_keep", ("rays_o", rays_o), ("rays_d", rays_d))
     rays_o, rays_d, t = f32(rays_o, "rays_o"), f32(rays_d, "rays_d"), f32(t, "t")
     ctx = _ctx(t, ctx)
     bits = pack_occupancy(occ.to(t.device)) if occ is not None else None
@@ -610,6 +657,7 @@ def termination_stops(rgbsigma, t, rays_d, t_far, eps, segment=64, ctx=None):
         raise ValueError("termination_stops: rays_d must be a (%d, 3) tensor on the device of t" % B)
     if not isinstance(t_far, torch.Tensor) or tuple(t_far.shape) not in ((B,), (B, 1)) or t_far.device != t.device:
         raise ValueError("termination_stops: t_far must be a (%d,) or (%d, 1) tensor on the device of t" % (B, B))
+    _floating("termination_stops", ("rgbsigma", rgbsigma), ("rays_d", rays_d), ("t_far", t_far))
     rgbsigma, t, rays_d, t_far = f32(rgbsigma, "rgbsigma"), f32(t, "t"), f32(rays_d, "rays_d"), f32(t_far.reshape(B), "t_far")
     ctx = _ctx(t, ctx)
     stop = torch.empty(B, dtype=torch.int32, device=t.device)
@@ -638,6 +686,7 @@ def termination_stops_outside(rgbsigma, s, bg_lambda, eps, segment=64, ctx=None)
         raise ValueError("termination_stops_outside: rgbsigma must be a (%d, %d, 4) tensor on the device of s" % (B, N))
     if not isinstance(bg_lambda, torch.Tensor) or tuple(bg_lambda.shape) not in ((B,), (B, 1)) or bg_lambda.device != s.device:
         raise ValueError("termination_stops_outside: bg_lambda must be a (%d,) or (%d, 1) tensor on the device of s" % (B, B))
+    _floating("termination_stops_outside", ("rgbsigma", rgbsigma), ("bg_lambda", bg_lambda))
     rgbsigma, s, bg_lambda = f32(rgbsigma, "rgbsigma"), f32(s, "s"), f32(bg_lambda.reshape(B), "bg_lambda")
     ctx = _ctx(s, ctx)
     stop = torch.empty(B, dtype=torch.int32, device=s.device)

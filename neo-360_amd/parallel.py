@@ -64,6 +64,8 @@ def gather_tiles(tile, n_rays, world, unit=1024, group=None, out=None, reuse=Fal
     equal = all(c == biggest for c in counts)
     if out is not None:
         assert tuple(out.shape) == (n_rays, C) and out.is_contiguous(), "out must be a contiguous (n_rays, C) tensor"
+        if out.dtype != tile.dtype or out.device != tile.device:        # the collective writes through it: nothing is converted
+            raise ValueError("out must be a %s tensor on %s like the tile, got %s on %s" % (tile.dtype, tile.device, out.dtype, out.device))
         frame = out
     elif reuse:
         frame = _buffer(("frame", gid), (n_rays, C), tile)

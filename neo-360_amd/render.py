@@ -11,6 +11,7 @@ import warnings
 import torch
 
 from . import _lib, models
+from .context import dense, radii_shapes, ray_rows
 from .parallel import gather_tiles, shard_bounds
 
 _WHOLE = ("src_imgs", "src_poses", "src_focal", "src_c")
@@ -226,6 +227,7 @@ def instance_layers(model, batch, RTs, moves, chunk=1024):
     from . import ops
     K = len(RTs["R"])
     moves = _check_moves(moves, K)
+    ray_rows(batch)         # rays_o defines R: the moved rays below are formed per tensor, so a tensor of another frame is refused first
     dev = batch["rays_o"].device
     R = batch["rays_o"].shape[0]
     out = dict(key=[], rgb=[], acc=[], depth=[])
@@ -441,6 +443,11 @@ def render_frame_sharded(model, batch, world, rank, chunk=1024, white_bkgd=False
     "f32": a range-guard retry, see render_rays_test) and, when the frame is gathered over more than one rank,
     `precision_by_rank` (one extra 4-byte all-gather, only when `info` is given): a frame whose ranks mixed arithmetics
     says so instead of hiding it in the gathered tile."""
+    # rays_o defines the rows of the batch: checked before `_slice` cuts every tensor to the shard's rows, which would make a
+    # longer tensor of another frame pass for this frame's
+    first = ray_rows(batch, tuple(k for k in ("rays_o", "rays_d", "viewdirs") if k in batch), on_device=False)[0]
+    if "radii" in batch:
+        dense(batch["radii"], "radii", radii_shapes(first.shape[0]), on_device=False)
     if n_rays is None:
         R = batch["rays_o"].shape[0]
         lo, hi = shard_bounds(R, world, rank, unit=chunk)

@@ -18,7 +18,7 @@ import os
 import torch
 
 from . import _lib
-from .context import f32, get_context, ptr, ptr_table
+from .context import dense, f32, get_context, ptr, ptr_table, radii_shapes, ray_rows
 
 
 def _ctx(t, ctx):
@@ -34,25 +34,31 @@ def rand_uniform(seed, stream_id, rows, cols, device="cuda", ctx=None):
 
 
 def sample_level0(far, n_coarse, u_fg=None, u_bg=None, ctx=None):
-    """neo360/helper.py:24-75 for both regions.  far (R,1) or (R,); u_* (R, n_coarse+1) uniforms = randomized=True.
+    """neo360/helper.py:24-75 for both regions.  far (R,1) or (R,) defines R; u_* (R, n_coarse+1) uniforms = randomized=True
+    (both or neither); any float dtype, any strides.
     Returns fg_t (ascending t) and bg_s (descending inverse radius), (R, n_coarse+1) each."""
-    far = f32(far, "far").reshape(-1)
+    far = dense(far, "far", [(None,), (None, 1)]).reshape(-1)
     ctx = _ctx(far, ctx)
     R = far.shape[0]
+    if (u_fg is None) != (u_bg is None):
+        raise ValueError("u_fg and u_bg go together: give both (randomized=True), or neither")
+    u_fg = dense(u_fg, "u_fg", (R, n_coarse + 1), device=far.device) if u_fg is not None else None
+    u_bg = dense(u_bg, "u_bg", (R, n_coarse + 1), device=far.device) if u_bg is not None else None
     fg = torch.empty(R, n_coarse + 1, device=far.device)
     bg = torch.empty(R, n_coarse + 1, device=far.device)
-    u_fg = f32(u_fg, "u_fg") if u_fg is not None else None
-    u_bg = f32(u_bg, "u_bg") if u_bg is not None else None
     _lib.check(ctx.lib.neo_tp_sample_level0(ctx.handle, ptr(far), R, n_coarse, ptr(u_fg), ptr(u_bg), ptr(fg), ptr(bg),
                                             ctx.stream()))
     return fg, bg
 
 
 def resample_u(t_prev, weights, u, descending=False, ctx=None):
-    """sorted_piecewise_constant_pdf(randomized=True) + the sort of sample_pdf with the caller's uniforms u (R, n_new)."""
-    t_prev, weights, u = f32(t_prev, "t_prev"), f32(weights, "weights").detach(), f32(u, "u")
-    ctx = _ctx(t_prev, ctx)
+    """sorted_piecewise_constant_pdf(randomized=True) + the sort of sample_pdf with the caller's uniforms u (R, n_new).
+    t_prev (R,n) defines R and n, weights (R,n), u defines n_new; any float dtype, any strides.  Returns (R, n + n_new)."""
+    t_prev = dense(t_prev, "t_prev", (None, None))
     R, n_prev = t_prev.shape
+    weights = dense(weights, "weights", (R, n_prev), device=t_prev.device).detach()
+    u = dense(u, "u", (R, None), device=t_prev.device)
+    ctx = _ctx(t_prev, ctx)
     n_new = u.shape[1]
     out = torch.empty(R, n_prev + n_new, device=t_prev.device)
     _lib.check(ctx.lib.neo_resample_u(ctx.handle, ptr(t_prev), ptr(weights), ptr(u), R, n_prev, n_new, int(descending),
@@ -64,16 +70,18 @@ class _Composite(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, mode, rgb, sigma, t, rays_d, t_far, white_bkgd, lib_ctx):
         packed = sigma is None                  # rgb is the packed (R,N,4) = (rgb, sigma) tensor of `activate`
-        if packed:
-            rgbsigma = f32(rgb, "rgbsigma")
-        else:
-            rgbsigma = torch.cat([f32(rgb, "rgb"), f32(sigma, "sigma").reshape(*rgb.shape[:-1], 1)], dim=-1).contiguous()
-        t = f32(t, "t")
-        c = _ctx(t, lib_ctx)
+        t = dense(t, "t", (None, None))         # t defines R, N and the device
         R, N = t.shape
         dev = t.device
-        rays_d = f32(rays_d, "rays_d") if rays_d is not None else None
-        t_far = f32(t_far, "t_far").reshape(-1) if t_far is not None else None
+        if packed:
+            rgbsigma = rgb
+        else:
+            rgbsigma = torch.cat([dense(rgb, "rgb", (R, N, 3), device=dev),
+                                  dense(sigma, "sigma", [(R, N, 1), (R, N)], device=dev).reshape(R, N, 1)], dim=-1)
+        from .ops import _composite_args
+        rgbsigma, t, rays_d, t_far = _composite_args(mode, rgbsigma, t, rays_d, t_far)
+        t_far = t_far.reshape(-1) if t_far is not None else None
+        c = _ctx(t, lib_ctx)
         out_rgb, acc, depth = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
         w = torch.empty(R, N, device=dev)
         lam = torch.empty(R, 1, device=dev) if mode == 1 else torch.zeros(R, 1, device=dev)
@@ -108,7 +116,8 @@ class _Composite(torch.autograd.Function):
 
 def composite(mode, rgb, sigma, t, rays_d=None, t_far=None, white_bkgd=False, ctx=None):
     """Differentiable volumetric_rendering.  mode 0 vanilla, 1 NeO-360 inside the sphere, 2 outside.
-    rgb (R,N,3), sigma (R,N,1) -> (comp_rgb (R,3), acc (R,), weights (R,N), bg_lambda (R,1), depth (R,));
+    t (R,N) defines R and N; rgb (R,N,3), sigma (R,N,1) or (R,N), rays_d (R,3), t_far (R,) or (R,1): any float dtype, any
+    strides -> (comp_rgb (R,3), acc (R,), weights (R,N), bg_lambda (R,1), depth (R,));
     gradients flow to rgb and sigma (sample positions are detached in the reference, helper.py:224).
     sigma=None: `rgb` is the packed (R,N,4) = (rgb, sigma) tensor `activate` returns (no concatenation)."""
     return _Composite.apply(mode, rgb, sigma, t, rays_d, t_far, white_bkgd, ctx)
@@ -117,11 +126,12 @@ def composite(mode, rgb, sigma, t, rays_d=None, t_far=None, white_bkgd=False, ct
 class _Activate(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, raw_rgb, raw_sigma, noise, noise_scale, lib_ctx):
-        raw_rgb, raw_sigma = f32(raw_rgb, "raw_rgb"), f32(raw_sigma, "raw_sigma")
+        raw_sigma = dense(raw_sigma, "raw_sigma")       # raw_sigma defines P and the device
+        raw_rgb = dense(raw_rgb, "raw_rgb", device=raw_sigma.device)
         P = raw_sigma.numel()
         if raw_rgb.numel() != 3 * P:
             raise ValueError("raw_rgb must hold 3 values per raw_sigma entry, got %s / %s" % (tuple(raw_rgb.shape), tuple(raw_sigma.shape)))
-        noise = f32(noise, "noise") if noise is not None else None
+        noise = dense(noise, "noise", device=raw_sigma.device) if noise is not None else None
         if noise is not None and noise.numel() != P:
             raise ValueError("noise must hold one value per point")
         c = _ctx(raw_sigma, lib_ctx)
@@ -156,18 +166,23 @@ def train_points(module, region, rays_o, rays_d, tvals, far, poses, ctx=None):
     feature lookups and x_enc (NV, R*N, 63 | 84) reference-order encodings of the camera-frame point per source view
     (neo_tp_train_points: the evaluators' own per-point set-up - neo360/helper.py:24-75, :401-451, util.py:52-70 - so the
     operator chain and the fused kernels see bitwise the same points).  No gradients: sample positions are detached in the
-    reference (helper.py:224) and the rays / poses are data."""
-    rays_o, rays_d, tvals = f32(rays_o, "rays_o"), f32(rays_d, "rays_d"), f32(tvals, "tvals")
+    reference (helper.py:224) and the rays / poses are data.  rays_o (R,3) defines R; rays_d (R,3), tvals (R,N) defines N,
+    far (R,) or (R,1) (read outside the sphere), poses (NV,4,4) defines NV; any float dtype, any strides."""
+    rays_o = dense(rays_o, "rays_o", (None, 3))
+    R, dev = rays_o.shape[0], rays_o.device
+    rays_d, tvals = dense(rays_d, "rays_d", (R, 3), device=dev), dense(tvals, "tvals", (R, None), device=dev)
+    if far is None and region:
+        raise ValueError("far must have shape (%d,) or (%d, 1), got None (the outside region reads it)" % (R, R))
     c = _ctx(rays_o, ctx)
-    R, N = tvals.shape
-    poses = f32(poses, "src_poses")
+    N = tvals.shape[1]
+    poses = dense(poses, "src_poses", (None, 4, 4))
     NV = poses.shape[0]
     host = poses.detach().cpu().contiguous()
     host_poses = (ctypes.c_float * (16 * NV))(*host.reshape(-1).tolist())
     ch = 4 if region else 3
     look = torch.empty(R * N, 3, device=rays_o.device)
     x_enc = torch.empty(NV, R * N, 21 * ch, device=rays_o.device)
-    far = f32(far, "far").reshape(-1) if far is not None else None
+    far = dense(far, "far", [(R,), (R, 1)], device=dev).reshape(-1) if far is not None else None
     _lib.check(c.lib.neo_tp_train_points(c.handle, ch, ptr(rays_o), ptr(rays_d), ptr(tvals), ptr(far), R, N, host_poses, NV,
                                          ptr(look), ptr(x_enc), c.stream()))
     return look, x_enc
@@ -176,7 +191,11 @@ def train_points(module, region, rays_o, rays_d, tvals, far, poses, ctx=None):
 class _DistLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, w, m, interval, lib_ctx):
-        w2, m2 = f32(w, "w").reshape(-1, w.shape[-1]), f32(m, "m").reshape(-1, w.shape[-1])
+        w = dense(w, "w")
+        if w.dim() < 1:
+            raise ValueError("w must have shape (..., N), got ()")
+        m = dense(m, "m", tuple(w.shape), device=w.device)
+        w2, m2 = w.reshape(-1, w.shape[-1]), m.reshape(-1, w.shape[-1])
         c = _ctx(w2, lib_ctx)
         R, N = w2.shape
         loss = torch.empty(R, device=w2.device)
@@ -194,7 +213,8 @@ class _DistLoss(torch.autograd.Function):
 
 
 def eff_distloss(w, m, interval, ctx=None):
-    """torch_efficient_distloss.eff_distloss: w (..., N) weights, m (..., N) interval midpoints, scalar interval."""
+    """torch_efficient_distloss.eff_distloss: w (..., N) weights define the shape, m (..., N) interval midpoints of
+    that shape, scalar interval; any float dtype, any strides."""
     return _DistLoss.apply(w, m, interval, ctx)
 
 
@@ -241,6 +261,14 @@ def shared_grad_buffers(shared, make):
     return box["bufs"]
 
 
+def _points(pts):
+    """World points (..., 3) of a lookup as dense fp32 (P,3) rows: any float dtype, any strides."""
+    pts = dense(pts, "pts")
+    if pts.dim() < 1 or pts.shape[-1] != 3:
+        raise ValueError("pts must have shape (..., 3), got %s" % (tuple(pts.shape),))
+    return pts.reshape(-1, 3)
+
+
 class _Gather(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, module, pts, plane_xz, plane_xy, plane_yz, latent, rays, planes_only=False, shared=None, src=None):
@@ -248,7 +276,7 @@ class _Gather(torch.autograd.Function):
         # version (an optimizer step or a fresh encoder output would otherwise leave the forward values stale while
         # gradients still flow to the arguments) - re-upload when the fingerprint differs.  src: the caller's tensor objects
         # when the planes arrive through a shared-gradient sink (its outputs are new views of the same tensors)
-        pts = f32(pts, "pts").reshape(-1, 3)
+        pts = _points(pts)
         maps = tuple(src) if src is not None else (plane_xz, plane_xy, plane_yz, latent)
         if not module.scene_matches(maps):
             module.set_scene(*(m.detach() for m in maps), module.scene_image_wh(rays), _source=maps)
@@ -319,7 +347,7 @@ class _ChannelsLast(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx_, x, lib_ctx):
-        x = f32(x, "map")
+        x = dense(x, "map")
         if x.dim() != 4:
             raise ValueError("expected an NCHW map, got %s" % (tuple(x.shape),))
         if not x.is_contiguous():
@@ -363,8 +391,8 @@ class _MapGather(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx_, module, gmap, pts, rays, kind="tp", col=None, width=None, shared=None):
-        pts = f32(pts, "pts").reshape(-1, 3)
-        gmap = f32(gmap, "map")
+        pts = _points(pts)
+        gmap = dense(gmap, "map", device=pts.device)
         if gmap.dim() != 2 or gmap.shape[1] % 64 != 0:
             raise ValueError("map must be (texels, C) with C a multiple of 64, got %s" % (tuple(gmap.shape),))
         c = module._context(pts.device)
@@ -462,9 +490,18 @@ def _check_layers(what, ws, bs, want):
                              % (what, i, tuple(w.shape), tuple(b.shape), want[i], want[i][0]))
 
 
+def _floating_rows(name, t):
+    """Row tensors of a chain are samples: an integer or bool tensor (or a non-tensor) is a mix-up the fp32 conversion would hide."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if not t.is_floating_point():
+        raise ValueError("%s must be a floating-point tensor, got %r" % (name, t.dtype))
+
+
 def _check_rows(rows, *named):
     """View-major row tensors (name, tensor, width): each must be (NV*P, width)."""
     for name, t, width in named:
+        _floating_rows(name, t)
         if tuple(t.shape) != (rows, width):
             raise ValueError("%s must be (NV*P, %d) = (%d, %d), got %s" % (name, width, rows, width, tuple(t.shape)))
 
@@ -499,7 +536,8 @@ class _TrainMLPPre(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, lib_ctx, input_ch, nv, x_enc, cond_rows, world_feat, pre, *params):
         ws, bs = params[:9], params[9:]
-        pe, npts = input_ch * 21, x_enc.shape[1]
+        _floating_rows("x_enc", x_enc)
+        pe, npts = input_ch * 21, x_enc.shape[1] if x_enc.dim() > 1 else -1
         if x_enc.dim() != 3 or tuple(x_enc.shape) != (nv, npts, pe):
             raise ValueError("x_enc must be (NV, P, %d), got %s" % (pe, tuple(x_enc.shape)))
         _check_rows(nv * npts, ("cond_rows", cond_rows, 27), ("world_feat", world_feat, 128), ("pre", pre, 256))
@@ -545,16 +583,22 @@ class _Linear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx_, lib_ctx, x, w, b, relu):
-        x = f32(x, "x")
+        x = dense(x, "x")               # x (rows, in) defines the rows, `in` and the device
+        if not isinstance(w, torch.Tensor) or not w.is_floating_point():
+            raise ValueError("W must be a floating-point tensor, got %r" % (w.dtype if isinstance(w, torch.Tensor) else type(w).__name__,))
         if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
             raise ValueError("x (rows, in) and W (out, in) do not match: %s, %s" % (tuple(x.shape), tuple(w.shape)))
+        if w.device != x.device:
+            raise ValueError("W must be on %s, got %s" % (x.device, w.device))
         c = _ctx(x, lib_ctx)
         wd = w.detach()
-        if wd.dtype != torch.float32 or wd.stride(1) != 1:
+        # a column block of a wider weight is read in place through its row pitch (the GEMM loads W element by element, so a block
+        # may start at any column); anything else that is not dense fp32 is copied
+        if wd.dtype != torch.float32 or wd.stride(1) != 1 or (wd.shape[0] > 1 and wd.stride(0) < wd.shape[1]):
             wd = wd.float().contiguous()
         rows, out_f, in_f = x.shape[0], w.shape[0], w.shape[1]
         y = torch.empty(rows, out_f, device=x.device)
-        bd = f32(b.detach(), "bias") if b is not None else None
+        bd = dense(b.detach(), "b", (w.shape[0],), device=x.device) if b is not None else None
         _lib.check(c.lib.neo_linear_forward(c.handle, rows, out_f, in_f, ptr(x), in_f, ptr(wd), wd.stride(0), ptr(bd) if bd is not None else None,
                                             int(bool(relu)), 0, ptr(y), out_f, c.stream()))
         ctx_.save_for_backward(x, wd, y if relu else None)
@@ -566,7 +610,7 @@ class _Linear(torch.autograd.Function):
     def backward(ctx_, gy):
         x, wd, y = ctx_.saved_tensors
         c, relu, has_b = ctx_.meta
-        g = gy.contiguous()
+        g = f32(gy, "gy")
         if relu:
             g = g * (y > 0)
         rows, out_f, in_f = x.shape[0], wd.shape[0], wd.shape[1]
@@ -598,7 +642,8 @@ def _linear_no_bias(lib_ctx, x, w):
 def weight_grad(gy, x, bias=False, ctx=None):
     """dW (M, N) = gy^T x over the rows of gy (K, M) and x (K, N) (and db = column sums of gy with bias=True): the weight gradient of
     a linear layer, neo_linear_weight_grad."""
-    gy, x = f32(gy, "gy"), f32(x, "x")
+    gy = dense(gy, "gy")                # gy (K, M) defines the rows and the device
+    x = dense(x, "x", device=gy.device)
     if gy.dim() != 2 or x.dim() != 2 or gy.shape[0] != x.shape[0]:
         raise ValueError("gy (K, M) and x (K, N) must share their rows, got %s and %s" % (tuple(gy.shape), tuple(x.shape)))
     c = _ctx(gy, ctx)
@@ -646,7 +691,8 @@ class _TrainMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, lib_ctx, input_ch, nv, x_enc, cond_rows, world_feat, local_feat, *params):
         ws, bs = params[:9], params[9:]
-        pe, npts = input_ch * 21, x_enc.shape[1]
+        _floating_rows("x_enc", x_enc)
+        pe, npts = input_ch * 21, x_enc.shape[1] if x_enc.dim() > 1 else -1
         if x_enc.dim() != 3 or tuple(x_enc.shape) != (nv, npts, pe):
             raise ValueError("x_enc must be (NV, P, %d), got %s" % (pe, tuple(x_enc.shape)))
         _check_rows(nv * npts, ("cond_rows", cond_rows, 27), ("world_feat", world_feat, 128), ("local_feat", local_feat, 512))
@@ -704,6 +750,8 @@ class _TrainVanillaMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, lib_ctx, x_enc, dir_enc, *params):
         ws, bs = params[:12], params[12:]
+        _floating_rows("x_enc", x_enc)
+        _floating_rows("dir_enc", dir_enc)
         if x_enc.dim() != 3 or x_enc.shape[-1] != 63 or tuple(dir_enc.shape) != (x_enc.shape[0], 27):
             raise ValueError("x_enc must be (B, N, 63) and dir_enc (B, 27), got %s / %s" % (tuple(x_enc.shape), tuple(dir_enc.shape)))
         _check_layers("NeRFMLP layer", ws, bs,
@@ -780,7 +828,7 @@ def tp_render_train(module, rays, randomized, white_bkgd, maps, chunk=None, seed
     stream for all rays of the call, sliced per chunk: both paths see the same samples for one seed at any `chunk`
     (round 5; the first version re-seeded every chunk).  `module.density_noise` (model.py:381-384, uniform noise on the raw
     density when randomized) is drawn from streams 4..7.  All rays form ONE reference chunk unless `chunk` is given."""
-    rays_o = f32(rays["rays_o"], "rays_o")
+    rays_o = ray_rows(rays)[0]           # rays_o defines B; rays_d / viewdirs of another batch are refused before anything runs
     B = rays_o.shape[0]
     c = module._context(rays_o.device)
     n0, n1 = module.num_coarse_samples, module.num_fine_samples
@@ -807,7 +855,7 @@ def _tp_render_train_chunk(module, rays, randomized, white_bkgd, maps, draws, pr
     """One reference chunk of tp_render_train; `draws` = this chunk's rows of the call's uniform tables (None: deterministic);
     `proj` = the call's cache of projected maps (None: the local features are gathered and multiplied per row)."""
     from . import ops
-    rays_o, rays_d, viewdirs = f32(rays["rays_o"], "rays_o"), f32(rays["rays_d"], "rays_d"), f32(rays["viewdirs"], "viewdirs")
+    rays_o, rays_d, viewdirs = ray_rows(rays)        # rays_o defines B
     B = rays_o.shape[0]
     dev = rays_o.device
     c = module._context(dev)
@@ -880,7 +928,7 @@ def nerf_render_train(module, rays, randomized, white_bkgd, near, far, seed=None
     level 0 / 1 (torch.manual_seed makes the default seed repeatable).  return_samples: also return [t0 (B,n0+1), t1 (B,n0+1+n1)],
     the sample positions of the two levels (tests evaluate the oracle at them)."""
     from . import ops
-    rays_o, rays_d, viewdirs = f32(rays["rays_o"], "rays_o"), f32(rays["rays_d"], "rays_d"), f32(rays["viewdirs"], "viewdirs")
+    rays_o, rays_d, viewdirs = ray_rows(rays)        # rays_o defines B
     B = rays_o.shape[0]
     dev = rays_o.device
     c = module._context(dev)
@@ -932,7 +980,8 @@ class _PixTrainMLPPre(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, lib_ctx, nv, x_enc, cond_rows, pre, *params):
         ws, bs = params[:9], params[9:]
-        npts = x_enc.shape[1]
+        _floating_rows("x_enc", x_enc)
+        npts = x_enc.shape[1] if x_enc.dim() > 1 else -1
         if x_enc.dim() != 3 or tuple(x_enc.shape) != (nv, npts, 63):
             raise ValueError("x_enc must be (NV, P, 63), got %s" % (tuple(x_enc.shape),))
         _check_rows(nv * npts, ("cond_rows", cond_rows, 27), ("pre", pre, 128))
@@ -982,6 +1031,12 @@ def pixel_mlp_projected(mlp, x_enc, cond_rows, pre, nv, ctx=None):
     of pts_linears.0 (W0 [:, 63:575]; the 512-wide product is formed per texel by project_pixel_latent) -> raw_rgb (P,3),
     raw_sigma (P,1).  The view means, the concatenation [bottleneck | cond] (two products into one sum) and the ReLU of
     the first layer are torch elementwise ops between the GEMMs."""
+    _floating_rows("x_enc", x_enc)
+    if x_enc.dim() != 3 or tuple(x_enc.shape) != (nv, x_enc.shape[1], 63):
+        raise ValueError("x_enc must be (NV, P, 63), got %s" % (tuple(x_enc.shape),))
+    _check_rows(nv * x_enc.shape[1], ("cond_rows", cond_rows, 27), ("pre", pre, 128))
+    x_enc = dense(x_enc, "x_enc")
+    cond_rows, pre = dense(cond_rows, "cond_rows", device=x_enc.device), dense(pre, "pre", device=x_enc.device)
     P = x_enc.shape[1]
     xe = x_enc.reshape(-1, x_enc.shape[-1])
     L = mlp.pts_linears
@@ -1014,7 +1069,7 @@ def pix_render_train(module, rays, randomized, white_bkgd, near, far, latent, se
     nerf_render_train: 0 level-0 jitter, 2 level-1 quantiles, 4 / 6 density noise.  The direction encodings are tiled with the
     reference's (1, N, 1) pattern on a (NV, B, 27) tensor (:219-222: row (v, j) carries ray j mod B)."""
     from . import ops
-    rays_o, rays_d, viewdirs = f32(rays["rays_o"], "rays_o"), f32(rays["rays_d"], "rays_d"), f32(rays["viewdirs"], "viewdirs")
+    rays_o, rays_d, viewdirs = ray_rows(rays)        # rays_o defines B
     B = rays_o.shape[0]
     dev = rays_o.device
     c = module._context(dev)
@@ -1072,24 +1127,33 @@ _EPS32 = float(torch.finfo(torch.float32).eps)
 
 def mip_resample_u(s_prev, w_prev, n, near, far, dilate, dilation, anneal, u, jitter=None, ctx=None):
     """One proposal-resampling step with the caller's quantile table u (n) and, when given, one jitter per ray (R,)
-    (neo_mip_resample_u; helper.py:343-396).  Returns sdist, tdist (R, n+1); no gradients (stop_level_grad)."""
-    s_prev, w_prev, u = f32(s_prev, "s_prev"), f32(w_prev, "w_prev"), f32(u, "u")
-    c = _ctx(s_prev, ctx)
+    (neo_mip_resample_u; helper.py:343-396).  w_prev (R,n_prev) defines R and n_prev, s_prev (R,n_prev+1), u (n,) or (1,n),
+    jitter (R,) or (R,1); any float dtype, any strides.  Returns sdist, tdist (R, n+1); no gradients (stop_level_grad)."""
+    w_prev = dense(w_prev, "w_prev", (None, None))
     R, n_prev = w_prev.shape
+    dev = w_prev.device
+    s_prev, u = dense(s_prev, "s_prev", (R, n_prev + 1), device=dev), dense(u, "u", [(n,), (1, n)], device=dev)
+    c = _ctx(s_prev, ctx)
     sdist = torch.empty(R, n + 1, device=s_prev.device)
     tdist = torch.empty(R, n + 1, device=s_prev.device)
-    jit = f32(jitter, "jitter").reshape(-1) if jitter is not None else None
+    jit = dense(jitter, "jitter", [(R,), (R, 1)], device=dev).reshape(-1) if jitter is not None else None
     _lib.check(c.lib.neo_mip_resample_u(c.handle, ptr(s_prev), ptr(w_prev), R, n_prev, int(bool(dilate)), float(dilation),
                                         float(anneal), n, ptr(u), ptr(jit), float(near), float(far), ptr(sdist), ptr(tdist), c.stream()))
     return sdist, tdist
 
 
 def mip_encode(rays_o, rays_d, radii, tdist, pos_basis_t, ctx=None):
-    """(R n, 504) integrated positional encodings of the intervals of tdist (R, n+1) (neo_mip_encode; helper.py:33-88, 278-334)."""
-    rays_o, rays_d, radii, tdist = f32(rays_o, "rays_o"), f32(rays_d, "rays_d"), f32(radii, "radii"), f32(tdist, "tdist")
-    basis = f32(pos_basis_t, "pos_basis_t")
-    c = _ctx(tdist, ctx)
+    """(R n, 504) integrated positional encodings of the intervals of tdist (R, n+1) (neo_mip_encode; helper.py:33-88, 278-334).
+    tdist defines R and n; rays_o, rays_d (R,3), radii (R,1), (R,) or (1,R), pos_basis_t (3,21); any float dtype, any strides."""
+    tdist = dense(tdist, "tdist", (None, None))
     R, n1 = tdist.shape
+    dev = tdist.device
+    if n1 < 2:
+        raise ValueError("tdist must have shape (R, n + 1) with n >= 1, got %s" % (tuple(tdist.shape),))
+    rays_o, rays_d = dense(rays_o, "rays_o", (R, 3), device=dev), dense(rays_d, "rays_d", (R, 3), device=dev)
+    radii = dense(radii, "radii", [(R, 1), (R,), (1, R)], device=dev)
+    basis = dense(pos_basis_t, "pos_basis_t", (3, 21), device=dev)
+    c = _ctx(tdist, ctx)
     out = torch.empty(R * (n1 - 1), 504, device=tdist.device)
     _lib.check(c.lib.neo_mip_encode(c.handle, ptr(rays_o), ptr(rays_d), ptr(radii), ptr(tdist), ptr(basis), R, n1 - 1, ptr(out), c.stream()))
     return out
@@ -1101,10 +1165,15 @@ class _MipComposite(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx_, rgb, density, tdist, rays_d, bg, lib_ctx):
-        rgbdens = torch.cat([f32(rgb, "rgb"), f32(density, "density")[..., None]], dim=-1).contiguous()
-        tdist, rays_d = f32(tdist, "tdist"), f32(rays_d, "rays_d")
-        c = _ctx(tdist, lib_ctx)
+        tdist = dense(tdist, "tdist", (None, None))     # tdist (R,n+1) defines R, n and the device
         R, n1 = tdist.shape
+        if n1 < 2:
+            raise ValueError("tdist must have shape (R, n + 1) with n >= 1, got %s" % (tuple(tdist.shape),))
+        dev = tdist.device
+        rgbdens = torch.cat([dense(rgb, "rgb", (R, n1 - 1, 3), device=dev), dense(density, "density", (R, n1 - 1), device=dev)[..., None]],
+                            dim=-1).contiguous()
+        rays_d = dense(rays_d, "rays_d", (R, 3), device=dev)
+        c = _ctx(tdist, lib_ctx)
         w = torch.empty(R, n1 - 1, device=tdist.device)
         out = torch.empty(R, 3, device=tdist.device)
         _lib.check(c.lib.neo_mip_composite(c.handle, ptr(rgbdens), ptr(tdist), ptr(rays_d), R, n1 - 1, float(bg), ptr(w), ptr(out), c.stream()))
@@ -1136,6 +1205,11 @@ def mip_mlp(mlp, x0, d_enc, n, ctx=None):
     one sum instead of the concatenation), density = softplus(raw - 1); with the rgb branch: bottleneck, view layer on
     [bottleneck | dir_enc] (the direction term once per RAY, broadcast over its n intervals), rgb = sigmoid(.) (1 + 2 pad) - pad.
     d_enc (R, 27).  Returns density (R, n), rgb (R, n, 3) (zeros without the branch)."""
+    _mip_rows(x0, d_enc, n, not mlp.disable_rgb)
+    # converted ONCE: x0 feeds the first layer and every skip, and the gradients of those uses are then summed in fp32 whatever the
+    # caller's dtype (autograd would sum them in the caller's)
+    x0 = dense(x0, "x0")
+    d_enc = dense(d_enc, "d_enc", device=x0.device) if not mlp.disable_rgb else d_enc
     W = mlp.netwidth
     h = x0
     for i, layer in enumerate(mlp.pts_linear):
@@ -1157,6 +1231,19 @@ def mip_mlp(mlp, x0, d_enc, n, ctx=None):
     return density, rgb * (1 + 2 * 0.001) - 0.001
 
 
+def _mip_rows(x0, d_enc, n, rgb):
+    """The row contract of the Mip-NeRF 360 MLP: x0 (R n, 504) defines R, d_enc (R, 27) with the colour branch.  Returns R."""
+    _floating_rows("x0", x0)
+    if x0.dim() != 2 or x0.shape[1] != 504 or x0.shape[0] % n:
+        raise ValueError("x0 must be (R n, 504) with n = %d, got %s" % (n, tuple(x0.shape)))
+    R = x0.shape[0] // n
+    if rgb:
+        _floating_rows("d_enc", d_enc)
+        if tuple(d_enc.shape) != (R, 27):
+            raise ValueError("d_enc must be (R, 27) = (%d, 27), got %s" % (R, tuple(d_enc.shape)))
+    return R
+
+
 class _MipTrainMLP(torch.autograd.Function):
     """MipNeRF360MLP.forward under autograd as ONE native chain each way (neo_mip_mlp_train_forward / _backward, round 6): trunk,
     skip layer, heads and both activations inside the library; the backward returns every parameter gradient.  x0 / d_enc are data
@@ -1166,12 +1253,8 @@ class _MipTrainMLP(torch.autograd.Function):
     def forward(ctx_, lib_ctx, width, depth, rgb, n, x0, d_enc, *params):
         nl = depth + (4 if rgb else 1)
         ws, bs = params[:nl], params[nl:]
+        R = _mip_rows(x0, d_enc, n, rgb)
         rows = x0.shape[0]
-        if x0.dim() != 2 or x0.shape[1] != 504 or rows % n:
-            raise ValueError("x0 must be (R n, 504) with n = %d, got %s" % (n, tuple(x0.shape)))
-        R = rows // n
-        if rgb and tuple(d_enc.shape) != (R, 27):
-            raise ValueError("d_enc must be (R, 27) = (%d, 27), got %s" % (R, tuple(d_enc.shape)))
         want = [(width, 504)] + [(width, width + 504 if (i - 1) % 4 == 0 and i - 1 > 0 else width) for i in range(1, depth)] + [(1, width)]
         if rgb:
             want += [(256, width), (128, 283), (3, 128)]
@@ -1223,8 +1306,8 @@ def mip_render_train(module, batch, train_frac, randomized, near, far, seed=None
     `weights`, which the interlevel / distortion losses of training_step read: mip_interlevel_loss / mip_distortion_loss /
     mip_training_loss below).  sdist is detached (stop_level_grad)."""
     from . import ops
-    rays_o, rays_d = f32(batch["rays_o"], "rays_o"), f32(batch["rays_d"], "rays_d")
-    viewdirs, radii = f32(batch["viewdirs"], "viewdirs"), f32(batch["radii"], "radii")
+    rays_o, rays_d, viewdirs = ray_rows(batch)       # rays_o defines B
+    radii = dense(batch["radii"], "radii", radii_shapes(rays_o.shape[0]), device=rays_o.device)
     dev = rays_o.device
     c = module._context(dev)
     B = rays_o.shape[0]
@@ -1278,12 +1361,16 @@ def _no_edge_grad(x, name, what):
 class _LossfunOuter(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, t, w, t_env, w_env, lib_ctx):
+        w = dense(w, "w")                               # w defines the rays and the device
+        t, t_env, w_env = (dense(x, k, device=w.device) for k, x in (("t", t), ("t_env", t_env), ("w_env", w_env)))
+        if min(t.dim(), w.dim(), t_env.dim(), w_env.dim()) < 1:
+            raise ValueError("t, w, t_env and w_env must have shape (..., n), got a scalar")
         N, Ne = w.shape[-1], w_env.shape[-1]
         if t.shape[-1] != N + 1 or t_env.shape[-1] != Ne + 1:
             raise ValueError("t / t_env must hold one more entry per row than w / w_env, got %s %s %s %s"
                              % (tuple(t.shape), tuple(w.shape), tuple(t_env.shape), tuple(w_env.shape)))
-        t2, w2 = f32(t, "t").reshape(-1, N + 1), f32(w, "w").reshape(-1, N)
-        te2, we2 = f32(t_env, "t_env").reshape(-1, Ne + 1), f32(w_env, "w_env").reshape(-1, Ne)
+        t2, w2 = t.reshape(-1, N + 1), w.reshape(-1, N)
+        te2, we2 = t_env.reshape(-1, Ne + 1), w_env.reshape(-1, Ne)
         R = w2.shape[0]
         if not (t2.shape[0] == te2.shape[0] == we2.shape[0] == R):
             raise ValueError("t, w, t_env and w_env must hold the same rays")
@@ -1327,10 +1414,14 @@ def lossfun_outer(t, w, t_env, w_env, ctx=None):
 class _LossfunDistortion(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, t, w, lib_ctx):
+        w = dense(w, "w")                               # w defines the rays and the device
+        t = dense(t, "t", device=w.device)
+        if t.dim() < 1 or w.dim() < 1:
+            raise ValueError("t must have shape (..., N + 1) and w (..., N), got %s %s" % (tuple(t.shape), tuple(w.shape)))
         N = w.shape[-1]
         if t.shape[-1] != N + 1:
             raise ValueError("t must hold one more entry per row than w, got %s %s" % (tuple(t.shape), tuple(w.shape)))
-        t2, w2 = f32(t, "t").reshape(-1, N + 1), f32(w, "w").reshape(-1, N)
+        t2, w2 = t.reshape(-1, N + 1), w.reshape(-1, N)
         R = w2.shape[0]
         if t2.shape[0] != R:
             raise ValueError("t and w must hold the same rays")
@@ -1362,10 +1453,14 @@ def lossfun_distortion(t, w, ctx=None):
 class _MipExpectedDistance(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, edges, w, near, far, lib_ctx):
+        w = dense(w, "w")                               # w defines the rays and the device
+        edges = dense(edges, "edges", device=w.device)
+        if edges.dim() < 1 or w.dim() < 1:
+            raise ValueError("edges must have shape (..., n + 1) and w (..., n), got %s %s" % (tuple(edges.shape), tuple(w.shape)))
         n = w.shape[-1]
         if edges.shape[-1] != n + 1 or edges.shape[:-1] != w.shape[:-1]:
             raise ValueError("edges must hold one more entry per row than w, got %s %s" % (tuple(edges.shape), tuple(w.shape)))
-        e2, w2 = f32(edges, "edges").reshape(-1, n + 1), f32(w, "w").reshape(-1, n)
+        e2, w2 = edges.reshape(-1, n + 1), w.reshape(-1, n)
         R = w2.shape[0]
         c = _ctx(w2, lib_ctx)
         acc, mean = torch.empty(R, device=w2.device), torch.empty(R, device=w2.device)
