@@ -219,6 +219,91 @@ int neo_vanilla_render(neo_ctx* ctx, const float* rays_o, const float* viewdirs,
                        int n_fine, int white_bkgd, float* rgb0, float* acc0, float* depth0,
                        float* rgb1, float* acc1, float* depth1, void* stream);
 
+/* VANILLA MARCHING FRAME: empty-space skipping and early ray termination for the vanilla renderer.  A vanilla NeRF is fitted to ONE
+ * scene, its density depends on the position alone and it has no outside-sphere half, so a grid built once from its own density
+ * stays valid for every later frame and both savings apply to the whole frame.  The pieces are those of the NeO-360 frame further
+ * down in this header (OCCUPANCY GRID, KEEP RULE, STOP RULE, ACCELERATED FRAME), restated for a grid over a box and for composite
+ * mode 0.
+ *
+ * COMPACT EVALUATOR LAUNCH.  neo_vanilla_mlp_compact is neo_vanilla_mlp on single points whose number lives on the device: rays_o,
+ * dirs (cap,3), t (cap) and out (cap,4) are allocated for `cap` rows, the host's bound, and min(*count_dev, cap) of them are live
+ * (count_dev [device]: one int; 0 is a valid launch).  Row k is the point rays_o[k] + t[k] * dirs[k] seen along dirs[k].  Its out row
+ * is bitwise what neo_vanilla_mlp gives the same point, whatever its neighbours and whichever kernel variant runs; the variant is
+ * chosen from the process's settings, never from the count.  A row at or behind the count is neither read nor written and takes no
+ * part in the fp16 range check; a workgroup whose first row is at or behind the count leaves before its first barrier. */
+int neo_vanilla_mlp_compact(neo_ctx* ctx, int slot, const float* rays_o, const float* dirs, const float* t, int cap,
+                            const int* count_dev, float* out, void* stream);
+
+/* BOX GRID.  G^3 cells over a caller-given box [lo_a, hi_a) per axis (lo, hi [host]: 3 floats each, finite, lo_a < hi_a); G and the
+ * bit layout are the OCCUPANCY GRID's.  scale_a = (float)G / (hi_a - lo_a) is formed ONCE, on the host, in fp32 (one subtraction,
+ * one division).  The cell of a coordinate x_a, in fp32 on the device: c_a = floorf((x_a - lo_a) * scale_a) - one subtraction, one
+ * multiply.  A point is OUTSIDE iff some c_a < 0 or c_a >= G (compared as floats; an overflow to infinity is outside) - the
+ * unit-cube rule clamps instead, which is not enough here, because vanilla samples run to `far` whatever the box is.
+ * BOX KEEP RULE.  Sample j of ray r, at x = rays_o[r] + t[r][j] * viewdirs[r] (one fp32 multiply and one fp32 add per coordinate,
+ * the evaluator's own expression), is KEPT iff a coordinate of x is not finite (written as the negation of |x| < inf, so that a NaN
+ * survives to the caller), or there is no grid, or x is outside and clip == 0, or x is inside and the bit of (c_0, c_1, c_2) is set.
+ * With clip != 0 a point outside the box is skipped.
+ *
+ * neo_vanilla_set_occupancy copies `bits` [device, G^3 / 8 bytes] into context-owned memory and records the box and `clip`; it is
+ * ordered behind every earlier call of the context.  bits == NULL removes the grid.  The grid belongs to the uploaded weights,
+ * which the library cannot check: install a new one after an upload.  neo_vanilla_set_march_window: rays per window of
+ * neo_vanilla_render_marching, 1 .. 65536, 0 = the default (8192); a window bounds the extra workspace at 68 bytes per (ray,
+ * sample) of one window and segment.  Results do not depend on it. */
+int neo_vanilla_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, const float* lo, const float* hi, int clip, void* stream);
+int neo_vanilla_set_march_window(neo_ctx* ctx, int rays);
+
+/* The BOX KEEP RULE on caller rows: rays_o, dirs (R,3), t (R,N) -> keep (R,N) uint8 0 / 1.  bits [device] may be NULL (no grid: all
+ * ones; G, lo, hi and clip are then not read).  R == 0 is a valid call.  Touches no context-owned memory. */
+int neo_vanilla_occupancy_keep(neo_ctx* ctx, const uint32_t* bits, int G, const float* lo, const float* hi, int clip,
+                               const float* rays_o, const float* dirs, const float* t, int R, int N, uint8_t* keep, void* stream);
+
+/* neo_occupancy_from_sigma (below) without its last step, the unit-sphere clip: the lattice is the box's, and a box has no sphere. */
+int neo_occupancy_from_sigma_box(neo_ctx* ctx, const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits,
+                                 void* stream);
+
+/* MODE-0 STOP RULE: the STOP RULE (below) restated for neo_composite mode 0.  delta_i = t_{i+1} - t_i, the last one 1e10, each
+ * times |rays_d| (the norm of rays_d, not of viewdirs); alpha = alpha(sigma * delta); keep = (1 - alpha) + 1e-10f; the 64-lane
+ * inclusive product scan in fp64; carry *= the round's last lane.  These are mode 0's own lines, so at a boundary b that is a
+ * multiple of 64, (float)carry_b is the transmittance that the composite assigns to sample b, bit for bit.  Segment 0 is always
+ * marched.  Segment k >= 1 is marched iff no earlier boundary b had (float)carry_b < eps - a negation, so a NaN marches on.
+ * `segment` is a positive multiple of 64, eps lies in [0, 1).  stop (R) int32 = the leading samples marched: N or a boundary;
+ * trans (R) = (float)carry at the stop.  R == 0 is a valid call.  Touches no context-owned memory. */
+int neo_vanilla_termination_stops(neo_ctx* ctx, const float* rgbsigma, const float* t, const float* rays_d, int R, int N, float eps,
+                                  int segment, int* stop, float* trans, void* stream);
+
+/* neo_vanilla_render in which a sample is evaluated iff the BOX KEEP RULE of the installed grid keeps it AND it lies in front of the
+ * ray's stop.  A sample that is not evaluated has the row (0, 0, 0, 0), to which composite mode 0 gives weight exactly 0 and an
+ * unchanged product (alpha(0 * delta) = 0, also for the last delta 1e10, and 1.0f + 1e-10f == 1.0f).  An evaluated sample goes through
+ * the compact evaluator launch and is bitwise neo_vanilla_render's for its position.  The composites, the resampling (on the resulting
+ * level-0 weights) and white_bkgd are neo_vanilla_render's.
+ * LEVELS.  Level 1 follows the MODE-0 STOP RULE, applied to its rows in which the samples that are not kept are zero.  Level 0 follows
+ * it only with coarse != 0, which moves the level-1 positions: NO bound is claimed for that mode.  A level that does not follow the rule
+ * has stop = N; with no grid either it is the dense launch of neo_vanilla_render.  eps == 0 stops nothing.  use_grid == 0 ignores an
+ * installed grid.  Without a grid (or with every cell set, or with a box that holds no sample and clip == 0) at eps == 0 the six
+ * outputs are bitwise neo_vanilla_render's.
+ * BOUND (coarse == 0, level 1), against the same call at eps == 0 with the same grid.  Level 0, and therefore the level-1 positions and
+ * the keep masks, are identical in the two calls; a ray that never stops is bitwise equal.  Let a ray stop at b with L = (float)carry_b
+ * < eps, the `trans` of neo_vanilla_termination_stops, and let F >= 0 be its final transmittance in the other call.  With T_{i+1} =
+ * T_i (1 - alpha_i + 1e-10), a weight is w_i = alpha_i T_i = T_i - T_{i+1} + 1e-10 T_i, so the skipped weights sum to S = L - F +
+ * 1e-10 sum T_i <= (1 + 1024e-10) L.  Colours lie in (-0.001, 1.001): without white_bkgd the change is -sum_skipped w_i c_i, at
+ * most 1.001 S; with it every sample contributes w_i (c_i - 1) instead - the white term turns c into 1 - c - and |c_i - 1| < 1.001
+ * again.  Either way |rgb change| < 1.0011 L per channel in real arithmetic, the same constant as for the NeO-360 rule; the asserted
+ * 1.003 L leaves 0.0019 L for the fp32 rounding of the two sums being compared.  Depth: positions are <= far, so |depth change| <=
+ * far S <= 1.0000002 far L, asserted as 1.001 far L.
+ * Per window of rays and per segment: compact the alive rays on their transmittance, classify and compact their samples of the
+ * segment, one compact evaluator launch, scatter into zero-filled rows, advance the product.  No call synchronises the device; the
+ * only atomic is the range guard's flag word.
+ * samples0 / samples1 (may be NULL, and any pointer in them): the level's positions t (level 0: ONE row of N_0, shared by all rays;
+ * level 1: (R,N_1)), weights w (R,N), keep (R,N) uint8 - the BOX KEEP RULE on the WHOLE row, behind the stop as well, all ones
+ * without a grid - stop (R) int32 and rows (R,N,4).  The evaluated set is keep & (j < stop).  kept (may be NULL): int64[2] on the
+ * device, the evaluated samples per level; nothing is read back. */
+typedef struct { float* t; float* w; uint8_t* keep; int* stop; float* rows; } neo_vanilla_march_samples;
+int neo_vanilla_render_marching(neo_ctx* ctx, const float* rays_o, const float* viewdirs, const float* rays_d, int R, float near,
+                                float far, int n_coarse, int n_fine, int white_bkgd, float eps, int segment, int coarse, int use_grid,
+                                float* rgb0, float* acc0, float* depth0, float* rgb1, float* acc1, float* depth1,
+                                const neo_vanilla_march_samples* samples0, const neo_vanilla_march_samples* samples1, long long* kept,
+                                void* stream);
+
 /* ---- NeO-360 decoder (models/neo360/model.py NeRF_TP) ---------------------- */
 /* Upload one NeRFPPMLP (neo360/model.py:37-108).  slot 0..3 = fg_coarse,
  * fg_fine, bg_coarse, bg_fine.  input_ch = 3 (fg) or 4 (bg).  weights/biases

@@ -70,6 +70,10 @@ class TpMarchSamples(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("fg_t", "fg_w", "bg_s", "stop", "fg_keep", "fg_rows", "bg_stop", "bg_value", "bg_rows")]
 
 
+class VanillaMarchSamples(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("t", "w", "keep", "stop", "rows")]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares
 SIGNATURES = {
     "neo_abi_version": (_i, []),
@@ -100,6 +104,14 @@ SIGNATURES = {
     "neo_vanilla_upload_mlp": (_i, [_vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_vanilla_mlp": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "neo_vanilla_render": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "neo_vanilla_mlp_compact": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "neo_vanilla_set_occupancy": (_i, [_vp, _vp, _i, c_float_p, c_float_p, _i, _vp]),
+    "neo_vanilla_set_march_window": (_i, [_vp, _i]),
+    "neo_vanilla_occupancy_keep": (_i, [_vp, _vp, _i, c_float_p, c_float_p, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "neo_occupancy_from_sigma_box": (_i, [_vp, _vp, _i, _i, _f, _i, _vp, _vp]),
+    "neo_vanilla_termination_stops": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "neo_vanilla_render_marching": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         ctypes.POINTER(VanillaMarchSamples), ctypes.POINTER(VanillaMarchSamples), _vp, _vp]),
     "neo_tp_upload_mlp": (_i, [_vp, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_tp_set_scene": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _f, _vp]),
     "neo_tp_set_preproject": (_i, [_vp, _i]),

@@ -35,28 +35,20 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_acc_keep(const float* __restrict_
                                                         const uint32_t* __restrict__ bits, int G, uint8_t* __restrict__ keep,
                                                         int* __restrict__ totals) {
     __shared__ int s_seg[OCC_SEGS];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int cand = *alive * len;      // at most rays x len, which the driver holds below 2^31 / 3
+    bool k[OCC_ROUNDS];
 #pragma unroll
     for (int it = 0; it < OCC_ROUNDS; ++it) {
         const int p = blockIdx.x * OCC_POINTS + it * OCC_BLOCK + threadIdx.x;
-        bool k = false;
+        k[it] = false;
         if (p < cand) {
             const int kk = p / len, j = b0 + (p - kk * len);
             const int ray = r0 + map[kk];
-            k = occ_keep_point(bits, G, rays_o + (long)ray * 3, rays_d + (long)ray * 3, t[(long)ray * N + j]);
-            keep[p] = k ? 1 : 0;
+            k[it] = occ_keep_point(bits, G, rays_o + (long)ray * 3, rays_d + (long)ray * 3, t[(long)ray * N + j]);
+            keep[p] = k[it] ? 1 : 0;
         }
-        const unsigned long long ballot = __ballot(k);
-        if (lane == 0) s_seg[it * 4 + wv] = __popcll(ballot);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int n = 0;
-#pragma unroll
-        for (int g = 0; g < OCC_SEGS; ++g) n += s_seg[g];
-        totals[blockIdx.x] = n;
-    }
+    occ_total(k, s_seg, totals);
 }
 
 __global__ __launch_bounds__(OCC_BLOCK) void k_acc_emit(const float* __restrict__ rays_o, const float* __restrict__ rays_d,

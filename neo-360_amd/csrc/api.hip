@@ -194,6 +194,7 @@ int neo_ctx_destroy(neo_ctx* ctx) {
     ctx->pix_latent.release();
     ctx->boxes.release();
     ctx->occ_bits.release();
+    ctx->vocc_bits.release();
     ctx->enc.release();
     ctx->enc_latent.release();
     ctx->enc_axes.release();
@@ -575,6 +576,45 @@ int neo_vanilla_mlp(neo_ctx* ctx, int slot, const float* rays_o, const float* di
     if (R == 0) return NEO_OK;
     REQUIRE(rays_o && dirs && t && out, "null pointer");
     return vanilla_mlp_launch(ctx, slot, rays_o, dirs, t, t_row_stride, R, N, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C++" {      // host helpers of other translation units, not part of the C ABI
+
+// one compact evaluator launch for other translation units (vanilla_march.hip); the caller holds the ordering scope
+int neo_vanilla_eval_compact(neo_ctx* ctx, int slot, const float* rays_o, const float* dirs, const float* t, long cap,
+                             const int* count_dev, float* out, hipStream_t s) {
+    MlpSlot& sl = ctx->vanilla[slot];
+    if (!sl.ready) return fail(NEO_ERR_STATE, "vanilla MLP slot %d has no weights", slot);
+    if (ctx->precision == 1) guard_split_weights(sl, sl.wpack_h.p, neo::vanilla_wpack_h_bytes(), ctx->flags, s);
+    ctx->span_begin(s);
+    if (ctx->precision == 1) {
+        neo::VanillaMlpHDev mh{sl.wpack_h.p, sl.bias_hp.as<float>(), sl.heads.as<float>(), ctx->flags};
+        neo::launch_vanilla_mlp_h_compact(mh, rays_o, dirs, t, cap, count_dev, out, s);
+    } else {
+        neo::VanillaMlpDev m{sl.wpack.as<float>(), sl.bias.as<float>(), sl.heads.as<float>()};
+        neo::launch_vanilla_mlp_compact(m, rays_o, dirs, t, cap, count_dev, out, s);
+    }
+    ctx->span_end(s, static_cast<double>(cap), 2.0 * 593408.0);      // the bound: the live count stays on the device
+    return check_launch();
+}
+
+// one dense evaluator launch for other translation units (vanilla_march.hip)
+int neo_vanilla_eval_dense(neo_ctx* ctx, int slot, const float* rays_o, const float* dirs, const float* t, int t_row_stride, int R,
+                           int N, float* out, hipStream_t s) {
+    return vanilla_mlp_launch(ctx, slot, rays_o, dirs, t, t_row_stride, R, N, out, s);
+}
+
+}  // extern "C++"
+
+int neo_vanilla_mlp_compact(neo_ctx* ctx, int slot, const float* rays_o, const float* dirs, const float* t, int cap,
+                            const int* count_dev, float* out, void* stream) {
+    ENTER(ctx);
+    ORDERED(ctx, static_cast<hipStream_t>(stream));      // touches context-owned memory: ordered across streams
+    REQUIRE(slot == 0 || slot == 1, "slot must be 0 or 1");
+    REQUIRE(cap >= 0, "bad shape");
+    if (cap == 0) return NEO_OK;
+    REQUIRE(rays_o && dirs && t && count_dev && out, "null pointer");
+    return neo_vanilla_eval_compact(ctx, slot, rays_o, dirs, t, cap, count_dev, out, static_cast<hipStream_t>(stream));
 }
 
 int neo_vanilla_render(neo_ctx* ctx, const float* rays_o, const float* viewdirs, const float* rays_d, int R,

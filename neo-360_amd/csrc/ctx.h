@@ -228,6 +228,13 @@ struct neo_ctx {
     neo_host::DevBuf occ_bits;
     int occ_G = 0;
     int skip_window = 0;
+    // neo_vanilla_set_occupancy: the vanilla scene's grid over a caller-given box (vanilla_march.hip: BOX KEEP RULE), vocc_G = 0:
+    // none installed; vocc_scale = (float)G / (hi - lo) per axis, formed once in fp32 on the host.
+    // neo_vanilla_set_march_window: rays per window of neo_vanilla_render_marching (0: the default of vanilla_march.hip)
+    neo_host::DevBuf vocc_bits;
+    int vocc_G = 0, vocc_clip = 0;
+    float vocc_lo[3] = {0.f, 0.f, 0.f}, vocc_scale[3] = {0.f, 0.f, 0.f};
+    int vanilla_window = 0;
     // pillar stage of the scene encoder (neo_enc_*): packed weights, biases (6x512), scorer heads (3x512), workspaces
     neo_host::MlpSlot enc;
     float enc_head_b[3] = {0.f, 0.f, 0.f};

@@ -100,6 +100,14 @@ void launch_vanilla_mlp_h(const VanillaMlpHDev& m, const float* rays_o, const fl
                           int t_row_stride, int R, int N, float* out, hipStream_t s);
 void launch_vanilla_mlp(const VanillaMlpDev& m, const float* rays_o, const float* dirs, const float* t,
                         int t_row_stride, int R, int N, float* out, hipStream_t s);
+// The compact launches of the two evaluators (vanilla_march.hip): rays_o, dirs (cap,3), t (cap), out (cap,4), all allocated for
+// `cap` rows, the host's bound, of which min(*count, cap) are live (count: a device word; 0 is a valid launch).  Row k is ONE point,
+// rays_o[k] + t[k] dirs[k] seen along dirs[k]; its out row is bitwise the dense launch's for the same point.  Rows behind the count
+// are neither read nor written, and the variant (waves, tile) follows the process's setting, never the count.
+void launch_vanilla_mlp_h_compact(const VanillaMlpHDev& m, const float* rays_o, const float* dirs, const float* t, long cap,
+                                  const int* count, float* out, hipStream_t s);
+void launch_vanilla_mlp_compact(const VanillaMlpDev& m, const float* rays_o, const float* dirs, const float* t, long cap,
+                                const int* count, float* out, hipStream_t s);
 
 // mlp_tp.hip — NeO-360 decoder
 constexpr int TP_MAX_VIEWS = 8;
@@ -449,7 +457,8 @@ void launch_occ_compact(const float* rays_o, const float* rays_d, const float* v
                         hipStream_t s);
 // out_win (P,4): w.out at the point's rank where kept, zeros where skipped (w.totals as launch_occ_compact left them)
 void launch_occ_scatter(const uint8_t* keep_win, int P, const OccRows& w, float* out_win, hipStream_t s);
-// sigma (G probes)^3 activated densities -> G^3 / 32 words: any probe > threshold, dilation, unit-sphere clip
-void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s);
+// sigma (G probes)^3 activated densities -> G^3 / 32 words: any probe > threshold, dilation, unit-sphere clip (sphere = false: none)
+void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s,
+                           bool sphere = true);
 
 }  // namespace neo

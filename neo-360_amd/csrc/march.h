@@ -34,6 +34,12 @@ void launch_march_scatter(const OccRows& w, long P, float* out, hipStream_t s);
 void launch_march_advance(bool outside, const float* rgbsigma, const float* pos, long stride, const float* rays_d, const float* t_far,
                           const float* lam_c, int N, int b0, int b_end, int segment, float eps, const int* map_w, const int* count_w,
                           int n_rows, int first, double* carry, float* value, float* alive, int* stop, hipStream_t s);
+// the same kernel by composite mode: 2 and 1 are the two calls above; 0 is the vanilla renderer's rule (rays_d by row, t_far and lam_c
+// unread, stride 0 for a shared row of positions).  launch_march_advance(outside, ...) is this with mode = outside ? 2 : 1.
+void launch_march_advance_mode(int mode, const float* rgbsigma, const float* pos, long stride, const float* rays_d, const float* t_far,
+                               const float* lam_c, int N, int b0, int b_end, int segment, float eps, const int* map_w,
+                               const int* count_w, int n_rows, int first, double* carry, float* value, float* alive, int* stop,
+                               hipStream_t s);
 // dense by ray through the slot table: stop (R) / value (R) = the compact entry at slot[ray], 0 where slot[ray] < 0; either may be null
 void launch_march_by_slot(const int* stop_c, const float* value_c, const int* slot, int R, int* stop, float* value, hipStream_t s);
 // dst (R,N) = src_c row slot[ray], zeros where slot[ray] < 0

@@ -95,15 +95,18 @@ __global__ __launch_bounds__(256) void k_march_scatter(const float4* __restrict_
 // that the composite assigns to the boundary's sample, bit for bit).  After every segment: stop = its end, v = (float)carry inside,
 // lam_c (float)carry - one fp32 multiply - outside; the march over further segments (b_end beyond the first: the pure functions
 // below) goes on iff !(v < eps) - the negation, so a NaN keeps marching.  carry_io (may be null when b0 == 0 and nobody continues):
-// the row's fp64 carry.
-template <bool OUTSIDE>
+// the row's fp64 carry.  MODE is the composite's: 1 inside the sphere, 2 outside, and 0 for the vanilla renderer (vanilla_march.hip:
+// the last delta is 1e10, every delta times |rays_d|, no far and no lambda; rows are rays, and `stride` is 0 for a level whose rays
+// share one row of positions).
+template <int MODE>
 __global__ __launch_bounds__(256) void k_march_advance(const float4* __restrict__ rgbsigma, const float* __restrict__ pos, long stride,
                                                        const float* __restrict__ rays_d, const float* __restrict__ t_far,
                                                        const float* __restrict__ lam_c, int N, int b0, int b_end, int segment,
                                                        float eps, const int* __restrict__ map_w, const int* __restrict__ count_w,
                                                        int n_rows, int first, double* __restrict__ carry_io,
                                                        float* __restrict__ value, float* __restrict__ alive, int* __restrict__ stop) {
-    constexpr int mode = OUTSIDE ? 2 : 1;
+    constexpr int mode = MODE;
+    constexpr bool OUTSIDE = MODE == 2;
     const int kk = blockIdx.x * MARCH_ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (kk >= (count_w ? *count_w : n_rows)) return;
     const int row = first + (map_w ? map_w[kk] : kk);
@@ -116,7 +119,7 @@ __global__ __launch_bounds__(256) void k_march_advance(const float4* __restrict_
     } else {
         const float dx = rays_d[row * 3], dy = rays_d[row * 3 + 1], dz = rays_d[row * 3 + 2];
         dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-        far = t_far[row];
+        if constexpr (MODE == 1) far = t_far[row];
     }
     double carry = b0 > 0 ? carry_io[row] : 1.0;      // product of (1-alpha+eps) over all earlier samples
     const auto running = [&]() { return OUTSIDE ? lam * (float)carry : (float)carry; };
@@ -189,8 +192,16 @@ void launch_march_scatter(const OccRows& w, long P, float* out, hipStream_t s) {
 void launch_march_advance(bool outside, const float* rgbsigma, const float* pos, long stride, const float* rays_d, const float* t_far,
                           const float* lam_c, int N, int b0, int b_end, int segment, float eps, const int* map_w, const int* count_w,
                           int n_rows, int first, double* carry, float* value, float* alive, int* stop, hipStream_t s) {
+    launch_march_advance_mode(outside ? 2 : 1, rgbsigma, pos, stride, rays_d, t_far, lam_c, N, b0, b_end, segment, eps, map_w, count_w,
+                              n_rows, first, carry, value, alive, stop, s);
+}
+
+void launch_march_advance_mode(int mode, const float* rgbsigma, const float* pos, long stride, const float* rays_d, const float* t_far,
+                               const float* lam_c, int N, int b0, int b_end, int segment, float eps, const int* map_w,
+                               const int* count_w, int n_rows, int first, double* carry, float* value, float* alive, int* stop,
+                               hipStream_t s) {
     if (n_rows <= 0) return;
-    hipLaunchKernelGGL(outside ? k_march_advance<true> : k_march_advance<false>,
+    hipLaunchKernelGGL(mode == 2 ? k_march_advance<2> : mode == 1 ? k_march_advance<1> : k_march_advance<0>,
                        dim3((n_rows + MARCH_ROWS_PER_BLOCK - 1) / MARCH_ROWS_PER_BLOCK), dim3(256), 0, s, (const float4*)rgbsigma, pos,
                        stride, rays_d, t_far, lam_c, N, b0, b_end, segment, eps, map_w, count_w, n_rows, first, carry, value, alive, stop);
 }
@@ -212,7 +223,7 @@ namespace {
 
 // the pure function k_march_advance on caller rows (ptrs: the entry point has all of its own pointers); touches no context-owned
 // memory: no ordering scope (as neo_tp_occupancy_keep)
-int march_stops(neo_ctx* ctx, bool outside, bool ptrs, const float* rgbsigma, const float* pos, const float* rays_d, const float* t_far,
+int march_stops(neo_ctx* ctx, int mode, bool ptrs, const float* rgbsigma, const float* pos, const float* rays_d, const float* t_far,
                 const float* lam, int R, int N, float eps, int segment, int* stop, float* value, void* stream) {
     ENTER(ctx);
     REQUIRE(R >= 0 && N >= 1, "bad shape");
@@ -221,8 +232,8 @@ int march_stops(neo_ctx* ctx, bool outside, bool ptrs, const float* rgbsigma, co
     REQUIRE(segment >= 64 && segment % 64 == 0, "segment must be a positive multiple of 64");
     if (R == 0) return NEO_OK;
     REQUIRE(ptrs, "null pointer");
-    neo::launch_march_advance(outside, rgbsigma, pos, N, rays_d, t_far, lam, N, 0, N, segment, eps, nullptr, nullptr, R, 0, nullptr, value,
-                              nullptr, stop, static_cast<hipStream_t>(stream));
+    neo::launch_march_advance_mode(mode, rgbsigma, pos, N, rays_d, t_far, lam, N, 0, N, segment, eps, nullptr, nullptr, R, 0, nullptr,
+                                   value, nullptr, stop, static_cast<hipStream_t>(stream));
     return check_launch();
 }
 
@@ -232,13 +243,19 @@ extern "C" {
 
 int neo_tp_termination_stops(neo_ctx* ctx, const float* rgbsigma, const float* t, const float* rays_d, const float* t_far, int R, int N,
                              float eps, int segment, int* stop, float* trans, void* stream) {
-    return march_stops(ctx, false, rgbsigma && t && rays_d && t_far && stop && trans, rgbsigma, t, rays_d, t_far, nullptr, R, N, eps,
+    return march_stops(ctx, 1, rgbsigma && t && rays_d && t_far && stop && trans, rgbsigma, t, rays_d, t_far, nullptr, R, N, eps,
                        segment, stop, trans, stream);
+}
+
+int neo_vanilla_termination_stops(neo_ctx* ctx, const float* rgbsigma, const float* t, const float* rays_d, int R, int N, float eps,
+                                  int segment, int* stop, float* trans, void* stream) {
+    return march_stops(ctx, 0, rgbsigma && t && rays_d && stop && trans, rgbsigma, t, rays_d, nullptr, nullptr, R, N, eps, segment, stop,
+                       trans, stream);
 }
 
 int neo_tp_termination_stops_outside(neo_ctx* ctx, const float* rgbsigma, const float* s, const float* bg_lambda, int R, int N,
                                      float eps, int segment, int* stop, float* value, void* stream) {
-    return march_stops(ctx, true, rgbsigma && s && bg_lambda && stop && value, rgbsigma, s, nullptr, nullptr, bg_lambda, R, N, eps,
+    return march_stops(ctx, 2, rgbsigma && s && bg_lambda && stop && value, rgbsigma, s, nullptr, nullptr, bg_lambda, R, N, eps,
                        segment, stop, value, stream);
 }
 

@@ -177,10 +177,13 @@ __device__ __forceinline__ void put_dir(float* dsm, int p, int f, float v) {
     dsm[p * DIR_LD + ((((f >> 2) ^ (p & 7))) << 2) + (f & 3)] = v;
 }
 
+// COMPACT (the vanilla march, vanilla_march.hip): min(*count, P) live rows of a launch sized for P; a workgroup whose first row is
+// at or behind the count leaves before the first barrier, as a whole.  See k_vanilla_mlp_h.
+template <bool COMPACT>
 __global__ __launch_bounds__(256, 2) void k_vanilla_mlp(VanillaMlpDev m, const float* __restrict__ rays_o,
                                                          const float* __restrict__ dirs,
                                                          const float* __restrict__ t, int t_row_stride, long P,
-                                                         int N, float4* __restrict__ out) {
+                                                         int N, float4* __restrict__ out, const int* __restrict__ count) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* act = smem;                   // [64][256] swizzled
     float* dsm = smem + TM * ACT_LD;     // [64][32]  swizzled view-direction encoding
@@ -191,6 +194,11 @@ __global__ __launch_bounds__(256, 2) void k_vanilla_mlp(VanillaMlpDev m, const f
     L.l31 = L.lane & 31;
     L.key = L.lane & 15;
     const long tile0 = (long)blockIdx.x * TM;
+    if constexpr (COMPACT) {
+        const long n = *count;
+        P = n < P ? n : P;
+        if (tile0 >= P) return;
+    }
     const f32x4* wp = reinterpret_cast<const f32x4*>(m.wpack);
 
     // ---- encodings: wave q handles a quarter of the octaves for all 64 points ----
@@ -374,16 +382,33 @@ void launch_vanilla_pack(const float* const* weights, const float* const* biases
     hipLaunchKernelGGL(k_copy, dim3(1), dim3(256), 0, s, biases[11], 3, heads + HD_RB);
 }
 
+namespace {
+
+template <bool COMPACT>
+void vanilla_mlp_go(const VanillaMlpDev& m, const float* rays_o, const float* dirs, const float* t, int t_row_stride, long P, int N,
+                    float* out, const int* count, hipStream_t s) {
+    const size_t lds = (TM * ACT_LD + TM * DIR_LD) * sizeof(float);
+    // per-device attribute: set on every launch (a host-side table write), not once per process
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_vanilla_mlp<COMPACT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const long tiles = (P + TM - 1) / TM;
+    hipLaunchKernelGGL(k_vanilla_mlp<COMPACT>, dim3((unsigned)tiles), dim3(256), lds, s, m, rays_o, dirs, t, t_row_stride, P,
+                       N, reinterpret_cast<float4*>(out), count);
+}
+
+}  // namespace
+
 void launch_vanilla_mlp(const VanillaMlpDev& m, const float* rays_o, const float* dirs, const float* t,
                         int t_row_stride, int R, int N, float* out, hipStream_t s) {
     const long P = (long)R * N;
     if (P <= 0) return;
-    const size_t lds = (TM * ACT_LD + TM * DIR_LD) * sizeof(float);
-    // per-device attribute: set on every launch (a host-side table write), not once per process
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_vanilla_mlp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const long tiles = (P + TM - 1) / TM;
-    hipLaunchKernelGGL(k_vanilla_mlp, dim3((unsigned)tiles), dim3(256), lds, s, m, rays_o, dirs, t, t_row_stride, P,
-                       N, reinterpret_cast<float4*>(out));
+    vanilla_mlp_go<false>(m, rays_o, dirs, t, t_row_stride, P, N, out, nullptr, s);
+}
+
+// row k < min(*count, cap): the point rays_o[k] + t[k] dirs[k] seen along dirs[k] (N = 1: a row is its own ray)
+void launch_vanilla_mlp_compact(const VanillaMlpDev& m, const float* rays_o, const float* dirs, const float* t, long cap,
+                                const int* count, float* out, hipStream_t s) {
+    if (cap <= 0) return;
+    vanilla_mlp_go<true>(m, rays_o, dirs, t, 1, cap, 1, out, count, s);
 }
 
 }  // namespace neo

@@ -263,13 +263,19 @@ __device__ __forceinline__ void store_act(const f32x16 (&acc)[NTW][MTW], const H
 //    resident waves per SIMD (4), unchanged weight traffic, twice the LDS fragment reads.
 //  * MT = 4 (NW = 4): a 128-point tile, 2 N-tiles x 4 M-tiles per wave: every weight fragment feeds 24 instead of
 //    12 MFMAs (half the L2 -> L1 weight stream per point) at the price of the whole LDS (160 KB) and one wave per SIMD.
-template <int NW, int MT>
+// COMPACT (the vanilla march, vanilla_march.hip): the launch was sized for P rows, the host's bound, of which min(*count, P) are
+// live - a device word.  A workgroup whose first row is at or behind the count leaves here, before the first barrier and as a
+// whole (the count is one word, tile0 is the workgroup's); a row behind the count inside a live tile is the dense launch's tail
+// row: it reads the LAST LIVE row (so it adds nothing to the range guard that a live row does not add) and stores nothing.
+// Nothing else differs, so a row's value is the dense launch's for the same point, bit for bit.
+template <int NW, int MT, bool COMPACT = false>
 __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : MT == 4 ? 1 : 2)) void k_vanilla_mlp_h(VanillaMlpHDev m,
                                                                                              const float* __restrict__ rays_o,
                                                                                              const float* __restrict__ dirs,
                                                                                              const float* __restrict__ t,
                                                                                              int t_row_stride, long P, int N,
-                                                                                             float4* __restrict__ out) {
+                                                                                             float4* __restrict__ out,
+                                                                                             const int* __restrict__ count) {
     constexpr int TM = 32 * MT;
     constexpr int NTW = 8 / NW;                 // N-tiles per wave in the 256-wide layers
     constexpr int LP = NW * 64 / TM;            // lanes per point in the VALU heads
@@ -282,6 +288,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : MT == 4 ? 1 : 2)) void k_va
     L.init();
     const int tid = threadIdx.x;
     const long tile0 = (long)blockIdx.x * TM;
+    if constexpr (COMPACT) {
+        const long n = *count;
+        P = n < P ? n : P;
+        if (tile0 >= P) return;
+    }
     const h8* wp = reinterpret_cast<const h8*>(m.wpack);
     const int p_enc = (L.wv % PW) * 64 + L.lane, grp = L.wv / PW;      // this thread's point / octave group in the encodings
 
@@ -482,10 +493,13 @@ void launch_vanilla_pack_h(const float* const* weights, const float* const* bias
     }
 }
 
-void launch_vanilla_mlp_h(const VanillaMlpHDev& m, const float* rays_o, const float* dirs, const float* t,
-                          int t_row_stride, int R, int N, float* out, hipStream_t s) {
-    const long P = (long)R * N;
-    if (P <= 0) return;
+namespace {
+
+// The variant (waves per tile, points per tile) is the process's: the environment, read once.  It never depends on a row count, so
+// a compact launch takes the variant of the dense launch - and a point's value does not depend on the variant anyway.
+template <bool COMPACT>
+void vanilla_mlp_h_go(const VanillaMlpHDev& m, const float* rays_o, const float* dirs, const float* t, int t_row_stride, long P, int N,
+                      float* out, const int* count, hipStream_t s) {
     static int nw = 0, tm = 0;
     if (nw == 0) {
         nw = 4;   // measured: 4 waves 396 TFLOP/s, 8 waves 381 (profiles/r01_vanilla_h_variants.log)
@@ -500,11 +514,27 @@ void launch_vanilla_mlp_h(const VanillaMlpHDev& m, const float* rays_o, const fl
     auto go = [&](auto kernel, int threads) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(threads), lds, s, m, rays_o, dirs, t, t_row_stride, P, N,
-                           reinterpret_cast<float4*>(out));
+                           reinterpret_cast<float4*>(out), count);
     };
-    if (nw == 8) go(k_vanilla_mlp_h<8, 2>, 512);
-    else if (tm == 128) go(k_vanilla_mlp_h<4, 4>, 256);
-    else go(k_vanilla_mlp_h<4, 2>, 256);
+    if (nw == 8) go(k_vanilla_mlp_h<8, 2, COMPACT>, 512);
+    else if (tm == 128) go(k_vanilla_mlp_h<4, 4, COMPACT>, 256);
+    else go(k_vanilla_mlp_h<4, 2, COMPACT>, 256);
+}
+
+}  // namespace
+
+void launch_vanilla_mlp_h(const VanillaMlpHDev& m, const float* rays_o, const float* dirs, const float* t,
+                          int t_row_stride, int R, int N, float* out, hipStream_t s) {
+    const long P = (long)R * N;
+    if (P <= 0) return;
+    vanilla_mlp_h_go<false>(m, rays_o, dirs, t, t_row_stride, P, N, out, nullptr, s);
+}
+
+// row k < min(*count, cap): the point rays_o[k] + t[k] dirs[k] seen along dirs[k] (N = 1: a row is its own ray)
+void launch_vanilla_mlp_h_compact(const VanillaMlpHDev& m, const float* rays_o, const float* dirs, const float* t, long cap,
+                                  const int* count, float* out, hipStream_t s) {
+    if (cap <= 0) return;
+    vanilla_mlp_h_go<true>(m, rays_o, dirs, t, 1, cap, 1, out, count, s);
 }
 
 }  // namespace neo

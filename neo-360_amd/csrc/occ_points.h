@@ -1,6 +1,7 @@
-// What the point compactions of occupancy.hip (k_occ_keep / k_occ_emit / k_occ_scatter) and accelerate.hip (k_acc_keep / k_acc_emit)
-// share: the KEEP RULE of one point and the rank of a kept point among the kept points in front of it.  Device code, included by
-// those two files only; everything here has internal linkage.
+// What the point compactions of occupancy.hip (k_occ_keep / k_occ_emit / k_occ_scatter), accelerate.hip (k_acc_keep / k_acc_emit) and
+// vanilla_march.hip (k_vm_keep / k_vm_emit) share: the KEEP RULE of one point over the unit cube, the per-workgroup totals and the
+// rank of a kept point among the kept points in front of it.  Device code, included by those three files only; everything here has
+// internal linkage.
 #pragma once
 #include "common.h"
 
@@ -31,6 +32,24 @@ __device__ __forceinline__ bool occ_keep_point(const uint32_t* __restrict__ bits
     if (!bits) return true;
     const int lin = (occ_cell(x[0], G) * G + occ_cell(x[1], G)) * G + occ_cell(x[2], G);
     return (bits[lin >> 5] >> (lin & 31)) & 1u;
+}
+
+// The first launch of the compaction: totals[workgroup] = the kept points of this workgroup, from the keep flag of this thread's
+// point of every round (false beyond the launch's points).  s_seg: int[OCC_SEGS] of LDS.  Called by the whole workgroup.
+__device__ __forceinline__ void occ_total(const bool (&k)[OCC_ROUNDS], int* s_seg, int* __restrict__ totals) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int it = 0; it < OCC_ROUNDS; ++it) {
+        const unsigned long long ballot = __ballot(k[it]);
+        if (lane == 0) s_seg[it * 4 + wv] = __popcll(ballot);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+#pragma unroll
+        for (int g = 0; g < OCC_SEGS; ++g) n += s_seg[g];
+        totals[blockIdx.x] = n;
+    }
 }
 
 // The compact index of this thread's point of every round (k[it], valid where kept[it]) and the kept points up to and including

@@ -41,27 +41,18 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_keep(const float* __restrict_
                                                         const uint32_t* __restrict__ bits, int G, uint8_t* __restrict__ keep,
                                                         int* __restrict__ totals) {
     __shared__ int s_seg[OCC_SEGS];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    bool k[OCC_ROUNDS];
 #pragma unroll
     for (int it = 0; it < OCC_ROUNDS; ++it) {
         const int p = blockIdx.x * OCC_POINTS + it * OCC_BLOCK + threadIdx.x;
-        bool k = false;
+        k[it] = false;
         if (p < P) {
             const int r = p / N;
-            k = occ_keep_point(bits, G, rays_o + (long)r * 3, rays_d + (long)r * 3, t[p]);
-            keep[p] = k ? 1 : 0;
+            k[it] = occ_keep_point(bits, G, rays_o + (long)r * 3, rays_d + (long)r * 3, t[p]);
+            keep[p] = k[it] ? 1 : 0;
         }
-        const unsigned long long ballot = __ballot(k);
-        if (lane == 0) s_seg[it * 4 + wv] = __popcll(ballot);
     }
-    if (!totals) return;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int n = 0;
-#pragma unroll
-        for (int g = 0; g < OCC_SEGS; ++g) n += s_seg[g];
-        totals[blockIdx.x] = n;
-    }
+    if (totals) occ_total(k, s_seg, totals);
 }
 
 // One window: rays r0 .. r0 + P / N - 1 of the frame's R rays; t and keep are the window's rows.  Per kept point p = r_w N + j:
@@ -127,6 +118,8 @@ __global__ void k_occ_iota(int* __restrict__ map, int n) {
 // NaN density counts as occupied, so that it reaches the caller); occupied iff a cell within `dilate` cells of it in every axis (the 26-neighbourhood, `dilate` times) is raw-occupied;
 // and cleared when no point of it lies inside the closed unit sphere: with h = G / 2 and n_a = the distance of the cell from the
 // origin along axis a in whole cells (i - h for i >= h, h - 1 - i below), iff n_x^2 + n_y^2 + n_z^2 > h^2 - integers, no rounding.
+// SPHERE = false (neo_occupancy_from_sigma_box: a grid over a caller's box, which has no unit sphere) leaves that last step out.
+template <bool SPHERE>
 __global__ __launch_bounds__(OCC_BLOCK) void k_occ_from_sigma(const float* __restrict__ sigma, int G, int probes, float threshold,
                                                               int dilate, uint32_t* __restrict__ bits) {
     const int idx = blockIdx.x * OCC_BLOCK + threadIdx.x;         // G^3 is a multiple of 256
@@ -134,7 +127,7 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_from_sigma(const float* __res
     const int h = G / 2;
     const int nx = ix >= h ? ix - h : h - 1 - ix, ny = iy >= h ? iy - h : h - 1 - iy, nz = iz >= h ? iz - h : h - 1 - iz;
     bool occ = false;
-    if (nx * nx + ny * ny + nz * nz <= h * h) {
+    if (!SPHERE || nx * nx + ny * ny + nz * nz <= h * h) {
         const long M = (long)G * probes;
         for (int cx = max(ix - dilate, 0); cx <= min(ix + dilate, G - 1) && !occ; ++cx)
             for (int cy = max(iy - dilate, 0); cy <= min(iy + dilate, G - 1) && !occ; ++cy)
@@ -190,9 +183,10 @@ void launch_occ_scatter(const uint8_t* keep_win, int P, const OccRows& w, float*
                        (const float4*)w.out, (float4*)out_win);
 }
 
-void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s) {
+void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s,
+                           bool sphere) {
     const long cells = (long)G * G * G;
-    hipLaunchKernelGGL(k_occ_from_sigma, dim3((int)(cells / OCC_BLOCK)), dim3(OCC_BLOCK), 0, s, sigma, G, probes, threshold, dilate, bits);
+    hipLaunchKernelGGL(sphere ? k_occ_from_sigma<true> : k_occ_from_sigma<false>, dim3((int)(cells / OCC_BLOCK)), dim3(OCC_BLOCK), 0, s, sigma, G, probes, threshold, dilate, bits);
 }
 
 }  // namespace neo
@@ -243,17 +237,35 @@ int neo_tp_occupancy_keep(neo_ctx* ctx, const uint32_t* bits, int G, const float
     return check_launch();
 }
 
+}  // extern "C"
+
+namespace {
+
 // the pure function k_occ_from_sigma; touches no context-owned memory
-int neo_occupancy_from_sigma(neo_ctx* ctx, const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits,
-                             void* stream) {
+int occ_from_sigma(neo_ctx* ctx, const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, bool sphere,
+                   void* stream) {
     ENTER(ctx);
     REQUIRE(occ_resolution_ok(G), "occupancy resolution must be 8, 16 or a multiple of 32 in [32, 256]");
     REQUIRE(probes >= 1 && probes <= 4, "1 .. 4 probes per cell and axis");
     REQUIRE(dilate >= 0 && dilate <= 4, "dilation of 0 .. 4 cells");
     REQUIRE(!(threshold != threshold), "the density threshold is NaN");
     REQUIRE(sigma && bits, "null pointer");
-    neo::launch_occ_from_sigma(sigma, G, probes, threshold, dilate, bits, static_cast<hipStream_t>(stream));
+    neo::launch_occ_from_sigma(sigma, G, probes, threshold, dilate, bits, static_cast<hipStream_t>(stream), sphere);
     return check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+int neo_occupancy_from_sigma(neo_ctx* ctx, const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits,
+                             void* stream) {
+    return occ_from_sigma(ctx, sigma, G, probes, threshold, dilate, bits, true, stream);
+}
+
+int neo_occupancy_from_sigma_box(neo_ctx* ctx, const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits,
+                                 void* stream) {
+    return occ_from_sigma(ctx, sigma, G, probes, threshold, dilate, bits, false, stream);
 }
 
 }  // extern "C"
