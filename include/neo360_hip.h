@@ -304,6 +304,52 @@ int neo_vanilla_render_marching(neo_ctx* ctx, const float* rays_o, const float* 
                                 const neo_vanilla_march_samples* samples0, const neo_vanilla_march_samples* samples1, long long* kept,
                                 void* stream);
 
+/* VANILLA MARCHING TRAINING: the pieces between neo_vanilla_mlp_train_forward / _backward (further down: they work on arbitrary rows,
+ * each with its own cond) and the BOX GRID above, so that a training step evaluates - forward and backward - only the samples the
+ * grid keeps, and the grid follows the weights while they move.  No stop rule: a training ray sees its whole interval.
+ *
+ * ROW BUILDER.  neo_vanilla_train_rows: the grid as neo_vanilla_occupancy_keep takes it (bits == NULL: no grid; G, lo, hi, clip are
+ * then not read), rays_o, dirs (R,3), t (R,N), dir_enc (R,27), and `cap`, the rows index / x_enc / cond are allocated for.
+ * keep (R,N) uint8 = the BOX KEEP RULE, bitwise neo_vanilla_occupancy_keep's.  count [device]: one int = the kept samples of the
+ * whole call, NOT clamped to cap.  For k < min(count, cap), in ascending flat order: index[k] = r N + j of the k-th kept sample;
+ * x_enc[k] (63) = the encoding of x = rays_o[r] + t[r][j] * dirs[r] (one fp32 multiply, one fp32 add), bitwise what
+ * neo_pos_enc(x, 3, 0, 10) gives that point; cond[k] (27) = dir_enc[r].  Rows at or behind the count are neither read nor written.
+ * R == 0 (count = 0) and a count of 0 are valid.  Two launches (classify + per-workgroup totals, then rank + emit: the compaction of
+ * the marching frames); no atomics, nothing synchronises, and the outputs do not depend on the launch geometry.  The totals live
+ * in a grow-only workspace of the context (4 bytes per 1024 samples), so the call is ordered like every call that writes one.
+ *
+ * ACTIVATE AND SCATTER.  neo_vanilla_train_scatter: raw_rgb (K,3), raw_sigma (K), index (K) - distinct values in [0, P) - noise (P)
+ * or NULL, noise_scale -> packed (P,4): row index[k] is bitwise neo_tp_activate's row for (raw_rgb[k], raw_sigma[k],
+ * noise[index[k]]); every other row is (0, 0, 0, 0), to which composite mode 0 gives weight exactly 0 and an unchanged product (see
+ * neo_vanilla_render_marching).  An index outside [0, P) writes nothing.  neo_vanilla_train_scatter_backward gathers
+ * g_packed[index[k]] and returns g_rgb (K,3), g_sigma (K), bitwise neo_tp_activate_backward on those rows.  K is a host value in both
+ * (0 <= K <= P); K == 0 launches nothing that reads a row (the forward still zero-fills packed).
+ *
+ * PROBE POINTS.  neo_vanilla_grid_probes: pts (G^3,3) in the grid's [ix][iy][iz] order, ONE point per cell of the BOX GRID over
+ * [lo, hi).  Per axis a, with w_a = (hi_a - lo_a) / (float)G formed once on the host in fp32: x_a = lo_a + ((float)c_a + u_a) * w_a
+ * (one add, one multiply, one add in fp32), u_a in [0, 1) = the value neo_rand_uniform gives key `seed` at row = the cell's linear
+ * index, col = `step`, stream_id = 8 + a (streams 0..7 belong to the samplers; the Philox counter is (cell, step, 8 + a, 0)).
+ * CONTRACT: the point of cell (c_0, c_1, c_2) lies in that cell under the BOX GRID's own fp32 expression floorf((x_a - lo_a) *
+ * scale_a).  A candidate x_a that rounding pushed over a face - its own cell expression is not c_a - is PULLED BACK to the centre
+ * of that axis, lo_a + ((float)c_a + 0.5f) * w_a; the other two coordinates stay.  So that the centre itself is inside, a box whose
+ * cell is thinner than 64 ulp of its largest coordinate (w_a * 2^17 < max(|lo_a|, |hi_a|)) is refused.  The same (seed, step)
+ * gives the same bits.
+ *
+ * RUNNING DENSITY.  neo_vanilla_density_update: density (G^3) in place = max(decay * density, max(sigma0, sigma1)) per cell, sigma1
+ * may be NULL; decay in [0, 1]; a NaN on either side of a max gives NaN, which neo_occupancy_from_sigma_box(density, G, probes = 1,
+ * threshold, dilate, bits) - the one threshold kernel - treats as occupied. */
+int neo_vanilla_train_rows(neo_ctx* ctx, const uint32_t* bits, int G, const float* lo, const float* hi, int clip, const float* rays_o,
+                           const float* dirs, const float* t, const float* dir_enc, int R, int N, int cap, uint8_t* keep, int* count,
+                           int* index, float* x_enc, float* cond, void* stream);
+int neo_vanilla_train_scatter(neo_ctx* ctx, const float* raw_rgb, const float* raw_sigma, const int* index, long K, const float* noise,
+                              float noise_scale, long P, float* packed, void* stream);
+int neo_vanilla_train_scatter_backward(neo_ctx* ctx, const float* raw_rgb, const float* raw_sigma, const int* index, long K,
+                                       const float* noise, float noise_scale, long P, const float* g_packed, float* g_rgb,
+                                       float* g_sigma, void* stream);
+int neo_vanilla_grid_probes(neo_ctx* ctx, int G, const float* lo, const float* hi, uint64_t seed, uint32_t step, float* pts,
+                            void* stream);
+int neo_vanilla_density_update(neo_ctx* ctx, float* density, const float* sigma0, const float* sigma1, int G, float decay, void* stream);
+
 /* ---- NeO-360 decoder (models/neo360/model.py NeRF_TP) ---------------------- */
 /* Upload one NeRFPPMLP (neo360/model.py:37-108).  slot 0..3 = fg_coarse,
  * fg_fine, bg_coarse, bg_fine.  input_ch = 3 (fg) or 4 (bg).  weights/biases

@@ -112,6 +112,12 @@ SIGNATURES = {
     "neo_vanilla_termination_stops": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
     "neo_vanilla_render_marching": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                          ctypes.POINTER(VanillaMarchSamples), ctypes.POINTER(VanillaMarchSamples), _vp, _vp]),
+    "neo_vanilla_train_rows": (_i, [_vp, _vp, _i, c_float_p, c_float_p, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "neo_vanilla_train_scatter": (_i, [_vp, _vp, _vp, _vp, ctypes.c_long, _vp, _f, ctypes.c_long, _vp, _vp]),
+    "neo_vanilla_train_scatter_backward": (_i, [_vp, _vp, _vp, _vp, ctypes.c_long, _vp, _f, ctypes.c_long, _vp, _vp, _vp, _vp]),
+    "neo_vanilla_grid_probes": (_i, [_vp, _i, c_float_p, c_float_p, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
+    "neo_vanilla_density_update": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp]),
     "neo_tp_upload_mlp": (_i, [_vp, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "neo_tp_set_scene": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _f, _vp]),
     "neo_tp_set_preproject": (_i, [_vp, _i]),

@@ -49,6 +49,16 @@ __device__ __forceinline__ float colour_act(float raw) {
     return s * 1.002f - 0.001f;
 }
 
+// The backward of the two, as neo_tp_activate_backward evaluates them: g x d colour_act / d raw = g (1.002 s (1 - s)), and
+// g x d density_act / d raw at x = raw - 1 ALREADY formed by the caller (torch.nn.Softplus: beyond the threshold 20 the derivative is 1).
+__device__ __forceinline__ float colour_act_grad(float raw, float g) {
+    const float sg = 1.0f / (1.0f + expf(-raw));
+    return g * (1.002f * sg * (1.0f - sg));
+}
+__device__ __forceinline__ float density_act_grad(float x, float g) {
+    return g * (x > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-x)));
+}
+
 // torch.sigmoid (PixelNeRF baseline's rgb activation, vanilla_nerf/model_pixel.py:165, :231)
 __device__ __forceinline__ float sigmoid_act(float raw) { return 1.0f / (1.0f + expf(-raw)); }
 
@@ -111,6 +121,25 @@ __device__ __forceinline__ float sin_cw(float x) {
     sincos_poly(r, sn, cs);
     const float res = (q & 1) ? cs : sn;
     return (q & 2) ? -res : res;
+}
+
+// Feature f of neo_pos_enc's row [x | sin(x 2^k) k-major | sin(x 2^k + pi/2) k-major] of a C-d point whose coordinate c is
+// coord(c), L = max_deg - min_deg (neo360/helper.py:121-125): the per-feature expression of k_pos_enc, shared with the training
+// row builder (which reads its point from LDS).
+template <class Coord>
+__device__ __forceinline__ float pos_enc_feature(Coord coord, int C, int min_deg, int L, int f) {
+    float v;
+    if (f < C) {
+        v = coord(f);
+    } else {
+        const int g = f - C;
+        const bool shifted = g >= L * C;
+        const int h = shifted ? g - L * C : g;
+        const int k = min_deg + h / C, c = h % C;
+        const float a = ldexpf(coord(c), k);
+        v = shifted ? sin_cw(a + HALF_PI_F32) : sin_cw(a);
+    }
+    return v;
 }
 
 // The reference's feature PAIR of one encoding argument a (neo360/helper.py:123-124): sin(a) and sin(fl32(a + fl32(pi/2))),

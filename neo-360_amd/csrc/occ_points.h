@@ -1,8 +1,10 @@
 // What the point compactions of occupancy.hip (k_occ_keep / k_occ_emit / k_occ_scatter), accelerate.hip (k_acc_keep / k_acc_emit) and
 // vanilla_march.hip (k_vm_keep / k_vm_emit) share: the KEEP RULE of one point over the unit cube, the per-workgroup totals and the
-// rank of a kept point among the kept points in front of it.  Device code, included by those three files only; everything here has
-// internal linkage.
+// rank of a kept point among the kept points in front of it - and, for the two vanilla files (vanilla_march.hip and the training row
+// builder of vanilla_train_march.hip), the BOX GRID's cell rule.  Included by those files only; everything here has internal linkage.
 #pragma once
+#include <cmath>
+
 #include "common.h"
 
 namespace neo {
@@ -32,6 +34,46 @@ __device__ __forceinline__ bool occ_keep_point(const uint32_t* __restrict__ bits
     if (!bits) return true;
     const int lin = (occ_cell(x[0], G) * G + occ_cell(x[1], G)) * G + occ_cell(x[2], G);
     return (bits[lin >> 5] >> (lin & 31)) & 1u;
+}
+
+// BOX GRID (include/neo360_hip.h): bits (GRID LAYOUT of occupancy.hip) or NULL for "no grid"; scale_a = (float)G / (hi_a - lo_a),
+// host fp32
+struct VmBox {
+    const uint32_t* bits;
+    int G, clip;
+    float lo[3], scale[3];
+};
+
+// BOX KEEP RULE: a non-finite coordinate (the negation of `<`: a NaN survives), no grid, outside the box without clip, or a set cell
+__device__ __forceinline__ bool vm_keep_point(const VmBox& b, const float* __restrict__ o, const float* __restrict__ d, float tv) {
+    float x[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) x[a] = o[a] + tv * d[a];      // mul then add, as the evaluators
+    if (!(fabsf(x[0]) < __builtin_inff()) || !(fabsf(x[1]) < __builtin_inff()) || !(fabsf(x[2]) < __builtin_inff())) return true;
+    if (!b.bits) return true;
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float cf = floorf((x[a] - b.lo[a]) * b.scale[a]);
+        if (!(cf >= 0.0f && cf < (float)b.G)) return b.clip == 0;      // outside (an overflow to inf included)
+        c[a] = (int)cf;
+    }
+    const int lin = (c[0] * b.G + c[1]) * b.G + c[2];
+    return (b.bits[lin >> 5] >> (lin & 31)) & 1u;
+}
+
+inline bool vm_resolution_ok(int G) { return G == 8 || G == 16 || (G >= 32 && G <= 256 && G % 32 == 0); }
+
+// lo < hi, both finite, and a finite positive scale per axis; fills box.lo / box.scale
+inline const char* vm_box_from(int G, const float* lo, const float* hi, VmBox& box) {
+    for (int a = 0; a < 3; ++a) {
+        if (!(std::fabs(lo[a]) < INFINITY) || !(std::fabs(hi[a]) < INFINITY) || !(lo[a] < hi[a])) return "the box needs finite lo < hi on every axis";
+        const float scale = static_cast<float>(G) / (hi[a] - lo[a]);
+        if (!(scale > 0.0f && scale < INFINITY)) return "the box is too thin or too wide for fp32 cell arithmetic";
+        box.lo[a] = lo[a];
+        box.scale[a] = scale;
+    }
+    return nullptr;
 }
 
 // The first launch of the compaction: totals[workgroup] = the kept points of this workgroup, from the keep flag of this thread's

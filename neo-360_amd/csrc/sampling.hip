@@ -25,18 +25,7 @@ __global__ void k_pos_enc(const float* __restrict__ x, int n, int C, int min_deg
     const long total = (long)n * width;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const int row = (int)(idx / width), f = (int)(idx - (long)row * width);
-        float v;
-        if (f < C) {
-            v = x[(long)row * C + f];
-        } else {
-            const int g = f - C;
-            const bool shifted = g >= L * C;
-            const int h = shifted ? g - L * C : g;
-            const int k = min_deg + h / C, c = h % C;
-            const float a = ldexpf(x[(long)row * C + c], k);
-            v = shifted ? sin_cw(a + HALF_PI_F32) : sin_cw(a);
-        }
-        out[idx] = v;
+        out[idx] = pos_enc_feature([&](int c) { return x[(long)row * C + c]; }, C, min_deg, L, f);
     }
 }
 

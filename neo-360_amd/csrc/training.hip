@@ -5,6 +5,7 @@
 // wavefront per ray with shuffle scans, or one 16-lane group per 256-byte run of a channels-last texel.
 #include "common.h"
 #include "kernels.h"
+#include "philox.h"
 #include "tp_common.h"
 
 namespace neo {
@@ -14,25 +15,7 @@ namespace {
 constexpr int RPB = 4;            // rays (waves) per 256-thread block
 constexpr int MAXN = 1024;        // samples per ray the per-wave LDS rows hold
 
-// ---- Philox4x32-10 (Salmon et al., SC'11), one 128-bit block per (row, col, stream) ------------------------
-__device__ __forceinline__ uint32_t philox_u32(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2) {
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    uint32_t x0 = c0, x1 = c1, x2 = c2, x3 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * x0, p1 = (uint64_t)0xCD9E8D57u * x2;
-        const uint32_t y0 = (uint32_t)(p1 >> 32) ^ x1 ^ k0, y1 = (uint32_t)p1;
-        const uint32_t y2 = (uint32_t)(p0 >> 32) ^ x3 ^ k1, y3 = (uint32_t)p0;
-        x0 = y0; x1 = y1; x2 = y2; x3 = y3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return x0;
-}
-// uniform in [0, 1) with 24 random bits, as torch.rand produces fp32 (value = k 2^-24)
-__device__ __forceinline__ float philox_uniform(uint64_t seed, uint32_t row, uint32_t col, uint32_t stream) {
-    return (float)(philox_u32(seed, row, col, stream) >> 8) * 5.9604644775390625e-08f;
-}
-
+// ---- Philox4x32-10, one 128-bit block per (row, col, stream): philox.h ---------------------------------------
 __global__ void k_uniform(uint64_t seed, uint32_t stream, int rows, int cols, float* __restrict__ out) {
     const long total = (long)rows * cols;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
@@ -537,12 +520,9 @@ __global__ void k_tp_activate_bwd(const float* __restrict__ raw_rgb, const float
     const float4 gi = g[i];
     const float gc[3] = {gi.x, gi.y, gi.z};
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float sg = 1.0f / (1.0f + expf(-raw_rgb[i * 3 + c]));
-        g_rgb[i * 3 + c] = gc[c] * (1.002f * sg * (1.0f - sg));
-    }
+    for (int c = 0; c < 3; ++c) g_rgb[i * 3 + c] = colour_act_grad(raw_rgb[i * 3 + c], gc[c]);
     const float x = raw_sigma[i] + (noise ? noise[i] * noise_scale : 0.0f) + (-1.0f);
-    g_sigma[i] = gi.w * (x > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-x)));
+    g_sigma[i] = density_act_grad(x, gi.w);
 }
 
 }  // namespace

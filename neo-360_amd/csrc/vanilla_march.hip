@@ -36,30 +36,7 @@ namespace neo {
 
 namespace {
 
-// a grid over the box: bits (GRID LAYOUT of occupancy.hip) or NULL for "no grid"; scale_a = (float)G / (hi_a - lo_a), host fp32
-struct VmBox {
-    const uint32_t* bits;
-    int G, clip;
-    float lo[3], scale[3];
-};
-
-// BOX KEEP RULE: a non-finite coordinate (the negation of `<`: a NaN survives), no grid, outside the box without clip, or a set cell
-__device__ __forceinline__ bool vm_keep_point(const VmBox& b, const float* __restrict__ o, const float* __restrict__ d, float tv) {
-    float x[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = o[a] + tv * d[a];      // mul then add, as the evaluators
-    if (!(fabsf(x[0]) < __builtin_inff()) || !(fabsf(x[1]) < __builtin_inff()) || !(fabsf(x[2]) < __builtin_inff())) return true;
-    if (!b.bits) return true;
-    int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float cf = floorf((x[a] - b.lo[a]) * b.scale[a]);
-        if (!(cf >= 0.0f && cf < (float)b.G)) return b.clip == 0;      // outside (an overflow to inf included)
-        c[a] = (int)cf;
-    }
-    const int lin = (c[0] * b.G + c[1]) * b.G + c[2];
-    return (b.bits[lin >> 5] >> (lin & 31)) & 1u;
-}
+// VmBox and vm_keep_point, the BOX KEEP RULE of one point: occ_points.h (shared with vanilla_train_march.hip)
 
 // sample and ray of candidate p
 __device__ __forceinline__ void vm_candidate(int p, const int* __restrict__ map, int r0, int b0, int len, int& ray, int& j) {
@@ -152,19 +129,8 @@ namespace {
 
 constexpr int VM_WINDOW_DEFAULT = 8192;      // rays per window: 36 MB of point rows at a segment of 64
 
-bool vm_resolution_ok(int G) { return G == 8 || G == 16 || (G >= 32 && G <= 256 && G % 32 == 0); }
-
-// lo < hi, both finite, and a finite positive scale per axis; fills box.lo / box.scale
-const char* vm_box_from(int G, const float* lo, const float* hi, neo::VmBox& box) {
-    for (int a = 0; a < 3; ++a) {
-        if (!(std::fabs(lo[a]) < INFINITY) || !(std::fabs(hi[a]) < INFINITY) || !(lo[a] < hi[a])) return "the box needs finite lo < hi on every axis";
-        const float scale = static_cast<float>(G) / (hi[a] - lo[a]);
-        if (!(scale > 0.0f && scale < INFINITY)) return "the box is too thin or too wide for fp32 cell arithmetic";
-        box.lo[a] = lo[a];
-        box.scale[a] = scale;
-    }
-    return nullptr;
-}
+using neo::vm_box_from;            // occ_points.h
+using neo::vm_resolution_ok;
 
 // Per-ray state of one level's march in W[4]: [carry fp64 R | alive fp32 R | stop int R | the alive compaction of one window | one
 // keep byte per candidate of one launch].  alive is what the compaction reads: 1 in front of segment 0, then the transmittance.

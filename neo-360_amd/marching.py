@@ -10,6 +10,14 @@ The stage functions expose the rules the frame is made of, on caller rows:
     eval_points                 the compact evaluator launch: single points under a device count (neo_vanilla_mlp_compact)
     render_marching_rays        the frame helper
 
+and, for training through the grid (VANILLA MARCHING TRAINING: `MarchingNeRF.render_train_marching`, `init_occupancy`,
+`update_occupancy`):
+
+    train_rows                  the compact row builder: keep mask, device count, indices, encodings (neo_vanilla_train_rows)
+    nerf_mlp_rows               `training.nerf_mlp` on K rows with a cond row each, under autograd
+    scatter_activate            activations + scatter into the composite's rows, under autograd (neo_vanilla_train_scatter)
+    occupancy_probes            one jittered probe point per cell (neo_vanilla_grid_probes)
+
 Every caller tensor goes through `context.dense` / `context.owned_output`; a bad shape, dtype, G, box, eps or segment raises
 ValueError before any device access.
 """
@@ -19,7 +27,7 @@ import math
 import torch
 
 from . import _lib, models, ops
-from .context import dense, owned_output, ptr, ray_rows
+from .context import dense, f32, get_context, owned_output, ptr, ptr_table, ray_rows
 
 
 def _check_box(box, who):
@@ -156,9 +164,195 @@ def eval_points(model, level, rays_o, dirs, t, count, out=None):
     return out
 
 
+# ---- training through the grid (include/neo360_hip.h: VANILLA MARCHING TRAINING) ----------------------------------------------
+
+def _train_rows(ctx, bits, G, lo, hi, clip, rays_o, dirs, t, dir_enc, out=None):
+    """neo_vanilla_train_rows on converted tensors and packed bits (None: no grid)."""
+    B, N = t.shape
+    dev = t.device
+    cap = B * N
+    keep = torch.empty(B, N, dtype=torch.bool, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    if out is None:
+        index = torch.empty(cap, dtype=torch.int32, device=dev)
+        x_enc, cond = torch.empty(cap, 63, device=dev), torch.empty(cap, 27, device=dev)
+    else:
+        index, x_enc, cond = out
+    _lib.check(ctx.lib.neo_vanilla_train_rows(ctx.handle, ptr(bits), G, _c3(lo), _c3(hi), int(bool(clip)), ptr(rays_o), ptr(dirs), ptr(t),
+                                              ptr(dir_enc), B, N, cap, keep.data_ptr(), count.data_ptr(), index.data_ptr(),
+                                              x_enc.data_ptr(), cond.data_ptr(), ctx.stream()))
+    return keep, count, index, x_enc, cond
+
+
+@torch.no_grad()
+def train_rows(occ, box, rays_o, dirs, t, dir_enc, clip=False, ctx=None, out=None):
+    """The compact row builder of `MarchingNeRF.render_train_marching` on caller rows (neo_vanilla_train_rows): occ / box / clip as
+    `occupancy_keep_box` takes them (occ None: no grid), rays_o, dirs (B,3), t (B,N) and dir_enc (B,27) on the GPU.  Returns
+    (keep bool (B,N) - the BOX KEEP RULE -, count int32[1] ON THE DEVICE - the kept samples, not read here -, index int32 (B N,),
+    x_enc (B N, 63), cond (B N, 27)): for k < count, in ascending flat order, index[k] = b N + j of the k-th kept sample, x_enc[k]
+    bitwise `ops.pos_enc(rays_o[b] + t[b, j] * dirs[b], 0, 10)` and cond[k] = dir_enc[b].  The last three are allocated for B N rows;
+    rows at or behind the count are neither read nor written (out = (index, x_enc, cond): caller-owned tensors of those shapes,
+    written in place, so that a caller can see it).  No atomics, nothing synchronises."""
+    G = 0
+    lo = hi = (0.0, 0.0, 0.0)
+    if occ is not None:
+        G = ops._check_occupancy(occ, "train_rows")
+        lo, hi = _check_box(box, "train_rows")
+    rays_o, dirs, t = _rows(rays_o, dirs, t, "train_rows")
+    B, N = t.shape
+    dir_enc = dense(dir_enc, "dir_enc", (B, 27), device=t.device)
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 3:
+            raise ValueError("train_rows: out must be the three tensors (index, x_enc, cond)")
+        out = (owned_output(out[0], "out[0] (index)", (B * N,), dtype=torch.int32, device=t.device),
+               owned_output(out[1], "out[1] (x_enc)", (B * N, 63), device=t.device),
+               owned_output(out[2], "out[2] (cond)", (B * N, 27), device=t.device))
+        _lib.note_external_write()
+    ctx = ops._ctx(t, ctx)
+    bits = ops.pack_occupancy(occ.to(t.device)) if occ is not None else None
+    return _train_rows(ctx, bits, G, lo, hi, clip, rays_o, dirs, t, dir_enc, out)
+
+
+_NERF_LAYER_SHAPES = [(256, 63)] + [(256, 256)] * 4 + [(256, 319)] + [(256, 256)] * 2 + [(128, 283), (256, 256), (1, 256), (3, 128)]
+
+
+class _TrainVanillaRows(torch.autograd.Function):
+    """Vanilla NeRFMLP on K caller rows, each with its own cond (neo_vanilla_mlp_train_forward / _backward with R = K)."""
+
+    @staticmethod
+    def forward(ctx_, lib_ctx, x_enc, cond, *params):
+        from . import training as T
+        ws, bs = params[:12], params[12:]
+        x0 = dense(x_enc, "x_enc", (None, 63))      # x_enc defines K and the device
+        K, dev = x0.shape[0], x0.device
+        cd = dense(cond, "cond", (K, 27), device=dev)
+        T._check_layers("NeRFMLP layer", ws, bs, _NERF_LAYER_SHAPES)
+        raw_rgb, raw_sigma = torch.empty(K, 3, device=dev), torch.empty(K, 1, device=dev)
+        ctx_.meta = (None, K)
+        if K == 0:      # nothing to evaluate: the library is not called, and the backward returns exact zeros
+            ctx_.save_for_backward(*[w.detach() for w in ws])
+            return raw_rgb, raw_sigma
+        c = ops._ctx(x0, lib_ctx)
+        wd, bd = T._detached(ws, bs)
+        tape = torch.empty(c.lib.neo_vanilla_mlp_train_tape_floats(K), device=dev)
+        _lib.check(c.lib.neo_vanilla_mlp_train_forward(c.handle, ptr_table(wd), ptr_table(bd), ptr(x0), ptr(cd), K, ptr(tape),
+                                                       ptr(raw_rgb), ptr(raw_sigma), c.stream()))
+        ctx_.save_for_backward(x0, cd, tape, *wd)
+        ctx_.meta = (c, K)
+        return raw_rgb, raw_sigma
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx_, g_rgb, g_sigma):
+        from . import training as T
+        c, K = ctx_.meta
+        if K == 0:
+            wd = ctx_.saved_tensors
+            gw, gb = T._zero_param_grads(wd)
+            return (None, torch.zeros(0, 63, device=wd[0].device) if ctx_.needs_input_grad[1] else None, None, *gw, *gb)
+        x0, cd, tape, *wd = ctx_.saved_tensors
+        if ctx_.needs_input_grad[2]:
+            raise NotImplementedError("nerf_mlp_rows: no gradient for cond (the view-direction encodings are data)")
+        g_rgb = T._grad_or_zeros(g_rgb, "g_rgb", K, 3, x0.device)
+        g_sigma = T._grad_or_zeros(g_sigma, "g_sigma", K, 1, x0.device)
+        gw, gb = T._zero_param_grads(wd)
+        g_x0 = torch.empty_like(x0) if ctx_.needs_input_grad[1] else None
+        _lib.check(c.lib.neo_vanilla_mlp_train_backward(c.handle, ptr_table(wd), ptr(x0), ptr(cd), K, ptr(tape), ptr(g_rgb),
+                                                        ptr(g_sigma), ptr_table(gw), ptr_table(gb), ptr(g_x0), None, c.stream()))
+        return (None, g_x0, None, *gw, *gb)
+
+
+def nerf_mlp_rows(mlp, x_enc, cond, ctx=None):
+    """The row form of `training.nerf_mlp`: x_enc (K,63) encoded points and cond (K,27), each row's own view-direction encoding
+    (what `train_rows` emits) -> raw_rgb (K,3), raw_sigma (K,1).  Gradients flow to the 24 parameter tensors of `mlp`
+    (a models.NeRFMLP) and to x_enc.  K == 0 returns empty outputs and, in the backward, exact-zero parameter gradients, without
+    calling the library.  Exact fp32 matrix arithmetic."""
+    from . import training as T
+    if not isinstance(mlp, models.NeRFMLP):
+        raise TypeError("nerf_mlp_rows evaluates NeRFMLP containers, got %r" % type(mlp))
+    return _TrainVanillaRows.apply(ctx, x_enc, cond, *T._mlp_params(mlp))
+
+
+class _ScatterActivate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx_, raw_rgb, raw_sigma, index, total, noise, noise_scale, lib_ctx):
+        if isinstance(total, bool) or not isinstance(total, int) or total < 0:
+            raise ValueError("scatter_activate: total must be a non-negative integer, got %r" % (total,))
+        index = dense(index, "index", (None,), dtypes=(torch.int32,), to=torch.int32)      # index defines K and the device
+        K, dev = index.shape[0], index.device
+        if K > total:
+            raise ValueError("scatter_activate: %d rows cannot be scattered into %d" % (K, total))
+        raw_rgb = dense(raw_rgb, "raw_rgb", (K, 3), device=dev)
+        raw_sigma = dense(raw_sigma, "raw_sigma", [(K,), (K, 1)], device=dev)
+        noise = dense(noise, "noise", device=dev) if noise is not None else None
+        if noise is not None and noise.numel() != total:
+            raise ValueError("noise must hold one value per point (%d), got %s" % (total, tuple(noise.shape)))
+        c = ops._ctx(index, lib_ctx)
+        packed = torch.empty(total, 4, device=dev)
+        _lib.check(c.lib.neo_vanilla_train_scatter(c.handle, ptr(raw_rgb), ptr(raw_sigma), ptr(index), K, ptr(noise), float(noise_scale),
+                                                   total, ptr(packed), c.stream()))
+        ctx_.save_for_backward(raw_rgb, raw_sigma, index, noise if noise is not None else torch.empty(0, device=dev))
+        ctx_.meta = (c, float(noise_scale), noise is not None, total, tuple(raw_sigma.shape))
+        return packed
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx_, g):
+        raw_rgb, raw_sigma, index, noise = ctx_.saved_tensors
+        c, scale, has_noise, total, shape_sigma = ctx_.meta
+        K = index.shape[0]
+        g_rgb, g_sigma = torch.empty(K, 3, device=index.device), torch.empty(K, device=index.device)
+        if K:
+            g = f32(g.reshape(total, 4).contiguous(), "grad")
+            _lib.check(c.lib.neo_vanilla_train_scatter_backward(c.handle, ptr(raw_rgb), ptr(raw_sigma), ptr(index), K,
+                                                                ptr(noise) if has_noise else None, scale, total, ptr(g), ptr(g_rgb),
+                                                                ptr(g_sigma), c.stream()))
+        return g_rgb, g_sigma.reshape(shape_sigma), None, None, None, None, None
+
+
+def scatter_activate(raw_rgb, raw_sigma, index, total, noise=None, noise_scale=0.0, ctx=None):
+    """`training.activate` fused with the scatter into the composite's rows (neo_vanilla_train_scatter / _backward): raw_rgb (K,3),
+    raw_sigma (K,) or (K,1), index int32 (K,) - distinct flat positions in [0, total) - and optionally noise, `total` uniforms
+    indexed by POSITION -> packed (total, 4): row index[k] is bitwise `training.activate`'s row of (raw_rgb[k], raw_sigma[k],
+    noise[index[k]]), every other row is zero (composite mode 0 gives such a sample weight exactly 0).  The backward gathers the
+    gradient rows at index and is bitwise `training.activate`'s on them.  K == 0: all zeros, empty gradients."""
+    return _ScatterActivate.apply(raw_rgb, raw_sigma, index, total, noise, noise_scale, ctx)
+
+
+def _check_counter(v, name, who, bits):
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** bits:
+        raise ValueError("%s: %s must be an integer in [0, 2^%d), got %r" % (who, name, bits, v))
+    return v
+
+
+@torch.no_grad()
+def occupancy_probes(box, resolution, seed, step, device="cuda", ctx=None):
+    """The probe points of `MarchingNeRF.update_occupancy` (neo_vanilla_grid_probes): (G^3, 3), G = resolution, in the grid's
+    [ix][iy][iz] order - one point per cell of the grid over box = (lo, hi), at lo + (c + u) (hi - lo) / G per axis, u in [0, 1) from
+    the library's counter-based generator (key `seed`, counter (cell, step, 8 + axis, 0)).  Every point lies in its own cell under
+    the grid's fp32 cell expression (`occupancy_keep_box`); a candidate that rounding pushed over a face is replaced by the cell's
+    centre on that axis.  The same (seed, step) gives the same bits."""
+    if not ops.occupancy_resolution_ok(resolution):
+        raise ValueError("occupancy_probes: resolution must be 8, 16 or a multiple of 32 in [32, 256], got %r" % (resolution,))
+    lo, hi = _check_box(box, "occupancy_probes")
+    seed = _check_counter(seed, "seed", "occupancy_probes", 64)
+    step = _check_counter(step, "step", "occupancy_probes", 32)
+    G = int(resolution)
+    for a in range(3):      # the library's own refusal, before any device access
+        lo32, hi32 = (torch.tensor(v, dtype=torch.float32) for v in (lo[a], hi[a]))
+        if not float((hi32 - lo32) / G) * 131072.0 >= max(abs(float(lo32)), abs(float(hi32))):
+            raise ValueError("occupancy_probes: the box's cells are too thin for fp32 probe points, got %r" % (box,))
+    if ctx is None:
+        ctx = get_context(device)
+    pts = torch.empty(G ** 3, 3, device=ctx.device)
+    _lib.check(ctx.lib.neo_vanilla_grid_probes(ctx.handle, G, _c3(lo), _c3(hi), seed, step, ptr(pts), ctx.stream()))
+    return pts
+
+
 class MarchingNeRF(models.NeRF):
-    """`models.NeRF` with an occupancy grid over a box and the marching frame.  `forward`, `eval_mlp` and the training path are
-    the parent's and read none of this."""
+    """`models.NeRF` with an occupancy grid over a box, the marching frame, and training through the grid
+    (`render_train_marching`, `init_occupancy`, `update_occupancy`).  `forward`, `eval_mlp` and the parent's training path read none
+    of this."""
 
     # rays per window of render_marching (None: the library's default, 8192): a window bounds the extra workspace at 68 bytes per
     # (ray, sample) of one window and segment; results do not depend on it
@@ -168,7 +362,15 @@ class MarchingNeRF(models.NeRF):
         super().__init__(*args, **kwargs)
         self._occupancy = self._occ_box = self._occ_ctx = None
         self._occ_clip = False
+        self._occ_bits = None
         self.last_march_kept = None
+        self.last_train_kept = None
+        self._run = None            # init_occupancy: dict(box, G, clip, density, updates)
+
+    @property
+    def occupancy_density(self):
+        """The running density of `update_occupancy` as a float (G,G,G) device tensor (a copy), or None before `init_occupancy`."""
+        return None if self._run is None else self._run["density"].clone()
 
     @property
     def occupancy(self):
@@ -191,7 +393,7 @@ class MarchingNeRF(models.NeRF):
             if self._occ_ctx is not None and self._occ_ctx.handle:
                 c = self._occ_ctx
                 _lib.check(c.lib.neo_vanilla_set_occupancy(c.handle, None, 0, None, None, 0, c.stream()))
-            self._occupancy = self._occ_box = self._occ_ctx = None
+            self._occupancy = self._occ_box = self._occ_ctx = self._occ_bits = None
             self._occ_clip = False
             return
         G = ops._check_occupancy(grid, "set_occupancy")
@@ -202,6 +404,118 @@ class MarchingNeRF(models.NeRF):
         bits = ops.pack_occupancy(occ)
         _lib.check(ctx.lib.neo_vanilla_set_occupancy(ctx.handle, ptr(bits), G, _c3(lo), _c3(hi), int(bool(clip)), ctx.stream()))
         self._occupancy, self._occ_box, self._occ_clip, self._occ_ctx = occ, (lo, hi), bool(clip), ctx
+        self._occ_bits = bits       # the training row builder reads the caller-side bits (render_train_marching)
+
+    @torch.no_grad()
+    def init_occupancy(self, box, resolution, clip=False):
+        """Starts a running grid over box = (lo, hi): installs an all-ones grid of `resolution` cells per axis (`set_occupancy`: every
+        sample inside the box is kept until the first update) and creates the zero running density (G,G,G) that
+        `update_occupancy` maintains (`occupancy_density`).  ValueError, before any device access, for a bad box or resolution."""
+        if not ops.occupancy_resolution_ok(resolution):
+            raise ValueError("init_occupancy: resolution must be 8, 16 or a multiple of 32 in [32, 256], got %r" % (resolution,))
+        G = int(resolution)
+        box = _check_box(box, "init_occupancy")
+        dev = next(self.parameters()).device
+        self.set_occupancy(torch.ones(G, G, G, dtype=torch.bool, device=dev), box, clip)
+        self._run = dict(box=box, G=G, clip=bool(clip), density=torch.zeros(G, G, G, device=dev), updates=0)
+
+    @torch.no_grad()
+    def update_occupancy(self, sigma_threshold, decay=0.95, dilate=1, seed=1):
+        """One update of the running grid of `init_occupancy`, from the module's CURRENT parameters: one jittered probe point per
+        cell (`occupancy_probes` with step = the number of updates so far), both MLPs evaluated there through the compact evaluator
+        (`eval_points`; a vanilla density depends on the position alone), density = max(decay * density, max(sigma_0, sigma_1))
+        per cell (neo_vanilla_density_update; a NaN stays), and the grid = `occupancy_from_sigma_box(density, G, sigma_threshold,
+        probes=1, dilate)`, installed with `set_occupancy` and returned.  EVERY cell is probed at every update, whatever the current
+        grid says: a cleared cell comes back as soon as its density does, and an emptied one clears once decay^n has taken its
+        remembered density to the threshold.  sigma_threshold has no default: nobody has measured one on trained weights.
+        ValueError, before any device access, for a bad threshold, decay (outside [0, 1]), dilate or seed; NeoError before
+        `init_occupancy`."""
+        if self._run is None:
+            raise _lib.NeoError("update_occupancy: no running grid - call init_occupancy(box, resolution) first")
+        run = self._run
+        G, _, dilate = ops._check_build(run["G"], sigma_threshold, 1, dilate, "update_occupancy")
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) <= 1.0:
+            raise ValueError("update_occupancy: decay must be a number in [0, 1], got %r" % (decay,))
+        seed = _check_counter(seed, "seed", "update_occupancy", 64)
+        dev = next(self.parameters()).device
+        if run["density"].device != dev:
+            raise _lib.NeoError("the running density lives on %s, the module on %s: call init_occupancy again" % (run["density"].device, dev))
+        ctx = self._context(dev)
+        cells = G ** 3
+        pts = occupancy_probes(run["box"], G, seed, run["updates"] & 0xFFFFFFFF, ctx=ctx)
+        dirs = torch.zeros(cells, 3, device=dev)
+        dirs[:, 2] = 1.0
+        t = torch.zeros(cells, device=dev)
+        count = torch.full((1,), cells, dtype=torch.int32, device=dev)
+        sigma = [eval_points(self, lv, pts, dirs, t, count)[:, 3].contiguous() for lv in range(2)]
+        _lib.check(ctx.lib.neo_vanilla_density_update(ctx.handle, ptr(run["density"]), ptr(sigma[0]), ptr(sigma[1]), G, float(decay),
+                                                      ctx.stream()))
+        grid = occupancy_from_sigma_box(run["density"], G, sigma_threshold, probes=1, dilate=dilate, ctx=ctx)
+        self.set_occupancy(grid, run["box"], run["clip"])
+        run["updates"] += 1
+        return grid
+
+    def render_train_marching(self, rays, randomized, white_bkgd, near, far, seed=None, grid=True, return_samples=False):
+        """`training.nerf_render_train(self, rays, randomized, white_bkgd, near, far, seed)` - the same sample positions, random
+        streams, noise tables, composite and resampling - in which only the samples the installed grid keeps (`occupancy_keep_box`;
+        grid=False or no grid: every sample) go through the MLP, forward and backward.  Per level, between the positions and the
+        composite: `train_rows` (keep mask, count, flat indices, encodings and direction rows of the kept samples), ONE 4-byte read
+        of the count, `nerf_mlp_rows` on exactly that many rows, `scatter_activate` into the level's zero rows.  A sample that is
+        not kept has the row (0, 0, 0, 0): weight exactly 0, no gradient.  There is no stop rule here: a training ray must see its
+        whole interval.  Without a grid (or with every cell set, or a box that holds no sample and clip=False) the six outputs
+        are bitwise `nerf_render_train`'s for the same seed.
+
+        The count read BLOCKS, once per level - the training GEMMs take their row count from the host - on top of the flag read at
+        the end of the call, which blocks as in `nerf_render_train`.  `self.last_train_kept` = (kept at level 0, kept at level 1)
+        as Python ints.  NeoError when grid=True and the installed grid belongs to another context.
+
+        Returns [(rgb (B,3), acc (B,), depth (B,))] * 2; with return_samples (that, [(t (B,N), keep (B,N) bool)] * 2)."""
+        from . import training as T
+        rays_o, rays_d, viewdirs = ray_rows(rays)        # rays_o defines B
+        B, dev = rays_o.shape[0], rays_o.device
+        c = self._context(dev)
+        use = bool(grid) and self._occupancy is not None
+        if use and self._occ_ctx is not c:
+            raise _lib.NeoError("the occupancy grid does not belong to this module's context on %s: install it again" % dev)
+        bits, G, clip = (self._occ_bits, self._occupancy.shape[0], self._occ_clip) if use else (None, 0, False)
+        lo, hi = self._occ_box if use else ((0.0,) * 3, (0.0,) * 3)
+        n0, n1 = self.num_coarse_samples, self.num_fine_samples
+        noise = float(self.noise_std) if randomized else 0.0
+        with torch.no_grad():       # positions and direction encodings: nerf_render_train's own lines
+            if randomized:
+                seed = int(seed) if seed is not None else int(torch.randint(1, 2 ** 62, (1,)).item())
+                seed = seed or 1
+            lin = torch.linspace(0.0, 1.0, n0 + 1).to(dev)
+            edges = float(near) * (1.0 - lin) + float(far) * lin
+            if randomized:
+                mids = 0.5 * (edges[1:] + edges[:-1])
+                upper, lower = torch.cat([mids, edges[-1:]]), torch.cat([edges[:1], mids])
+                t = lower + (upper - lower) * T.rand_uniform(seed, 0, B, n0 + 1, ctx=c)
+            else:
+                t = edges[None, :].expand(B, n0 + 1).contiguous()
+            d_enc = ops.pos_enc(viewdirs, 0, self.deg_view, ctx=c)
+        out, used, kept = [], [], []
+        for level, mlp in enumerate((self.coarse_mlp, self.fine_mlp)):
+            N = t.shape[1]
+            with torch.no_grad():
+                keep, count, index, x_enc, cond = _train_rows(c, bits, G, lo, hi, clip, rays_o, viewdirs, t, d_enc)
+                K = int(count.item()) if B else 0      # the one blocking read of this level
+            kept.append(K)
+            used.append((t, keep))
+            raw_rgb, raw_sigma = nerf_mlp_rows(mlp, x_enc[:K], cond[:K], ctx=c)
+            u_noise = T.rand_uniform(seed, 4 + 2 * level, B, N, ctx=c) if noise > 0.0 else None
+            packed = scatter_activate(raw_rgb, raw_sigma, index[:K], B * N, u_noise, noise, ctx=c).reshape(B, N, 4)
+            comp_rgb, acc, w, _, depth = T.composite(0, packed, None, t, rays_d, None, white_bkgd, ctx=c)
+            out.append((comp_rgb, acc, depth))
+            if level == 0:
+                with torch.no_grad():
+                    if randomized:
+                        t = T.resample_u(t, w, T.rand_uniform(seed, 2, B, n1, ctx=c), False, ctx=c)
+                    else:
+                        t = ops.resample(t, w.detach(), n1, False, ctx=c)
+        self.last_train_kept = tuple(kept)
+        self._raise_flags(c.poll_flags())
+        return (out, used) if return_samples else out
 
     @torch.no_grad()
     def _occupancy_sigma(self, box, resolution, probes, points_per_piece=1 << 22):
