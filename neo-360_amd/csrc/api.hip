@@ -193,8 +193,8 @@ int neo_ctx_destroy(neo_ctx* ctx) {
     for (auto& sl : ctx->pix) sl.release();
     ctx->pix_latent.release();
     ctx->boxes.release();
-    ctx->occ_bits.release();
-    ctx->vocc_bits.release();
+    ctx->occ.bits.release();
+    ctx->vocc.bits.release();
     ctx->enc.release();
     ctx->enc_latent.release();
     ctx->enc_axes.release();

@@ -203,110 +203,54 @@ int tp_launch(neo_ctx* ctx, MlpSlot& sl, const neo::TpScene& sc, const neo::TpVi
 // the frame's size; the frame's 75 windows per level cost 5 small launches each.
 constexpr int SKIP_WINDOW_DEFAULT = 4096;
 
-// The inside-sphere evaluation of one level of a skipping frame (tp_render_dense, TpDenseOptions::skip): per window of rays,
-// classify + compact the points (occupancy.hip), ONE compact launch of the level's evaluator on single points - R = the window's
-// rows, N = 1, the identity map, the device count - and the scatter into the dense rows.  keep: the caller's (R,N) mask of the
-// level, or null: the mask then lives one window at a time in W[13].
-int tp_eval_skipping(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* fg_t, int N, float* fg_out,
-                     uint8_t* keep, long long* kept) {
-    hipStream_t s = f.s;
-    const int win = std::min(ctx->skip_window > 0 ? ctx->skip_window : SKIP_WINDOW_DEFAULT, a.R);
-    const size_t cap = static_cast<size_t>(win) * N;
-    REQUIRE(cap * 3 <= 2147483647UL, "skip window too large for 32-bit indices");
-    if (ctx->ws[12].reserve(neo::occ_rows_bytes(cap)) || (!keep && ctx->ws[13].reserve(cap))) return NEO_ERR_NOMEM;
-    neo::OccRows w;
-    w.carve(ctx->ws[12].p, cap);
-    const uint32_t* bits = ctx->occ_G ? ctx->occ_bits.as<uint32_t>() : nullptr;
-    if (kept) HIP_TRY(hipMemsetAsync(kept, 0, sizeof(long long), s));
-    neo::launch_occ_iota(w.iota, static_cast<int>(cap), s);
-    for (int r0 = 0; r0 < a.R; r0 += win) {
-        const int rays = std::min(win, a.R - r0);
-        const int P = rays * N;
-        const size_t first = static_cast<size_t>(r0) * N;
-        uint8_t* keep_win = keep ? keep + first : ctx->ws[13].as<uint8_t>();
-        neo::launch_occ_compact(a.rays_o, a.rays_d, a.viewdirs, fg_t + first, r0, rays, a.R, N, a.chunk, bits, ctx->occ_G, keep_win,
-                                w, kept, s);
-        if (int rc = tp_launch(ctx, ctx->tp[level], f.sc, f.views, w.o, w.d, w.v, w.t, nullptr, P, 1, a.chunk, w.out, s, w.iota, w.count))
-            return rc;
-        neo::launch_occ_scatter(keep_win, P, w, fg_out + first * 4, s);
-    }
-    return NEO_OK;
-}
-
-// Per-row state of one region's march in W[13] (march.h: a row is a ray inside the sphere, a COMPACT background row outside):
-// inside  [carry fp64 R | alive fp32 R | stop int R | the alive compaction of one window | with a grid: one keep byte per candidate of
-//          one segment launch];
-// outside [carry fp64 R | lam_c fp32 R | alive fp32 R | value fp32 R | stop int R | the alive compaction of one window].
-// alive is what the compaction reads: 1 in front of segment 0, then the running value; outside, -1 behind the survivor count.  The
-// outside march follows the inside marches of both levels, whose state is dead by then: the two carvings share the bytes.
-struct TpMarchState {
-    double* carry;
-    float *lam_c, *alive, *value;      // lam_c, value: outside only (null inside)
-    int *stop, *cws;
-    uint8_t* keep;
-    static size_t bytes(bool outside, size_t r, int win, size_t candidates = 0) {
-        return r * (outside ? 24 : 16) + neo::cull_ws_ints(win) * sizeof(int) + candidates;
-    }
-    void carve(void* base, bool outside, size_t r, int win) {
-        carry = static_cast<double*>(base);
-        float* f = reinterpret_cast<float*>(carry + r);
-        lam_c = outside ? f : nullptr;
-        alive = outside ? f + r : f;
-        value = outside ? f + 2 * r : nullptr;
-        stop = reinterpret_cast<int*>(alive + (outside ? 2 : 1) * r);
-        cws = stop + r;
-        keep = reinterpret_cast<uint8_t*>(cws + neo::cull_ws_ints(win));
-    }
-};
-
-// One region's evaluation of one level of a marching frame (include/neo360_hip.h: STOP RULE, OUTSIDE STOP RULE) into zero-filled
-// rows `out`.  Per window of rows and per segment: compact the alive rows (launch_cull_compact on the running value: !(alive < eps),
-// ascending order, the count on the device), emit their point rows of the segment, ONE compact launch of the level's evaluator on
-// single points (as tp_eval_skipping), scatter, advance.  A point list has at most skip_window x N rows - the bound, the buffer
-// (W[12]) and the knob of the skipping frame - so a window holds skip_window N / segment rows.  st.stop: samples marched per row;
-// *kept: their sum.
-//   inside  (map, count, lam NULL): rows are the frame's rays, pos = the level's dense fg_t.  bits / G (neo_tp_render_accelerated with
-//           a grid; NULL otherwise): the emit step is the fused classify + compact of accelerate.hip over the segment's candidates, so
-//           only the samples that the grid keeps are evaluated and counted.  A skipped sample stays a zero row, which is what the
-//           advance and the composite read: the stops are the STOP RULE on the masked rows.
-//   outside (map / count: the frame's survivors; lam: the level's dense lambdas): rows are the compact background rows of the culled
+// One region's evaluation of one level through THE LEVEL LOOP (march_level, march.h; include/neo360_hip.h: KEEP RULE, STOP RULE,
+// OUTSIDE STOP RULE) into `out`: the point rows of one launch in W[12], the level's evaluator as ONE compact launch on single points
+// per window and segment - R = the launch's rows, N = 1, the identity map, the device count.  rule: how the level stops, and with
+// its composite mode the region (1 inside, 2 outside); win: rows per window; st.stop: samples marched per row; *kept: the evaluated
+// samples.
+//   inside  (map, rule.count, rule.lam NULL): rows are the frame's rays, pos = the level's dense fg_t.  grid (NULL: none is read): only the
+//           samples that the KEEP RULE keeps are evaluated and counted.  A skipped sample stays a zero row, which is what the
+//           advance and the composite read: the stops are the STOP RULE on the masked rows.  Without `follow` the level is one
+//           segment of N samples per window - the skipping frame.
+//   outside (map / rule.count: the frame's survivors; rule.lam: the level's dense lambdas; rule.t_far: the far column): rows are the compact background rows of the culled
 //           frame, pos row k at pos + k N (level 0: R equal rows).  The survivor count lives on the device, so the windows cover all R
 //           rows and every launch behind the count finds no alive row.
-int tp_eval_march(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, bool outside, int level, const float* pos, const float* far,
-                  int N, float* out, const float* lam, const int* map, const int* count, float eps, int segment, const TpMarchState& st,
-                  int win, long long* kept, bool dens, const uint32_t* bits, int G) {
+int tp_eval_march(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, const MarchRule& rule, int level, const float* pos, int N,
+                  float* out, const int* map, const MarchState& st, int win, long long* kept, bool dens, const neo::OccGrid* grid) {
     hipStream_t s = f.s;
-    const int seg = std::min(segment, N);
-    const size_t cap = static_cast<size_t>(win) * seg;
+    const bool outside = rule.mode == 2;
+    const size_t cap = march_level_cap(rule, N, win);
     if (ctx->ws[12].reserve(neo::occ_rows_bytes(cap))) return NEO_ERR_NOMEM;
     neo::OccRows w;
     w.carve(ctx->ws[12].p, cap);
-    HIP_TRY(hipMemsetAsync(out, 0, static_cast<size_t>(a.R) * N * 16, s));
-    neo::launch_march_init(lam, map, count, a.R, st.lam_c, st.alive, st.value, st.stop, 0, kept, 0, s);
     neo::launch_occ_iota(w.iota, static_cast<int>(cap), s);
-    for (int k0 = 0; k0 < a.R; k0 += win) {
-        const int rows = std::min(win, a.R - k0);
-        for (int b0 = 0; b0 < N; b0 += segment) {
-            const int len = std::min(segment, N - b0);
-            const int P = rows * len;
-            neo::launch_cull_compact(st.alive + k0, st.alive + k0, rows, eps, st.cws, nullptr, s);
-            const int* map_w = neo::cull_map_of(st.cws, rows);      // the workspace's layout follows the window's row count
-            const int* count_w = neo::cull_count_of(st.cws, rows);
-            if (bits)
-                neo::launch_acc_compact(a.rays_o, a.rays_d, a.viewdirs, pos, map_w, count_w, k0, rows, a.R, N, b0, len, a.chunk, bits, G,
-                                        st.keep, w, kept, s);
-            else
-                neo::launch_march_emit(a.rays_o, a.rays_d, a.viewdirs, outside ? far : nullptr, pos, N, map, map_w, count_w, k0, rows, a.R,
-                                       N, b0, len, a.chunk, w, kept, s);
-            if (int rc = tp_launch(ctx, ctx->tp[(outside ? 2 : 0) + level], f.sc, f.views, w.o, w.d, w.v, w.t, outside ? w.far : nullptr, P,
-                                   1, a.chunk, w.out, s, w.iota, w.count, dens))
-                return rc;
-            neo::launch_march_scatter(w, P, out, s);
-            neo::launch_march_advance(outside, out, pos, N, a.rays_d, far, st.lam_c, N, b0, b0 + len, segment, eps, map_w, count_w, rows, k0,
-                                      st.carry, st.value, st.alive, st.stop, s);
-        }
-    }
-    return NEO_OK;
+    neo::PointSource src{};
+    src.rays_o = a.rays_o, src.dirs = a.rays_d, src.viewdirs = a.viewdirs, src.far = outside ? rule.t_far : nullptr;
+    src.pos = pos, src.stride = N, src.map = map;
+    src.R = a.R, src.N = N, src.chunk = a.chunk;
+    return march_level(src, grid, rule, st, win, w, out, kept, s, [&](const neo::OccRows& rows, long P) {
+        return tp_launch(ctx, ctx->tp[(outside ? 2 : 0) + level], f.sc, f.views, rows.o, rows.d, rows.v, rows.t,
+                         outside ? rows.far : nullptr, static_cast<int>(P), 1, a.chunk, rows.out, s, rows.iota, rows.count, dens);
+    });
+}
+
+// The inside-sphere evaluation of one level of a skipping frame (tp_render_dense, TpDenseOptions::skip): the march that follows
+// no rule, in windows of skip_window rays.  keep: the caller's (R,N) mask of the level, or null: the mask then lives one window at
+// a time in W[13].
+int tp_eval_skipping(neo_ctx* ctx, const TpFrame& f, const TpFrameArgs& a, int level, const float* fg_t, int N, float* fg_out,
+                     uint8_t* keep, long long* kept) {
+    const int win = std::min(ctx->skip_window > 0 ? ctx->skip_window : SKIP_WINDOW_DEFAULT, a.R);
+    const size_t cap = static_cast<size_t>(win) * N;
+    REQUIRE(cap * 3 <= 2147483647UL, "skip window too large for 32-bit indices");
+    if (!keep && ctx->ws[13].reserve(cap)) return NEO_ERR_NOMEM;
+    MarchState st{};
+    st.keep = keep ? keep : ctx->ws[13].as<uint8_t>();
+    st.keep_dense = keep != nullptr;
+    const neo::OccGrid* grid = ctx->occ.get();
+    if (!grid && keep)      // no grid installed: the point list classifies nothing, and the KEEP RULE keeps every point
+        HIP_TRY(hipMemsetAsync(keep, 1, static_cast<size_t>(a.R) * N, f.s));
+    return tp_eval_march(ctx, f, a, MarchRule{false, 0.0f, 0, 1, a.rays_d, nullptr, nullptr, nullptr}, level, fg_t, N, fg_out, nullptr, st,
+                         win, kept, false, grid);
 }
 
 // may the level-0 launches of a frame render be density-only?  Yes when the caller takes none of the level's colours or depth
@@ -556,7 +500,7 @@ int neo_tp_set_scene(neo_ctx* ctx, const float* plane_xz, const float* plane_xy,
     ctx->scene.fy_sign = -1.0f;                                       // NeRF_TP projects with (f, -f) (model.py:243)
     ctx->scene_epoch += 1;
     ctx->scene_ready = true;
-    ctx->occ_G = 0;      // an occupancy grid describes one scene
+    ctx->occ.clear();      // an occupancy grid describes one scene
     return check_launch();
 }
 
@@ -719,29 +663,25 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
     // the background has run) and the compact background results, W[10] the compaction's map / slot / count; a march adds the
     // point rows of one segment launch in W[12] and the per-row march state in W[13]
     auto* W = ctx->ws;
-    int win_of[2] = {0, 0};
-    const uint32_t* bits = nullptr;
-    int G = 0;
-    TpMarchState st{}, ot{};      // inside by ray; outside by compact row: the same bytes, read only after the inside marches are done
+    int win_of[2] = {0, 0}, win_skip = 0;
+    const neo::OccGrid* grid = nullptr;
+    MarchState st{}, ot{};      // inside by ray; outside by compact row: the same bytes, read only after the inside marches are done
     if (o.stop_inside) {
         REQUIRE(r * N1 <= 2147483647UL, "too many points for 32-bit indices");
         const int skip_window = ctx->skip_window > 0 ? ctx->skip_window : SKIP_WINDOW_DEFAULT;
         win_of[0] = static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N0 / segment)));
         win_of[1] = static_cast<int>(std::min<size_t>(r, std::max<size_t>(1, static_cast<size_t>(skip_window) * N1 / segment)));
         const int win_max = std::max(win_of[0], win_of[1]);
-        REQUIRE(static_cast<size_t>(win_max) * std::min(segment, N1) * 3 <= 2147483647UL, "skip window too large for 32-bit indices");
-        // with a grid: one keep byte per candidate of a segment launch behind the march state, and room for the keep window that a
-        // level 0 without `coarse` (tp_eval_skipping) puts at the front of W[13] before the state is initialised - reserved here, so
-        // that nothing re-allocates under the state
-        if (use_occ && ctx->occ_G) {
-            bits = ctx->occ_bits.as<uint32_t>();
-            G = ctx->occ_G;
-        }
-        const size_t candidates = bits ? static_cast<size_t>(win_max) * std::min(segment, N1) : 0;
-        const size_t skip_keep = bits && !coarse ? static_cast<size_t>(std::min(skip_window, R)) * N0 : 0;
-        if (bits || (use_occ && ((samples0 && samples0->fg_keep) || (samples1 && samples1->fg_keep))))
+        if (use_occ) grid = ctx->occ.get();
+        // the rows of one launch: a segment of a window - or, with a grid and without `coarse`, all N0 samples of a window of
+        // skip_window rays, the skipping frame's level 0, which follows no rule
+        win_skip = grid && !coarse ? std::min(skip_window, R) : 0;
+        const size_t launch_rows = std::max(static_cast<size_t>(win_max) * std::min(segment, N1), static_cast<size_t>(win_skip) * N0);
+        REQUIRE(launch_rows * 3 <= 2147483647UL, "skip window too large for 32-bit indices");
+        const size_t candidates = grid ? launch_rows : 0;      // with a grid: one keep byte per candidate behind the march state
+        if (grid || (use_occ && ((samples0 && samples0->fg_keep) || (samples1 && samples1->fg_keep))))
             REQUIRE(r * N1 <= 2147483647UL - 1024, "too many points for 32-bit indices");
-        if (W[13].reserve(std::max({TpMarchState::bytes(false, r, win_max, candidates), skip_keep, TpMarchState::bytes(true, r, win_max)})))
+        if (W[13].reserve(std::max(MarchState::bytes(false, r, win_max, candidates), MarchState::bytes(true, r, win_max))))
             return NEO_ERR_NOMEM;
         st.carve(W[13].p, false, r, win_max);
         ot.carve(W[13].p, true, r, win_max);
@@ -779,12 +719,15 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
         const bool dens = level == 0 && sigma0;
         uint8_t* fg_keep = use_occ && so ? so->fg_keep : nullptr;       // the KEEP RULE on the whole row, behind the stops as well
         if (o.stop_inside && (level == 1 || coarse)) {
-            if (int rc = tp_eval_march(ctx, f, a, false, level, fg_t, far, N, fg_out, nullptr, nullptr, nullptr, eps, segment, st,
-                                       win_of[level], kept ? kept + level : nullptr, false, bits, G))
+            if (int rc = tp_eval_march(ctx, f, a, MarchRule{true, eps, segment, 1, rays_d, far, nullptr, nullptr}, level, fg_t, N, fg_out,
+                                       nullptr, st, win_of[level], kept ? kept + level : nullptr, false, grid))
                 return rc;
-        } else if (bits) {      // the grid alone: neo_tp_render_skipping's level 0 (it may use the front of W[13]: before the init)
-            if (int rc = tp_eval_skipping(ctx, f, a, 0, fg_t, N, fg_out, fg_keep, kept)) return rc;
-            neo::launch_march_init(nullptr, nullptr, nullptr, R, nullptr, nullptr, nullptr, st.stop, N, nullptr, 0, s);
+        } else if (grid) {      // the grid alone: neo_tp_render_skipping's level 0, its mask straight into the caller's
+            MarchState sk = st;
+            if (fg_keep) sk.keep = fg_keep, sk.keep_dense = true;
+            if (int rc = tp_eval_march(ctx, f, a, MarchRule{false, 0.0f, 0, 1, rays_d, far, nullptr, nullptr}, 0, fg_t, N, fg_out, nullptr, sk,
+                                       win_skip, kept, false, grid))
+                return rc;
             fg_keep = nullptr;
         } else {
             if (int rc = tp_launch(ctx, ctx->tp[level], sc, views, rays_o, rays_d, viewdirs, fg_t, nullptr, R, N, chunk, fg_out, s, nullptr, nullptr, dens)) return rc;
@@ -799,7 +742,9 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
             if (so->fg_w && level == 0) HIP_TRY(hipMemcpyAsync(so->fg_w, fg_w0, row, hipMemcpyDeviceToDevice, s));
             if (so->stop) HIP_TRY(hipMemcpyAsync(so->stop, st.stop, r * sizeof(int), hipMemcpyDeviceToDevice, s));
             if (so->fg_rows) HIP_TRY(hipMemcpyAsync(so->fg_rows, fg_out, row * 4, hipMemcpyDeviceToDevice, s));
-            if (fg_keep) neo::launch_occ_keep(rays_o, rays_d, fg_t, R, N, bits, G, fg_keep, s);
+            if (fg_keep)
+                neo::launch_point_keep(neo::point_source_dense(rays_o, rays_d, fg_t, N, R, N), grid ? *grid : neo::OccGrid{},
+                                       fg_keep, nullptr, s);
         }
         if (level == 0 && neo::launch_resample(fg_t0, N0, fg_w0, f.u, 0, R, N0, n_fine, 0, fg_t1, s))
             return fail(NEO_ERR_INVALID, "unsupported sample counts");
@@ -814,8 +759,8 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
         const neo_tp_march_samples* so = sos[level];
         long long* kept_l = kept_out ? kept_out + level : nullptr;
         if (outside && (level == 1 || coarse)) {
-            if (int rc = tp_eval_march(ctx, f, a, true, level, bg_s, rows.far, N, rows.bg_out, L[level].lam, map, count, eps, segment, ot,
-                                       win_of[level], kept_l, dens, nullptr, 0))
+            if (int rc = tp_eval_march(ctx, f, a, MarchRule{true, eps, segment, 2, rays_d, rows.far, L[level].lam, count}, level, bg_s, N,
+                                       rows.bg_out, map, ot, win_of[level], kept_l, dens, nullptr))
                 return rc;
         } else {
             if (int rc = tp_launch(ctx, ctx->tp[2 + level], sc, views, rays_o, rays_d, viewdirs, bg_s, rows.far, R, N, chunk, rows.bg_out, s, map,
@@ -826,7 +771,7 @@ static int tp_render_marching(neo_ctx* ctx, const TpFrameArgs& a, const neo_tp_l
                 neo::launch_march_init(L[level].lam, map, count, R, value ? ot.lam_c : nullptr, nullptr, value ? ot.value : nullptr, ot.stop,
                                        N, kept_l, N, s);
             if (value)
-                neo::launch_march_advance(true, rows.bg_out, bg_s, N, nullptr, nullptr, ot.lam_c, N, 0, N, segment, 0.0f, nullptr, count, R, 0,
+                neo::launch_march_advance(2, rows.bg_out, bg_s, N, nullptr, nullptr, ot.lam_c, N, 0, N, segment, 0.0f, nullptr, count, R, 0,
                                           nullptr, ot.value, nullptr, ot.stop, s);
         }
         if (so) {

@@ -223,17 +223,21 @@ struct neo_ctx {
     neo_host::DevBuf ws_sets[LANES][14];                          // render workspaces (grow-only), one set per lane
     neo_host::DevBuf* ws = ws_sets[0];                            // the current lane's set
     neo_host::DevBuf boxes;                                       // neo_aabb_multi: box frames + bounds
-    // neo_tp_set_occupancy: the scene's occupancy grid as bits (occupancy.hip: GRID LAYOUT), occ_G = 0: none installed;
+    // An installed occupancy grid (occupancy.hip: GRID LAYOUT): the bits in context-owned memory and their descriptor - G, lo, scale
+    // and the outside policy; grid.bits = bits.p while one is installed, grid.G = 0: none.
+    struct OccInstalled {
+        neo_host::DevBuf bits;
+        neo::OccGrid grid{};
+        const neo::OccGrid* get() const { return grid.G ? &grid : nullptr; }
+        void clear() { grid = neo::OccGrid{}; }
+    };
+    // neo_tp_set_occupancy: the NeO-360 scene's grid over the unit cube;
     // neo_tp_set_skip_window: rays per window of neo_tp_render_skipping (0: the default of api_tp.hip)
-    neo_host::DevBuf occ_bits;
-    int occ_G = 0;
+    OccInstalled occ;
     int skip_window = 0;
-    // neo_vanilla_set_occupancy: the vanilla scene's grid over a caller-given box (vanilla_march.hip: BOX KEEP RULE), vocc_G = 0:
-    // none installed; vocc_scale = (float)G / (hi - lo) per axis, formed once in fp32 on the host.
+    // neo_vanilla_set_occupancy: the vanilla scene's grid over a caller-given box;
     // neo_vanilla_set_march_window: rays per window of neo_vanilla_render_marching (0: the default of vanilla_march.hip)
-    neo_host::DevBuf vocc_bits;
-    int vocc_G = 0, vocc_clip = 0;
-    float vocc_lo[3] = {0.f, 0.f, 0.f}, vocc_scale[3] = {0.f, 0.f, 0.f};
+    OccInstalled vocc;
     int vanilla_window = 0;
     // pillar stage of the scene encoder (neo_enc_*): packed weights, biases (6x512), scorer heads (3x512), workspaces
     neo_host::MlpSlot enc;

@@ -435,14 +435,22 @@ void launch_composite_layers(const float* rgbsigma, const float* t, const float*
 void launch_tp_decompose(const float* rgbsigma, const float* t, const float* weights, const float* near_inst, const float* far_inst,
                          int K, int R, int N, const float* bg_lambda, float* rgb, float* acc, float* depth, int* id, hipStream_t s);
 
-// occupancy.hip - empty-space skipping of neo_tp_render_skipping (include/neo360_hip.h: OCCUPANCY GRID, KEEP RULE)
-// keep (R,N) uint8 = the KEEP RULE at x = rays_o + t rays_d; bits null: everything is kept
-void launch_occ_keep(const float* rays_o, const float* rays_d, const float* t, int R, int N, const uint32_t* bits, int G, uint8_t* keep,
-                     hipStream_t s);
-// One window's compact rows, `cap` of them, in one buffer of occ_rows_bytes(cap): row k is ONE kept point - the origin, direction and
-// t of its ray, the view direction of its quirk-Q1 ray, dst = its point index in the window - and out its (rgb, sigma) row; iota =
-// the identity map of the evaluator's compact launch; count the device word; totals the compaction's per-workgroup sums.  far: the
-// ray's sphere exit, which only the outside-sphere evaluators read (march.hip fills it there; the inside paths leave it alone).
+// occupancy.hip - the occupancy grids of the NeO-360 and the vanilla scene (include/neo360_hip.h: OCCUPANCY GRID, KEEP RULE, BOX GRID)
+// What the KEEP RULE (occ_points.h) does with a point outside the grid's box: the edge cell decides (the unit cube of the NeO-360
+// scene), the point is kept, or the point is skipped (the vanilla box without and with `clip`).
+enum { OCC_CLAMP = 0, OCC_KEEP = 1, OCC_SKIP = 2 };
+// bits (GRID LAYOUT of occupancy.hip) or NULL for "no grid"; G^3 cells, cell = floor((x - lo) scale) per axis, scale formed once in
+// host fp32 (occ_grid_unit / occ_grid_box); travels by value as a kernel argument
+struct OccGrid {
+    const uint32_t* bits;
+    int G;
+    float lo[3], scale[3];
+    int outside;
+};
+// One launch's point rows, `cap` of them, in one buffer of occ_rows_bytes(cap) (march.h: launch_point_list fills them): row k is ONE
+// point - the origin, direction and t of its ray, the view direction of its quirk-Q1 ray, dst = its place in the window's rows - and
+// out its (rgb, sigma) row; iota = the identity map of the evaluator's compact launch; count the device word; totals the
+// compaction's per-workgroup sums.  far: the ray's sphere exit, which only the outside-sphere evaluators read.
 struct OccRows {
     float *out, *o, *d, *v, *t, *far;
     int *dst, *iota, *count, *totals;
@@ -450,13 +458,6 @@ struct OccRows {
 };
 size_t occ_rows_bytes(size_t cap);
 void launch_occ_iota(int* map, int n, hipStream_t s);
-// classify (into keep_win, the window's (rays, N) rows of the mask) and compact the points of rays r0 .. r0 + rays - 1 of R: kept
-// points in ascending point order, *w.count of them, also added to *kept_sum when not null.  Two launches, no atomics.
-void launch_occ_compact(const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_win, int r0, int rays, int R,
-                        int N, int chunk, const uint32_t* bits, int G, uint8_t* keep_win, const OccRows& w, long long* kept_sum,
-                        hipStream_t s);
-// out_win (P,4): w.out at the point's rank where kept, zeros where skipped (w.totals as launch_occ_compact left them)
-void launch_occ_scatter(const uint8_t* keep_win, int P, const OccRows& w, float* out_win, hipStream_t s);
 // sigma (G probes)^3 activated densities -> G^3 / 32 words: any probe > threshold, dilation, unit-sphere clip (sphere = false: none)
 void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s,
                            bool sphere = true);

@@ -1,25 +1,21 @@
-// The segmented march of the NeO-360 frame (neo_tp_render_terminating / _accelerated / _marching): a ray's march through a region
-// stops at the first SEGMENT boundary at which its running value has fallen below eps (include/neo360_hip.h: STOP RULE inside the
-// sphere, OUTSIDE STOP RULE outside).  This file holds everything but the driver (tp_eval_march, api_tp.hip); march.h has the table
-// of what differs between the two regions.  A ROW is a dense ray inside the sphere and a compact background row of the culled frame
-// outside (row k belongs to ray map[k], the survivor count is a device word).
+// The segmented march of a level (the NeO-360 frames neo_tp_render_terminating / _accelerated / _marching and the vanilla frame
+// neo_vanilla_render_marching): a row's march stops at the first SEGMENT boundary at which its running value has fallen below eps
+// (include/neo360_hip.h: STOP RULE inside the sphere, OUTSIDE STOP RULE outside, composite mode 0 for vanilla).  This file holds
+// the kernels around the point list (point_list.hip); the loop that drives them is march_level (march.h, with the table of what
+// differs between the users).  A ROW is a dense ray, or outside the sphere a compact background row of the culled frame (row k
+// belongs to ray map[k], the survivor count is a device word).
 //
 //   k_march_init          per level: alive 1, stop 0 (or N for a level that does not follow the rule), outside also lam_c = the
 //                         level's lambda of the row's ray - and dead rows behind the count; the kept count;
-//   k_march_emit          the point rows of one segment of the ALIVE rows of one window (the alive rows come from launch_cull_compact
-//                         on the running value: ascending order, the count in a device word);
 //   k_march_scatter       compact (rgb, sigma) rows to their place in the zero-filled rows of the level;
 //   k_march_advance       the stop rule: one wave per alive row over the segment's rows continues k_composite's own transmittance
 //                         product (composite_round.h) from the row's fp64 carry;
 //   k_march_by_slot       stop / value of compact rows back behind their rays, 0 for a ray without a slot;
 //   k_march_rows_by_slot  the same for whole rows (the bg_s and bg_rows copies of a culled frame).
 //
-// A segment's work is proportional to the segment: emit, the evaluator, scatter and advance touch (alive rows) x (segment) points,
-// never the whole row.  No atomics, no spinning: every count is a device word written by one thread behind its producers in stream
-// order.  A point row is ONE point, as in occupancy.hip: the evaluator's compact launch with N = 1 and the identity map takes the
-// view direction of row `row` itself, so emit writes the view direction of the quirk-Q1 ray of the DENSE launch of the level's full
-// N, c0 + ((ray - c0) N + j) mod bc on the dense ray index (k_occ_emit's expression), and - its point_setup_row reads far[row] -
-// outside the ray's far.  The evaluator sources are not touched.
+// A segment's work is proportional to the segment: the point list, the evaluator, scatter and advance touch (alive rows) x
+// (segment) points, never the whole row.  No atomics, no spinning: every count is a device word written by one thread behind its
+// producers in stream order.
 #include "common.h"
 #include "composite_round.h"
 #include "march.h"
@@ -43,44 +39,9 @@ __global__ void k_march_init(const float* __restrict__ lam, const int* __restric
         if (lam_c) lam_c[k] = live ? lam[map[k]] : 0.0f;
         if (alive) alive[k] = live ? 1.0f : -1.0f;      // -1 < eps for every eps >= 0: a row behind the count never marches
         if (value) value[k] = 0.0f;
-        stop[k] = live ? stop_value : 0;
+        if (stop) stop[k] = live ? stop_value : 0;
     }
     if (k == 0 && kept) *kept = kept_per_row * (long long)n;
-}
-
-// One window (rows first .. of the frame's R), one segment (samples b0 .. b0 + len - 1 of the level's N): point row kk len + jj is
-// sample b0 + jj of row first + map_w[kk], kk < *count_w.  Thread 0 writes the row count and adds it to *kept_sum (behind the
-// previous segment in stream order: no atomic).
-__global__ __launch_bounds__(256) void k_march_emit(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                                                    const float* __restrict__ viewdirs, const float* __restrict__ far,
-                                                    const float* __restrict__ pos, long stride, const int* __restrict__ map,
-                                                    const int* __restrict__ map_w, const int* __restrict__ count_w, int first, int R,
-                                                    int N, int b0, int len, int chunk, float* __restrict__ c_o,
-                                                    float* __restrict__ c_d, float* __restrict__ c_v, float* __restrict__ c_t,
-                                                    float* __restrict__ c_far, int* __restrict__ dst, int* __restrict__ rows,
-                                                    long long* __restrict__ kept_sum) {
-    const int alive = *count_w;
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p == 0) {
-        *rows = alive * len;
-        if (kept_sum) *kept_sum = *kept_sum + (long long)alive * len;
-    }
-    if (p >= (long)alive * len) return;
-    const int kk = (int)(p / len), j = b0 + (int)(p - (long)kk * len);
-    const int row = first + map_w[kk];
-    const int ray = map ? map[row] : row;
-    const int c0 = (ray / chunk) * chunk;
-    const int bc = min(chunk, R - c0);
-    const int dray = c0 + (int)(((long)(ray - c0) * N + j) % bc);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        c_o[p * 3 + a] = rays_o[(long)ray * 3 + a];
-        c_d[p * 3 + a] = rays_d[(long)ray * 3 + a];
-        c_v[p * 3 + a] = viewdirs[(long)dray * 3 + a];
-    }
-    c_t[p] = pos[(long)row * stride + j];
-    if (far) c_far[p] = far[ray];
-    dst[p] = row * N + j;
 }
 
 __global__ __launch_bounds__(256) void k_march_scatter(const float4* __restrict__ c_out, const int* __restrict__ dst,
@@ -174,32 +135,15 @@ void launch_march_init(const float* lam, const int* map, const int* count, int R
                            kept, kept_per_row);
 }
 
-void launch_march_emit(const float* rays_o, const float* rays_d, const float* viewdirs, const float* far, const float* pos, long stride,
-                       const int* map, const int* map_w, const int* count_w, int first, int rows, int R, int N, int b0, int len, int chunk,
-                       const OccRows& w, long long* kept_sum, hipStream_t s) {
-    const long P = (long)rows * len;
-    if (P <= 0) return;
-    hipLaunchKernelGGL(k_march_emit, dim3((int)((P + 255) / 256)), dim3(256), 0, s, rays_o, rays_d, viewdirs, far, pos, stride, map,
-                       map_w, count_w, first, R, N, b0, len, chunk, w.o, w.d, w.v, w.t, w.far, w.dst, w.count, kept_sum);
-}
-
 void launch_march_scatter(const OccRows& w, long P, float* out, hipStream_t s) {
     if (P <= 0) return;
     hipLaunchKernelGGL(k_march_scatter, dim3((int)((P + 255) / 256)), dim3(256), 0, s, (const float4*)w.out, (const int*)w.dst,
                        (const int*)w.count, (float4*)out);
 }
 
-void launch_march_advance(bool outside, const float* rgbsigma, const float* pos, long stride, const float* rays_d, const float* t_far,
+void launch_march_advance(int mode, const float* rgbsigma, const float* pos, long stride, const float* rays_d, const float* t_far,
                           const float* lam_c, int N, int b0, int b_end, int segment, float eps, const int* map_w, const int* count_w,
                           int n_rows, int first, double* carry, float* value, float* alive, int* stop, hipStream_t s) {
-    launch_march_advance_mode(outside ? 2 : 1, rgbsigma, pos, stride, rays_d, t_far, lam_c, N, b0, b_end, segment, eps, map_w, count_w,
-                              n_rows, first, carry, value, alive, stop, s);
-}
-
-void launch_march_advance_mode(int mode, const float* rgbsigma, const float* pos, long stride, const float* rays_d, const float* t_far,
-                               const float* lam_c, int N, int b0, int b_end, int segment, float eps, const int* map_w,
-                               const int* count_w, int n_rows, int first, double* carry, float* value, float* alive, int* stop,
-                               hipStream_t s) {
     if (n_rows <= 0) return;
     hipLaunchKernelGGL(mode == 2 ? k_march_advance<2> : mode == 1 ? k_march_advance<1> : k_march_advance<0>,
                        dim3((n_rows + MARCH_ROWS_PER_BLOCK - 1) / MARCH_ROWS_PER_BLOCK), dim3(256), 0, s, (const float4*)rgbsigma, pos,
@@ -232,8 +176,8 @@ int march_stops(neo_ctx* ctx, int mode, bool ptrs, const float* rgbsigma, const 
     REQUIRE(segment >= 64 && segment % 64 == 0, "segment must be a positive multiple of 64");
     if (R == 0) return NEO_OK;
     REQUIRE(ptrs, "null pointer");
-    neo::launch_march_advance_mode(mode, rgbsigma, pos, N, rays_d, t_far, lam, N, 0, N, segment, eps, nullptr, nullptr, R, 0, nullptr,
-                                   value, nullptr, stop, static_cast<hipStream_t>(stream));
+    neo::launch_march_advance(mode, rgbsigma, pos, N, rays_d, t_far, lam, N, 0, N, segment, eps, nullptr, nullptr, R, 0, nullptr, value,
+                              nullptr, stop, static_cast<hipStream_t>(stream));
     return check_launch();
 }
 

@@ -1,11 +1,13 @@
-// What the point compactions of occupancy.hip (k_occ_keep / k_occ_emit / k_occ_scatter), accelerate.hip (k_acc_keep / k_acc_emit) and
-// vanilla_march.hip (k_vm_keep / k_vm_emit) share: the KEEP RULE of one point over the unit cube, the per-workgroup totals and the
-// rank of a kept point among the kept points in front of it - and, for the two vanilla files (vanilla_march.hip and the training row
-// builder of vanilla_train_march.hip), the BOX GRID's cell rule.  Included by those files only; everything here has internal linkage.
+// The KEEP RULE of one point over an occupancy grid and the compaction of kept points (point_list.hip builds the point rows of the
+// NeO-360 and the vanilla frames with them, vanilla_train_march.hip its training rows): the rule, the host helpers that fill a grid
+// descriptor, the per-workgroup totals and the rank of a kept point among the kept points in front of it.  The descriptor itself,
+// OccGrid with its OCC_* outside policies, is declared in kernels.h, because the context (ctx.h) holds one per installed grid and
+// the launch wrappers take it.  Everything here has internal linkage.
 #pragma once
 #include <cmath>
 
 #include "common.h"
+#include "kernels.h"      // OccGrid
 
 namespace neo {
 
@@ -16,63 +18,53 @@ constexpr int OCC_ROUNDS = 4;
 constexpr int OCC_POINTS = OCC_BLOCK * OCC_ROUNDS;      // points per workgroup
 constexpr int OCC_SEGS = OCC_POINTS / 64;               // 64-point segments per workgroup, in point order
 
-// i = min(max((int)floorf((x + 1) (G / 2)), 0), G - 1), clamped before the conversion (the same value for every finite x)
-__device__ __forceinline__ int occ_cell(float x, int G) {
-    float c = floorf((x + 1.0f) * (0.5f * (float)G));
-    c = c > 0.0f ? c : 0.0f;
-    c = c < (float)(G - 1) ? c : (float)(G - 1);
-    return (int)c;
-}
-
-// KEEP RULE: a set cell, a non-finite coordinate (the negation of `<`, as cull_keep: a NaN survives to the caller) or no grid
-__device__ __forceinline__ bool occ_keep_point(const uint32_t* __restrict__ bits, int G, const float* __restrict__ o,
-                                               const float* __restrict__ d, float tv) {
+// KEEP RULE of the point x = o + t d (mul then add, as the evaluators).  In this order: a non-finite coordinate is kept (the
+// negation of `<`, as cull_keep: a NaN survives to the caller); no grid keeps; then the cell floorf((x - lo) scale) per axis - for
+// the unit cube (x + 1) (G / 2) bit for bit - decides: outside [0, G) (an overflow to inf included) OCC_CLAMP takes the edge cell,
+// clamped before the conversion to int, OCC_KEEP keeps and OCC_SKIP skips; inside, the cell's bit.
+__device__ __forceinline__ bool occ_keep(const OccGrid& g, const float* __restrict__ o, const float* __restrict__ d, float tv) {
     float x[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) x[a] = o[a] + tv * d[a];
     if (!(fabsf(x[0]) < __builtin_inff()) || !(fabsf(x[1]) < __builtin_inff()) || !(fabsf(x[2]) < __builtin_inff())) return true;
-    if (!bits) return true;
-    const int lin = (occ_cell(x[0], G) * G + occ_cell(x[1], G)) * G + occ_cell(x[2], G);
-    return (bits[lin >> 5] >> (lin & 31)) & 1u;
-}
-
-// BOX GRID (include/neo360_hip.h): bits (GRID LAYOUT of occupancy.hip) or NULL for "no grid"; scale_a = (float)G / (hi_a - lo_a),
-// host fp32
-struct VmBox {
-    const uint32_t* bits;
-    int G, clip;
-    float lo[3], scale[3];
-};
-
-// BOX KEEP RULE: a non-finite coordinate (the negation of `<`: a NaN survives), no grid, outside the box without clip, or a set cell
-__device__ __forceinline__ bool vm_keep_point(const VmBox& b, const float* __restrict__ o, const float* __restrict__ d, float tv) {
-    float x[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = o[a] + tv * d[a];      // mul then add, as the evaluators
-    if (!(fabsf(x[0]) < __builtin_inff()) || !(fabsf(x[1]) < __builtin_inff()) || !(fabsf(x[2]) < __builtin_inff())) return true;
-    if (!b.bits) return true;
+    if (!g.bits) return true;
     int c[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float cf = floorf((x[a] - b.lo[a]) * b.scale[a]);
-        if (!(cf >= 0.0f && cf < (float)b.G)) return b.clip == 0;      // outside (an overflow to inf included)
+        float cf = floorf((x[a] - g.lo[a]) * g.scale[a]);
+        if (g.outside == OCC_CLAMP) {
+            cf = cf > 0.0f ? cf : 0.0f;
+            cf = cf < (float)(g.G - 1) ? cf : (float)(g.G - 1);
+        } else if (!(cf >= 0.0f && cf < (float)g.G)) {
+            return g.outside == OCC_KEEP;
+        }
         c[a] = (int)cf;
     }
-    const int lin = (c[0] * b.G + c[1]) * b.G + c[2];
-    return (b.bits[lin >> 5] >> (lin & 31)) & 1u;
+    const int lin = (c[0] * g.G + c[1]) * g.G + c[2];
+    return (g.bits[lin >> 5] >> (lin & 31)) & 1u;
 }
 
-inline bool vm_resolution_ok(int G) { return G == 8 || G == 16 || (G >= 32 && G <= 256 && G % 32 == 0); }
+inline bool occ_resolution_ok(int G) { return G == 8 || G == 16 || (G >= 32 && G <= 256 && G % 32 == 0); }
+constexpr const char* OCC_RESOLUTION_MSG = "occupancy resolution must be 8, 16 or a multiple of 32 in [32, 256]";
 
-// lo < hi, both finite, and a finite positive scale per axis; fills box.lo / box.scale
-inline const char* vm_box_from(int G, const float* lo, const float* hi, VmBox& box) {
+// the unit cube [-1, 1]^3: lo = -1, scale = G / 2, the edge cell outside
+inline OccGrid occ_grid_unit(const uint32_t* bits, int G) {
+    const float h = 0.5f * static_cast<float>(G);
+    return {bits, G, {-1.0f, -1.0f, -1.0f}, {h, h, h}, OCC_CLAMP};
+}
+
+// a caller's box: lo < hi, both finite, and a finite positive scale (float)G / (hi - lo) per axis; fills G, lo, scale and the
+// policy of `clip` (bits stay the caller's).  Returns the message of the failing check, or NULL.
+inline const char* occ_grid_box(int G, const float* lo, const float* hi, int clip, OccGrid& out) {
     for (int a = 0; a < 3; ++a) {
         if (!(std::fabs(lo[a]) < INFINITY) || !(std::fabs(hi[a]) < INFINITY) || !(lo[a] < hi[a])) return "the box needs finite lo < hi on every axis";
         const float scale = static_cast<float>(G) / (hi[a] - lo[a]);
         if (!(scale > 0.0f && scale < INFINITY)) return "the box is too thin or too wide for fp32 cell arithmetic";
-        box.lo[a] = lo[a];
-        box.scale[a] = scale;
+        out.lo[a] = lo[a];
+        out.scale[a] = scale;
     }
+    out.G = G;
+    out.outside = clip ? OCC_SKIP : OCC_KEEP;
     return nullptr;
 }
 

@@ -1,112 +1,23 @@
-// Empty-space skipping of the NeO-360 frame (neo_tp_render_skipping): a per-scene occupancy grid over the world cube [-1, 1]^3
-// decides, SAMPLE by sample, which inside-sphere points the evaluators see.  This file holds everything but the driver
-// (tp_eval_skipping, api_tp.hip):
+// The occupancy grids: a per-scene grid over the world cube [-1, 1]^3 (NeO-360, neo_tp_set_occupancy) or over a caller-given box
+// (vanilla, neo_vanilla_set_occupancy) decides, SAMPLE by sample, which points the evaluators see.  The rule of one point and the
+// compaction are occ_points.h's, the point rows point_list.hip's, the loop march_level's (march.h).  This file holds
 //
-//   k_occ_keep          the classifier: x = o + t d (point_setup_row's expression, this library's -ffp-contract=off), the cell of x,
-//                       one bit of the grid -> a uint8 keep mask over dense (R, N) rows; with `totals` also the kept points of every
-//                       workgroup (the first launch of the compaction);
-//   k_occ_emit          the second launch of the compaction: the compact rows of the kept points of one WINDOW of rays;
-//   k_occ_scatter       compact (rgb, sigma) rows back to their dense place, zeros where a sample was skipped;
-//   k_occ_from_sigma    a lattice of activated densities -> the bits of a grid (threshold, dilation, unit-sphere clip).
+//   the installation    one helper behind both set_occupancy entry points: the bits into context-owned memory, the descriptor beside;
+//   the pure functions  neo_tp_occupancy_keep / neo_vanilla_occupancy_keep, the KEEP RULE on caller rows (launch_point_keep);
+//   k_occ_from_sigma    a lattice of activated densities -> the bits of a grid (threshold, dilation, unit-sphere clip);
+//   OccRows             the carving of one launch's point rows.
 //
 // GRID LAYOUT (include/neo360_hip.h: OCCUPANCY GRID).  Cell (ix, iy, iz) is bit lin & 31 of the 32-bit word lin >> 5,
 // lin = (ix G + iy) G + iz: G^3 / 32 words, iz fastest, the order of a contiguous bool (G, G, G) tensor.
-//
-// COMPACTION.  The totals / emit scheme of compact.h on POINTS: no atomics, no spinning on other workgroups, survivors in ascending
-// point order p = r N + j of the window, identically on every run.  A workgroup owns 1024 consecutive points (4 rounds of 256
-// threads, one ballot per wave and round: 16 segments of 64 points in LDS), and emit sums the totals of the workgroups in front of
-// it as compact.h does.  That sum is linear in the workgroups of ONE window, and the driver keeps windows small: at its default of
-// 4096 rays a level-1 window of the 129 + 385 frame is 1540 workgroups, 1.2 M integer reads per window for all of them together -
-// no hierarchical scan is needed at that size.
-//
-// A compact row is ONE point: the evaluator's compact launch with N = 1 and the identity map forms x = o[row] + t[row] d[row] and
-// takes the view direction of row `row` itself (point_setup_row: c0 + ((row - c0) 1 + 0) mod bc = row), so emit writes, per kept
-// point, the origin and direction of its ray, its t, and the view direction of the quirk-Q1 ray of the DENSE launch,
-// c0 + ((r - c0) N + j) mod bc.  The evaluator sources are not touched.
 #include "common.h"
+#include "march.h"
 #include "occ_points.h"
-#include "tp_frame.h"
 
 using namespace neo_host;
 
 namespace neo {
 
 namespace {
-
-// the workgroup layout, occ_cell, occ_keep_point (the KEEP RULE) and occ_rank: occ_points.h, shared with accelerate.hip
-
-// rays_o / rays_d: row 0 is the ray of point 0; t, keep: P = rays x N points.  totals (may be null): kept points per workgroup.
-__global__ __launch_bounds__(OCC_BLOCK) void k_occ_keep(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                                                        const float* __restrict__ t, int P, int N,
-                                                        const uint32_t* __restrict__ bits, int G, uint8_t* __restrict__ keep,
-                                                        int* __restrict__ totals) {
-    __shared__ int s_seg[OCC_SEGS];
-    bool k[OCC_ROUNDS];
-#pragma unroll
-    for (int it = 0; it < OCC_ROUNDS; ++it) {
-        const int p = blockIdx.x * OCC_POINTS + it * OCC_BLOCK + threadIdx.x;
-        k[it] = false;
-        if (p < P) {
-            const int r = p / N;
-            k[it] = occ_keep_point(bits, G, rays_o + (long)r * 3, rays_d + (long)r * 3, t[p]);
-            keep[p] = k[it] ? 1 : 0;
-        }
-    }
-    if (totals) occ_total(k, s_seg, totals);
-}
-
-// One window: rays r0 .. r0 + P / N - 1 of the frame's R rays; t and keep are the window's rows.  Per kept point p = r_w N + j:
-// c_o, c_d = the ray's origin and direction, c_v = the view direction of ray c0 + ((r - c0) N + j) mod bc (r = r0 + r_w, c0 and bc
-// the reference chunk of r: the `chunk` arithmetic of point_setup_row), c_t = t, dst = p.  The last workgroup writes the count and
-// adds it to *kept_sum (one thread, behind the previous window in stream order: no atomic).
-__global__ __launch_bounds__(OCC_BLOCK) void k_occ_emit(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                                                        const float* __restrict__ viewdirs, const float* __restrict__ t,
-                                                        const uint8_t* __restrict__ keep, int r0, int R, int P, int N, int chunk,
-                                                        const int* __restrict__ totals, float* __restrict__ c_o,
-                                                        float* __restrict__ c_d, float* __restrict__ c_v, float* __restrict__ c_t,
-                                                        int* __restrict__ dst, int* __restrict__ count,
-                                                        long long* __restrict__ kept_sum) {
-    __shared__ int s_part[OCC_BLOCK / 64];
-    __shared__ int s_seg[OCC_SEGS];
-    const OccRank rk = occ_rank(keep, P, totals, s_part, s_seg);
-#pragma unroll
-    for (int it = 0; it < OCC_ROUNDS; ++it) {
-        if (!rk.kept[it]) continue;
-        const int p = blockIdx.x * OCC_POINTS + it * OCC_BLOCK + threadIdx.x;
-        const int k = rk.k[it];
-        const int rw = p / N, j = p - rw * N;
-        const int ray = r0 + rw;
-        const int c0 = (ray / chunk) * chunk;
-        const int bc = min(chunk, R - c0);
-        const int dray = c0 + ((ray - c0) * N + j) % bc;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            c_o[(long)k * 3 + a] = rays_o[(long)ray * 3 + a];
-            c_d[(long)k * 3 + a] = rays_d[(long)ray * 3 + a];
-            c_v[(long)k * 3 + a] = viewdirs[(long)dray * 3 + a];
-        }
-        c_t[k] = t[p];
-        dst[k] = p;
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        *count = rk.upto;
-        if (kept_sum) *kept_sum = *kept_sum + (long long)rk.upto;
-    }
-}
-
-// dense row p of the window: the compact row of its rank where kept, (0, 0, 0, 0) where skipped
-__global__ __launch_bounds__(OCC_BLOCK) void k_occ_scatter(const uint8_t* __restrict__ keep, int P, const int* __restrict__ totals,
-                                                           const float4* __restrict__ c_out, float4* __restrict__ out) {
-    __shared__ int s_part[OCC_BLOCK / 64];
-    __shared__ int s_seg[OCC_SEGS];
-    const OccRank rk = occ_rank(keep, P, totals, s_part, s_seg);
-#pragma unroll
-    for (int it = 0; it < OCC_ROUNDS; ++it) {
-        const int p = blockIdx.x * OCC_POINTS + it * OCC_BLOCK + threadIdx.x;
-        if (p >= P) continue;
-        out[p] = rk.kept[it] ? c_out[rk.k[it]] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
 
 __global__ void k_occ_iota(int* __restrict__ map, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -155,32 +66,8 @@ void OccRows::carve(void* base, size_t cap) {
 }
 size_t occ_rows_bytes(size_t cap) { return cap * 68 + (1 + (size_t)occ_blocks((long)cap)) * sizeof(int); }
 
-void launch_occ_keep(const float* rays_o, const float* rays_d, const float* t, int R, int N, const uint32_t* bits, int G, uint8_t* keep,
-                     hipStream_t s) {
-    if (R <= 0 || N <= 0) return;
-    const int P = R * N;
-    hipLaunchKernelGGL(k_occ_keep, dim3(occ_blocks(P)), dim3(OCC_BLOCK), 0, s, rays_o, rays_d, t, P, N, bits, G, keep, (int*)nullptr);
-}
-
 void launch_occ_iota(int* map, int n, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_occ_iota, dim3((n + 255) / 256), dim3(256), 0, s, map, n);
-}
-
-void launch_occ_compact(const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_win, int r0, int rays, int R,
-                        int N, int chunk, const uint32_t* bits, int G, uint8_t* keep_win, const OccRows& w, long long* kept_sum,
-                        hipStream_t s) {
-    if (rays <= 0) return;
-    const int P = rays * N, nb = occ_blocks(P);
-    hipLaunchKernelGGL(k_occ_keep, dim3(nb), dim3(OCC_BLOCK), 0, s, rays_o + (size_t)r0 * 3, rays_d + (size_t)r0 * 3, t_win, P, N, bits,
-                       G, keep_win, w.totals);
-    hipLaunchKernelGGL(k_occ_emit, dim3(nb), dim3(OCC_BLOCK), 0, s, rays_o, rays_d, viewdirs, t_win, (const uint8_t*)keep_win, r0, R, P,
-                       N, chunk, (const int*)w.totals, w.o, w.d, w.v, w.t, w.dst, w.count, kept_sum);
-}
-
-void launch_occ_scatter(const uint8_t* keep_win, int P, const OccRows& w, float* out_win, hipStream_t s) {
-    if (P <= 0) return;
-    hipLaunchKernelGGL(k_occ_scatter, dim3(occ_blocks(P)), dim3(OCC_BLOCK), 0, s, keep_win, P, (const int*)w.totals,
-                       (const float4*)w.out, (float4*)out_win);
 }
 
 void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, hipStream_t s,
@@ -193,28 +80,52 @@ void launch_occ_from_sigma(const float* sigma, int G, int probes, float threshol
 
 namespace {
 
-bool occ_resolution_ok(int G) { return G == 8 || G == 16 || (G >= 32 && G <= 256 && G % 32 == 0); }
+using neo::occ_resolution_ok;      // occ_points.h
+using neo::OCC_RESOLUTION_MSG;
+
+// copies into context-owned memory that the frame calls read: an exclusive call, ordered across streams.  bits NULL removes the
+// grid; desc: the validated descriptor of the new one (its bits are replaced by the context's copy)
+int set_occupancy(neo_ctx* ctx, neo_ctx::OccInstalled& to, const uint32_t* bits, const neo::OccGrid& desc, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ORDERED(ctx, s);
+    to.clear();
+    if (!bits) return NEO_OK;
+    const size_t bytes = static_cast<size_t>(desc.G) * desc.G * desc.G / 8;
+    if (to.bits.reserve(bytes)) return NEO_ERR_NOMEM;
+    HIP_TRY(hipMemcpyAsync(to.bits.p, bits, bytes, hipMemcpyDeviceToDevice, s));
+    to.grid = desc;
+    to.grid.bits = to.bits.as<uint32_t>();
+    return NEO_OK;
+}
+
+// the KEEP RULE on caller rows (R,N): touches no context-owned memory, no ordering scope (as neo_tp_edit_rows)
+int occupancy_keep(const neo::OccGrid& grid, const float* rays_o, const float* dirs, const float* t, int R, int N, uint8_t* keep,
+                   void* stream) {
+    if (R == 0) return NEO_OK;
+    REQUIRE(rays_o && dirs && t && keep, "null pointer");
+    neo::launch_point_keep(neo::point_source_dense(rays_o, dirs, t, N, R, N), grid, keep, nullptr, static_cast<hipStream_t>(stream));
+    return check_launch();
+}
 
 }  // namespace
 
 extern "C" {
 
-// copies into context-owned memory that the frame calls read: an exclusive call, ordered across streams
 int neo_tp_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, void* stream) {
     ENTER(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    ORDERED(ctx, s);
-    if (!bits) {
-        ctx->occ_G = 0;
-        return NEO_OK;
+    REQUIRE(!bits || occ_resolution_ok(G), OCC_RESOLUTION_MSG);
+    return set_occupancy(ctx, ctx->occ, bits, neo::occ_grid_unit(bits, G), stream);
+}
+
+int neo_vanilla_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, const float* lo, const float* hi, int clip, void* stream) {
+    ENTER(ctx);
+    neo::OccGrid box{};
+    if (bits) {
+        REQUIRE(occ_resolution_ok(G), OCC_RESOLUTION_MSG);
+        REQUIRE(lo && hi, "null pointer");
+        if (const char* msg = neo::occ_grid_box(G, lo, hi, clip, box)) return fail(NEO_ERR_INVALID, "%s", msg);
     }
-    REQUIRE(occ_resolution_ok(G), "occupancy resolution must be 8, 16 or a multiple of 32 in [32, 256]");
-    const size_t bytes = static_cast<size_t>(G) * G * G / 8;
-    ctx->occ_G = 0;
-    if (ctx->occ_bits.reserve(bytes)) return NEO_ERR_NOMEM;
-    HIP_TRY(hipMemcpyAsync(ctx->occ_bits.p, bits, bytes, hipMemcpyDeviceToDevice, s));
-    ctx->occ_G = G;
-    return NEO_OK;
+    return set_occupancy(ctx, ctx->vocc, bits, box, stream);
 }
 
 int neo_tp_set_skip_window(neo_ctx* ctx, int rays) {
@@ -224,17 +135,28 @@ int neo_tp_set_skip_window(neo_ctx* ctx, int rays) {
     return NEO_OK;
 }
 
-// the pure function k_occ_keep on caller rows; touches no context-owned memory: no ordering scope (as neo_tp_edit_rows)
 int neo_tp_occupancy_keep(neo_ctx* ctx, const uint32_t* bits, int G, const float* rays_o, const float* rays_d, const float* t, int R,
                           int N, uint8_t* keep, void* stream) {
     ENTER(ctx);
     REQUIRE(R >= 0 && N >= 1, "bad shape");
     REQUIRE(static_cast<long>(R) * N <= 2147483647L - 1024, "too many points for 32-bit indices");
-    REQUIRE(!bits || occ_resolution_ok(G), "occupancy resolution must be 8, 16 or a multiple of 32 in [32, 256]");
-    if (R == 0) return NEO_OK;
-    REQUIRE(rays_o && rays_d && t && keep, "null pointer");
-    neo::launch_occ_keep(rays_o, rays_d, t, R, N, bits, G, keep, static_cast<hipStream_t>(stream));
-    return check_launch();
+    REQUIRE(!bits || occ_resolution_ok(G), OCC_RESOLUTION_MSG);
+    return occupancy_keep(neo::occ_grid_unit(bits, G), rays_o, rays_d, t, R, N, keep, stream);
+}
+
+int neo_vanilla_occupancy_keep(neo_ctx* ctx, const uint32_t* bits, int G, const float* lo, const float* hi, int clip,
+                               const float* rays_o, const float* dirs, const float* t, int R, int N, uint8_t* keep, void* stream) {
+    ENTER(ctx);
+    REQUIRE(R >= 0 && N >= 1, "bad shape");
+    REQUIRE(static_cast<long>(R) * N <= 2147483647L - 1024, "too many points for 32-bit indices");
+    neo::OccGrid box{};
+    if (bits) {
+        REQUIRE(occ_resolution_ok(G), OCC_RESOLUTION_MSG);
+        REQUIRE(lo && hi, "null pointer");
+        if (const char* msg = neo::occ_grid_box(G, lo, hi, clip, box)) return fail(NEO_ERR_INVALID, "%s", msg);
+        box.bits = bits;
+    }
+    return occupancy_keep(box, rays_o, dirs, t, R, N, keep, stream);
 }
 
 }  // extern "C"
@@ -245,7 +167,7 @@ namespace {
 int occ_from_sigma(neo_ctx* ctx, const float* sigma, int G, int probes, float threshold, int dilate, uint32_t* bits, bool sphere,
                    void* stream) {
     ENTER(ctx);
-    REQUIRE(occ_resolution_ok(G), "occupancy resolution must be 8, 16 or a multiple of 32 in [32, 256]");
+    REQUIRE(occ_resolution_ok(G), OCC_RESOLUTION_MSG);
     REQUIRE(probes >= 1 && probes <= 4, "1 .. 4 probes per cell and axis");
     REQUIRE(dilate >= 0 && dilate <= 4, "dilation of 0 .. 4 cells");
     REQUIRE(!(threshold != threshold), "the density threshold is NaN");

@@ -10,7 +10,7 @@
 // neo_tp_render_culled, neo_tp_render_terminating, neo_tp_render_accelerated and neo_tp_render_marching share one driver of their own,
 // tp_render_marching in api_tp.hip, with a launch order of its own - the foreground of both levels first, then the background on the
 // rays that still let light through; it takes the preamble and the dense row layout only.  Where a level marches, the driver calls
-// tp_eval_march (one window x segment loop for both regions; march.h has the region table).
+// tp_eval_march, a call of the one window x segment loop march_level (march.h, with the region table).
 #pragma once
 #include "ctx.h"
 
@@ -94,8 +94,8 @@ struct TpDenseOptions {
     const neo_tp_decomposed_out* decomposed[2] = {nullptr, nullptr};      // k_tp_decompose behind the inside-sphere composite
     int K_dec = 0;
     const neo_tp_edit_samples* samples[2] = {nullptr, nullptr};          // copies of the level's sample rows and scene weights
-    // skipping (occupancy.hip): the inside-sphere launch of each level becomes, per window of rays, classify + compact, one compact
-    // launch of single points, scatter; fg_keep / fg_rows (may be null): the level's keep mask (R,N) and rgb/sigma rows (R,N,4);
+    // skipping (tp_eval_skipping: march_level without a stop rule): the inside-sphere launch of each level becomes, per window of
+    // rays, the point list (classify + compact), one compact launch of single points, scatter; fg_keep / fg_rows (may be null): the level's keep mask (R,N) and rgb/sigma rows (R,N,4);
     // kept (may be null): int64[2] on the device, the kept points per level
     bool skip = false;
     uint8_t* fg_keep[2] = {nullptr, nullptr};

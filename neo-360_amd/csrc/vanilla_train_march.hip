@@ -1,9 +1,10 @@
 // Training through the vanilla occupancy grid (include/neo360_hip.h: VANILLA MARCHING TRAINING).  The training chain
 // neo_vanilla_mlp_train_forward / _backward works on arbitrary rows, each with its own cond; what this file adds around it:
 //
-//   k_vt_keep / k_vt_rows   the compact row builder: the BOX KEEP RULE over the (R,N) samples of one level, and for the kept ones -
-//                           in ascending flat order, by the two-launch compaction of occ_points.h - their flat index, their 63-d
-//                           position encoding (k_pos_enc's per-feature expression) and their ray's direction encoding;
+//   k_vt_rows               the compact row builder: behind the keep mask and totals of the (R,N) samples of one level (the BOX
+//                           KEEP RULE, launch_point_keep of point_list.hip), for the kept ones - in ascending flat order, by
+//                           occ_rank - their flat index, their 63-d position encoding (k_pos_enc's per-feature expression) and
+//                           their ray's direction encoding;
 //   k_vt_scatter / _bwd     the output activations (neo_tp_activate's expressions) fused with the scatter into the composite's
 //                           zero-filled (R N, 4) rows, and the gather + activation backward;
 //   k_vt_probes             one jittered probe point per cell of the BOX GRID, from the library's counter-based generator;
@@ -14,6 +15,7 @@
 // store), not as 252-byte strided rows per thread.  No atomics, no spinning; the results do not depend on the launch geometry.
 #include "common.h"
 #include "ctx.h"
+#include "march.h"
 #include "occ_points.h"
 #include "philox.h"
 
@@ -25,24 +27,6 @@ namespace {
 
 constexpr int VT_PE = 63, VT_COND = 27;      // pos_enc(x, 0, 10) of a 3-d point, pos_enc(d, 0, 4) of a direction
 constexpr uint32_t VT_PROBE_STREAM = 8;      // streams 0..7 are the samplers' (training.py: _draws); 8, 9, 10 = the probe's x, y, z
-
-__global__ __launch_bounds__(OCC_BLOCK) void k_vt_keep(const float* __restrict__ rays_o, const float* __restrict__ dirs,
-                                                       const float* __restrict__ t, int N, int P, VmBox box,
-                                                       uint8_t* __restrict__ keep, int* __restrict__ totals) {
-    __shared__ int s_seg[OCC_SEGS];
-    bool k[OCC_ROUNDS];
-#pragma unroll
-    for (int it = 0; it < OCC_ROUNDS; ++it) {
-        const int p = blockIdx.x * OCC_POINTS + it * OCC_BLOCK + threadIdx.x;
-        k[it] = false;
-        if (p < P) {
-            const int ray = p / N;
-            k[it] = vm_keep_point(box, rays_o + (long)ray * 3, dirs + (long)ray * 3, t[p]);
-            keep[p] = k[it] ? 1 : 0;
-        }
-    }
-    occ_total(k, s_seg, totals);
-}
 
 __global__ __launch_bounds__(OCC_BLOCK) void k_vt_rows(const float* __restrict__ rays_o, const float* __restrict__ dirs,
                                                        const float* __restrict__ t, const float* __restrict__ dir_enc,
@@ -151,12 +135,12 @@ int neo_vanilla_train_rows(neo_ctx* ctx, const uint32_t* bits, int G, const floa
     REQUIRE(R >= 0 && N >= 1 && cap >= 0, "bad shape");
     REQUIRE(static_cast<long>(R) * N <= 2147483647L - 1024, "too many points for 32-bit indices");
     REQUIRE(count, "null pointer");
-    neo::VmBox box{};
+    neo::OccGrid box{};
     if (bits) {
-        REQUIRE(neo::vm_resolution_ok(G), "occupancy resolution must be 8, 16 or a multiple of 32 in [32, 256]");
+        REQUIRE(neo::occ_resolution_ok(G), neo::OCC_RESOLUTION_MSG);
         REQUIRE(lo && hi, "null pointer");
-        if (const char* msg = neo::vm_box_from(G, lo, hi, box)) return fail(NEO_ERR_INVALID, "%s", msg);
-        box.bits = bits, box.G = G, box.clip = clip != 0;
+        if (const char* msg = neo::occ_grid_box(G, lo, hi, clip, box)) return fail(NEO_ERR_INVALID, "%s", msg);
+        box.bits = bits;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (R == 0) {
@@ -170,7 +154,7 @@ int neo_vanilla_train_rows(neo_ctx* ctx, const uint32_t* bits, int G, const floa
     ORDERED_LANE(ctx, s);
     if (ctx->ws[5].reserve(static_cast<size_t>(nb) * sizeof(int))) return NEO_ERR_NOMEM;
     int* totals = ctx->ws[5].as<int>();
-    hipLaunchKernelGGL(neo::k_vt_keep, dim3(nb), dim3(neo::OCC_BLOCK), 0, s, rays_o, dirs, t, N, P, box, keep, totals);
+    neo::launch_point_keep(neo::point_source_dense(rays_o, dirs, t, N, R, N), box, keep, totals, s);
     hipLaunchKernelGGL(neo::k_vt_rows, dim3(nb), dim3(neo::OCC_BLOCK), 0, s, rays_o, dirs, t, dir_enc, (const uint8_t*)keep, N, P,
                        (const int*)totals, cap, count, index, x_enc, cond);
     return check_launch();
@@ -208,10 +192,10 @@ int neo_vanilla_train_scatter_backward(neo_ctx* ctx, const float* raw_rgb, const
 int neo_vanilla_grid_probes(neo_ctx* ctx, int G, const float* lo, const float* hi, uint64_t seed, uint32_t step, float* pts,
                             void* stream) {
     ENTER(ctx);
-    REQUIRE(neo::vm_resolution_ok(G), "occupancy resolution must be 8, 16 or a multiple of 32 in [32, 256]");
+    REQUIRE(neo::occ_resolution_ok(G), neo::OCC_RESOLUTION_MSG);
     REQUIRE(lo && hi && pts, "null pointer");
-    neo::VmBox box{};
-    if (const char* msg = neo::vm_box_from(G, lo, hi, box)) return fail(NEO_ERR_INVALID, "%s", msg);
+    neo::OccGrid box{};
+    if (const char* msg = neo::occ_grid_box(G, lo, hi, 0, box)) return fail(NEO_ERR_INVALID, "%s", msg);
     neo::VtProbeBox pb{};
     for (int a = 0; a < 3; ++a) {
         pb.lo[a] = box.lo[a];
@@ -230,7 +214,7 @@ int neo_vanilla_grid_probes(neo_ctx* ctx, int G, const float* lo, const float* h
 
 int neo_vanilla_density_update(neo_ctx* ctx, float* density, const float* sigma0, const float* sigma1, int G, float decay, void* stream) {
     ENTER(ctx);
-    REQUIRE(neo::vm_resolution_ok(G), "occupancy resolution must be 8, 16 or a multiple of 32 in [32, 256]");
+    REQUIRE(neo::occ_resolution_ok(G), neo::OCC_RESOLUTION_MSG);
     REQUIRE(decay >= 0.0f && decay <= 1.0f, "decay must lie in [0, 1]");
     REQUIRE(density && sigma0, "null pointer");
     const int cells = G * G * G;
