@@ -1057,6 +1057,43 @@ int neo_pix_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const
                    float* rgb0, float* acc0, float* depth0, float* rgb1, float* acc1,
                    float* depth1, void* stream);
 
+/* PIXELNERF MARCHING FRAME: empty-space skipping and early ray termination for the PixelNeRF baseline decoder.  Given the scene
+ * latent, the source cameras and the weights, a PixelNeRF density depends on the position alone, so a grid built once per scene over
+ * a caller-given box stays valid for every frame of that scene.  The pieces are those of the VANILLA MARCHING FRAME above (BOX GRID,
+ * BOX KEEP RULE, MODE-0 STOP RULE, its BOUND and its samples struct), with two differences: positions lie along rays_d (the keep
+ * rule's `dirs` is rays_d), and a sample is SEEN along the direction of the quirk-Q1 ray of the dense launch, ray c0 + ((r - c0) N
+ * + j) mod bc of the reference chunk [c0, c0 + bc) of ray r - so a row's value depends on `chunk`, as in neo_pix_render.
+ *
+ * neo_pix_set_occupancy installs the BOX GRID in a slot of its own (arguments and ordering of neo_vanilla_set_occupancy; bits == NULL
+ * removes it).  The grid belongs to the scene latent, the source cameras and the uploaded weights, which the library cannot check.
+ * neo_pix_set_march_window: rays per window of neo_pix_render_marching, 1 .. 65536, 0 = the default (16384); results do not depend on it.
+ *
+ * neo_pix_mlp_compact is neo_pix_mlp on single points whose number lives on the device: rays_o, rays_d, viewdirs (cap,3), t (cap) and
+ * out (cap,4) are allocated for `cap` rows, the host's bound, and min(*count_dev, cap) of them are live (count_dev [device]: one int;
+ * 0 is a valid launch).  Row k is the point rays_o[k] + t[k] * rays_d[k] seen along viewdirs[k]: the caller has resolved quirk Q1,
+ * every row is its own ray (N = 1, one chunk).  Its out row is bitwise what neo_pix_mlp gives the same point and direction, with and
+ * without pre-projection and in both arithmetics.  A row at or behind the count is neither read nor written; a workgroup whose first
+ * row is at or behind the count leaves before its first barrier.  Checks and src_poses / focal / cx / cy as for neo_pix_mlp.
+ *
+ * neo_pix_render_marching is neo_pix_render in which a sample is evaluated iff the BOX KEEP RULE of the installed grid keeps it AND it
+ * lies in front of its ray's stop.  A sample that is not evaluated has the row (0, 0, 0, 0) and weight exactly 0; an evaluated one
+ * goes through the compact launch and is bitwise neo_pix_mlp's at the call's `chunk`.  LEVELS, eps, segment, coarse, use_grid, the
+ * BOUND (coarse == 0: a never-stopped ray bitwise equal to the same call at eps == 0, a stopped ray's level-1 rgb within 1.003 trans
+ * per channel and its depth within 1.001 far trans), samples0 / samples1 and kept are neo_vanilla_render_marching's.  Without a grid
+ * (or use_grid == 0, or every cell set, or a box that holds no sample and clip == 0) at eps == 0 the six outputs are bitwise
+ * neo_pix_render's.  coarse != 0 claims no bound.  Results do not depend on the window, the stream, or on whether the frame is one
+ * call or the caller's loop over reference chunks.  R == 0 zeroes kept.  No call synchronises the device. */
+int neo_pix_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, const float* lo, const float* hi, int clip, void* stream);
+int neo_pix_set_march_window(neo_ctx* ctx, int rays);
+int neo_pix_mlp_compact(neo_ctx* ctx, int slot, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t,
+                        int cap, const int* count_dev, const float* src_poses, int NV, float focal, float cx, float cy, float* out,
+                        void* stream);
+int neo_pix_render_marching(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                            const float* src_poses, int NV, float focal, float cx, float cy, float near, float far, int n_coarse,
+                            int n_fine, int white_bkgd, float eps, int segment, int coarse, int use_grid, float* rgb0, float* acc0,
+                            float* depth0, float* rgb1, float* acc1, float* depth1, const neo_vanilla_march_samples* samples0,
+                            const neo_vanilla_march_samples* samples1, long long* kept, void* stream);
+
 /* ---- Mip-NeRF 360 (models/mipnerf360/model.py) -------------------------------- */
 /* Upload one MipNeRF360MLP (model.py:30-107).  slot 0..2 = mlps.0, mlps.1 (PropMLP: width 256,
  * depth 4, rgb 0) and mlps.2 (NeRFMLP: width 1024, depth 8, rgb 1) — the shapes the kernels are

@@ -220,6 +220,12 @@ SIGNATURES = {
     "neo_pix_mlp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, c_float_p, _i, _f, _f, _f, _vp, _vp]),
     "neo_pix_render": (_i, [_vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _f, _f, _i, _i, _i,
                             _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "neo_pix_set_occupancy": (_i, [_vp, _vp, _i, c_float_p, c_float_p, _i, _vp]),
+    "neo_pix_set_march_window": (_i, [_vp, _i]),
+    "neo_pix_mlp_compact": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, c_float_p, _i, _f, _f, _f, _vp, _vp]),
+    "neo_pix_render_marching": (_i, [_vp, _vp, _vp, _vp, _i, _i, c_float_p, _i, _f, _f, _f, _f, _f, _i, _i, _i, _f, _i, _i, _i,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(VanillaMarchSamples),
+                                     ctypes.POINTER(VanillaMarchSamples), _vp, _vp]),
     "neo_mip_upload_mlp": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]),
     "neo_mip_resample": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _f, _f, _vp, _vp, _vp]),
     "neo_mip_mlp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),

@@ -195,6 +195,7 @@ int neo_ctx_destroy(neo_ctx* ctx) {
     ctx->boxes.release();
     ctx->occ.bits.release();
     ctx->vocc.bits.release();
+    ctx->pocc.bits.release();
     ctx->enc.release();
     ctx->enc_latent.release();
     ctx->enc_axes.release();

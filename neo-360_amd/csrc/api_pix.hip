@@ -1,5 +1,7 @@
 // PixelNeRF baseline decoder entry points of the C ABI (models/vanilla_nerf/model_pixel.py:133-258).
+#include "common.h"
 #include "ctx.h"
+#include "march.h"
 
 using namespace neo_host;
 
@@ -9,21 +11,13 @@ namespace {
 // 158,976; per point density 128 + 128*128 + rgb 384 = 16,896
 double pix_flop_per_point(int nv) { return 2.0 * (nv * 158976.0 + 16896.0); }
 
-int pix_launch(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
-               const float* rays_d, const float* viewdirs, const float* tvals, int t_shared, int R, int N, int chunk,
-               float* out, hipStream_t s) {
+// What surrounds a launch of slot `slot`, dense or compact: the slot's state, and in the split arithmetic the one-time range
+// guards and the lazy pre-projection (proj: the map to gather, null without pre-projection or in the exact arithmetic)
+int pix_prepare(neo_ctx* ctx, int slot, const neo::TpScene& sc, hipStream_t s, const float** proj) {
     MlpSlot& sl = ctx->pix[slot];
+    *proj = nullptr;
     if (!sl.ready) return fail(NEO_ERR_STATE, "PixelNeRF MLP slot %d has no weights", slot);
-    if (ctx->precision != 1) {
-        // exact fp32 MFMA, the reference's operation order up to the folded view layer (mlp_pix.hip): what a range-guard retry
-        // of the split evaluator lands on
-        neo::TpMlpDev mf{sl.wpack.as<float>(), sl.bias_hp.as<float>(), sl.heads.as<float>()};
-        ctx->span_kernel_next = 9;
-        ctx->span_begin(s);
-        neo::launch_pix_mlp(mf, sc, views, rays_o, rays_d, viewdirs, tvals, t_shared, R, N, chunk, out, s);
-        ctx->span_end(s, static_cast<double>(R) * N, pix_flop_per_point(sc.nv));
-        return NEO_OK;
-    }
+    if (ctx->precision != 1) return NEO_OK;
     // low end: the bottleneck (upload index 6) is folded into view layer 0 in fp64 at pack time (launch_pix_pack_h)
     guard_split_weights(sl, sl.wpack_h.p, neo::pix_wpack_h_bytes(), ctx->flags, s, neo::SPLIT_WEIGHT_LOW_PIX, 1u << 6);
     if (!ctx->pix_latent_checked) {
@@ -36,7 +30,6 @@ int pix_launch(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpView
                                    neo::SPLIT_MAP_LOW, true, s)) return rc;
         ctx->pix_latent_low_checked = true;
     }
-    const float* proj = nullptr;
     if (ctx->pix_preproject) {
         // latent pre-projected through this slot's pts_linears.0 latent columns (exact fp32 MFMA): rebuilt only when the
         // scene or the slot's weights changed since the last launch
@@ -48,7 +41,26 @@ int pix_launch(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpView
             sl.proj_weights = sl.weights_epoch;
             sl.proj_scene = ctx->pix_scene_epoch;
         }
-        proj = sl.proj.as<float>();
+        *proj = sl.proj.as<float>();
+    }
+    return NEO_OK;
+}
+
+int pix_launch(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
+               const float* rays_d, const float* viewdirs, const float* tvals, int t_shared, int R, int N, int chunk,
+               float* out, hipStream_t s) {
+    const float* proj = nullptr;
+    if (int rc = pix_prepare(ctx, slot, sc, s, &proj)) return rc;
+    MlpSlot& sl = ctx->pix[slot];
+    if (ctx->precision != 1) {
+        // exact fp32 MFMA, the reference's operation order up to the folded view layer (mlp_pix.hip): what a range-guard retry
+        // of the split evaluator lands on
+        neo::TpMlpDev mf{sl.wpack.as<float>(), sl.bias_hp.as<float>(), sl.heads.as<float>()};
+        ctx->span_kernel_next = 9;
+        ctx->span_begin(s);
+        neo::launch_pix_mlp(mf, sc, views, rays_o, rays_d, viewdirs, tvals, t_shared, R, N, chunk, out, s);
+        ctx->span_end(s, static_cast<double>(R) * N, pix_flop_per_point(sc.nv));
+        return NEO_OK;
     }
     neo::TpMlpHDev mh{sl.wpack_h.p, sl.bias.as<float>(), sl.heads.as<float>(), ctx->flags};
     ctx->span_begin(s);
@@ -56,6 +68,32 @@ int pix_launch(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpView
     ctx->span_end(s, static_cast<double>(R) * N, pix_flop_per_point(sc.nv));
     return NEO_OK;
 }
+
+// The compact launch of slot `slot` (kernels.h: launch_pix_mlp_h_compact): `cap` rows of one point each under the device count.
+// The span prices no points: the live count stays on the device, and a span must not price rows that were never evaluated (as
+// tp_launch's for a cull_map launch).
+int pix_launch_compact(neo_ctx* ctx, int slot, const neo::TpScene& sc, const neo::TpViews& views, const float* rays_o,
+                       const float* rays_d, const float* viewdirs, const float* t, long cap, const int* count_dev, float* out,
+                       hipStream_t s) {
+    const float* proj = nullptr;
+    if (int rc = pix_prepare(ctx, slot, sc, s, &proj)) return rc;
+    MlpSlot& sl = ctx->pix[slot];
+    if (ctx->precision != 1) {
+        neo::TpMlpDev mf{sl.wpack.as<float>(), sl.bias_hp.as<float>(), sl.heads.as<float>()};
+        ctx->span_kernel_next = 9;
+        ctx->span_begin(s);
+        neo::launch_pix_mlp_compact(mf, sc, views, rays_o, rays_d, viewdirs, t, cap, count_dev, out, s);
+        ctx->span_end(s, 0.0, pix_flop_per_point(sc.nv));
+        return NEO_OK;
+    }
+    neo::TpMlpHDev mh{sl.wpack_h.p, sl.bias.as<float>(), sl.heads.as<float>(), ctx->flags};
+    ctx->span_begin(s);
+    neo::launch_pix_mlp_h_compact(mh, proj, sc, views, rays_o, rays_d, viewdirs, t, cap, count_dev, out, s);
+    ctx->span_end(s, 0.0, pix_flop_per_point(sc.nv));
+    return NEO_OK;
+}
+
+constexpr int PM_WINDOW_DEFAULT = 16384;      // rays per window of neo_pix_render_marching: measured, DESIGN.md 4.22 (144 MB of point rows at most)
 
 }  // namespace
 
@@ -180,6 +218,63 @@ int neo_pix_render(neo_ctx* ctx, const float* rays_o, const float* rays_d, const
     if (rc) return rc;
     neo::launch_composite(0, out1, t1, N1, rays_d, nullptr, R, N1, white_bkgd, rgb1, acc1, depth1, nullptr, nullptr, s);
     return check_launch();
+}
+
+int neo_pix_set_march_window(neo_ctx* ctx, int rays) {
+    ENTER(ctx);
+    REQUIRE(rays >= 0 && rays <= 65536, "march window must be 0 (the default) or 1 .. 65536 rays");
+    ctx->pix_window = rays;
+    return NEO_OK;
+}
+
+int neo_pix_mlp_compact(neo_ctx* ctx, int slot, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t,
+                        int cap, const int* count_dev, const float* src_poses, int NV, float focal, float cx, float cy, float* out,
+                        void* stream) {
+    ENTER(ctx);
+    ORDERED(ctx, static_cast<hipStream_t>(stream));      // touches context-owned memory: ordered across streams
+    REQUIRE(slot == 0 || slot == 1, "slot must be 0 or 1");
+    REQUIRE(cap >= 0 && cap <= 2147483647 / 4, "bad shape");
+    if (cap == 0) return NEO_OK;
+    REQUIRE(rays_o && rays_d && viewdirs && t && count_dev && src_poses && out, "null pointer");
+    if (!ctx->pix_scene_ready) return fail(NEO_ERR_STATE, "scene latent not set (neo_pix_set_scene)");
+    REQUIRE(NV == ctx->pix_scene.nv, "NV differs from the uploaded scene");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto [sc, views] = call_scene(ctx->pix_scene, src_poses, NV, focal, cx, cy);
+    const int rc = pix_launch_compact(ctx, slot, sc, views, rays_o, rays_d, viewdirs, t, cap, count_dev, out, s);
+    if (rc) return rc;
+    return check_launch();
+}
+
+int neo_pix_render_marching(neo_ctx* ctx, const float* rays_o, const float* rays_d, const float* viewdirs, int R, int chunk,
+                            const float* src_poses, int NV, float focal, float cx, float cy, float near, float far, int n_coarse,
+                            int n_fine, int white_bkgd, float eps, int segment, int coarse, int use_grid, float* rgb0, float* acc0,
+                            float* depth0, float* rgb1, float* acc1, float* depth1, const neo_vanilla_march_samples* samples0,
+                            const neo_vanilla_march_samples* samples1, long long* kept, void* stream) {
+    ENTER(ctx);
+    REQUIRE(chunk >= 1, "bad ray count / chunk");
+    neo::TpScene sc{};
+    neo::TpViews views{};
+    if (R > 0) {      // as neo_pix_render: no rays is a valid call, whatever else is missing
+        REQUIRE(viewdirs && src_poses, "null pointer");
+        if (!ctx->pix_scene_ready) return fail(NEO_ERR_STATE, "scene latent not set (neo_pix_set_scene)");
+        REQUIRE(NV == ctx->pix_scene.nv, "NV differs from the uploaded scene");
+        auto [scene, poses] = call_scene(ctx->pix_scene, src_poses, NV, focal, cx, cy);
+        sc = scene, views = poses;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // samples along rays_d, seen along the quirk-Q1 ray of the dense launch (model_pixel.py:183-192, :219-222): the view column
+    const Mode0Frame f{rays_o, rays_d, viewdirs, rays_d, R, chunk, near, far, n_coarse, n_fine, white_bkgd, eps, segment, coarse,
+                       rgb0, acc0, depth0, rgb1, acc1, depth1, samples0, samples1, kept};
+    // both callbacks do what pix_launch does around a launch: the range guards and the lazy pre-projection (touch_shared)
+    return march_frame_mode0(
+        ctx, f, use_grid != 0 ? ctx->pocc.get() : nullptr, ctx->pix_window > 0 ? ctx->pix_window : PM_WINDOW_DEFAULT, s,
+        [&](int level, const neo::PointSource& src, float* out) {
+            return pix_launch(ctx, level, sc, views, src.rays_o, src.dirs, src.viewdirs, src.pos, src.stride == 0, src.R, src.N, src.chunk,
+                              out, s);
+        },
+        [&](int level, const neo::OccRows& rows, long P) {
+            return pix_launch_compact(ctx, level, sc, views, rows.o, rows.d, rows.v, rows.t, P, rows.count, rows.out, s);
+        });
 }
 
 }  // extern "C"

@@ -239,6 +239,10 @@ struct neo_ctx {
     // neo_vanilla_set_march_window: rays per window of neo_vanilla_render_marching (0: the default of vanilla_march.hip)
     OccInstalled vocc;
     int vanilla_window = 0;
+    // neo_pix_set_occupancy: the PixelNeRF scene's grid over a caller-given box (it describes ONE scene latent);
+    // neo_pix_set_march_window: rays per window of neo_pix_render_marching (0: the default of api_pix.hip)
+    OccInstalled pocc;
+    int pix_window = 0;
     // pillar stage of the scene encoder (neo_enc_*): packed weights, biases (6x512), scorer heads (3x512), workspaces
     neo_host::MlpSlot enc;
     float enc_head_b[3] = {0.f, 0.f, 0.f};

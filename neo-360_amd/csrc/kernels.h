@@ -340,6 +340,17 @@ void launch_pix_pack(const float* const* w, const float* const* b, float* fold_v
                      float* wpack, hipStream_t s);
 void launch_pix_mlp(const TpMlpDev& m, const TpScene& sc, const TpViews& views, const float* rays_o, const float* rays_d,
                     const float* viewdirs, const float* tvals, int t_shared, int R, int N, int chunk, float* out, hipStream_t s);
+// The compact launches of the two PixelNeRF evaluators (api_pix.hip), the contract of launch_vanilla_mlp_h_compact above with a
+// view column: rays_o, rays_d, viewdirs (cap,3), t (cap), out (cap,4), all allocated for `cap` rows, the host's bound, of which
+// min(*count, cap) are live (count: a device word; 0 is a valid launch).  Row k is ONE point, rays_o[k] + t[k] rays_d[k], seen
+// along viewdirs[k] - the caller has already resolved quirk Q1, the launch treats every row as its own ray (N = 1, one chunk).
+// Its out row is bitwise the dense launch's for the same point and direction, in both operation orders (proj or not) and both
+// arithmetics.  Rows at or behind the count are neither read nor written; the variant never depends on the count.
+void launch_pix_mlp_h_compact(const TpMlpHDev& m, const float* proj, const TpScene& sc, const TpViews& views, const float* rays_o,
+                              const float* rays_d, const float* viewdirs, const float* t, long cap, const int* count, float* out,
+                              hipStream_t s);
+void launch_pix_mlp_compact(const TpMlpDev& m, const TpScene& sc, const TpViews& views, const float* rays_o, const float* rays_d,
+                            const float* viewdirs, const float* t, long cap, const int* count, float* out, hipStream_t s);
 
 // pillar.hip — pillar stage of the scene encoder
 struct PillarGeom {

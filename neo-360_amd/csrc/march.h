@@ -1,16 +1,17 @@
 // The windowed, segmented march of a level (include/neo360_hip.h: KEEP RULE, STOP RULE, OUTSIDE STOP RULE, VANILLA MARCHING FRAME):
 // the point-list builder (point_list.hip), the march kernels (march.hip) and the one level loop, march_level below, that the
-// NeO-360 frames (api_tp.hip) and the vanilla frame (vanilla_march.hip) drive with their own evaluator.  One set of kernels serves
-// every user:
+// NeO-360 frames (api_tp.hip), the vanilla frame (vanilla_march.hip) and the PixelNeRF frame (api_pix.hip) drive with their own
+// evaluator.  One set of kernels serves every user:
 //
-//                     NeO-360 inside the sphere       NeO-360 outside the sphere        vanilla
-//   rows              dense, row = ray                compact, row k of ray map[k]      dense, row = ray
-//   position rows     (R, N)                          stride given (level 0: one row)   stride given (level 0: one shared row)
-//   view column       quirk-Q1 ray                    quirk-Q1 ray                      not written
-//   far column        not written                     written (the evaluators read it)  not written
-//   grid              unit cube, edge cell outside    none                              caller's box, keep or skip outside
-//   composite mode    1                               2                                 0
-//   running value     (float)carry                    lam_c x (float)carry              (float)carry
+//                     NeO-360 inside the sphere       NeO-360 outside the sphere        vanilla                                 PixelNeRF
+//   rows              dense, row = ray                compact, row k of ray map[k]      dense, row = ray                        dense, row = ray
+//   position rows     (R, N)                          stride given (level 0: one row)   stride given (level 0: one shared row)  as vanilla
+//   direction column  rays_d                          rays_d                            viewdirs                                rays_d
+//   view column       quirk-Q1 ray                    quirk-Q1 ray                      not written                             quirk-Q1 ray
+//   far column        not written                     written (the evaluators read it)  not written                             not written
+//   grid              unit cube, edge cell outside    none                              caller's box, keep or skip outside      as vanilla
+//   composite mode    1                               2                                 0                                       0
+//   running value     (float)carry                    lam_c x (float)carry              (float)carry                            (float)carry
 //
 // The arithmetic differences (mode, the multiply) are compile-time; map, far, viewdirs and lam are optional pointers.
 #pragma once
@@ -161,6 +162,94 @@ int march_level(neo::PointSource src, const neo::OccGrid* grid, const MarchRule&
         }
     }
     return NEO_OK;
+}
+
+// THE TWO-LEVEL MODE-0 FRAME (include/neo360_hip.h: VANILLA MARCHING FRAME, PIXELNERF MARCHING FRAME): a coarse + fine render whose
+// levels are march_level in composite mode 0 - one shared row of level-0 positions, launch_resample between the levels.  What a
+// renderer brings is data and its evaluator: the columns (dirs: what positions lie along; viewdirs / chunk: the optional view column of
+// PointSource), its grid, its window, and two callbacks,
+//     dense(level, src, out)     the renderer's dense launch of the level (src.pos / stride / R / N), taken when the level has neither
+//                                a grid nor a rule to follow - the level of the plain render;
+//     compact(level, rows, P)    its compact launch on the point rows (march_level's eval).
+struct Mode0Frame {
+    const float *rays_o, *dirs, *viewdirs, *rays_d;
+    int R, chunk;
+    float near, far;
+    int n_coarse, n_fine, white_bkgd;
+    float eps;
+    int segment, coarse;
+    float *rgb0, *acc0, *depth0, *rgb1, *acc1, *depth1;
+    const neo_vanilla_march_samples *samples0, *samples1;      // per level: t, w, keep, stop, rows; any pointer may be null
+    long long* kept;
+};
+
+template <class Dense, class Compact>
+int march_frame_mode0(neo_ctx* ctx, const Mode0Frame& f, const neo::OccGrid* grid, int window, hipStream_t s, Dense&& dense,
+                      Compact&& compact) {
+    const int R = f.R;
+    REQUIRE(R >= 0, "negative ray count");
+    REQUIRE(f.n_coarse >= 3 && f.n_coarse <= 256 && f.n_fine >= 1 && f.n_coarse + 1 + f.n_fine <= 1024, "unsupported sample counts");
+    REQUIRE(f.eps >= 0.0f && f.eps < 1.0f, "eps must lie in [0, 1)");
+    REQUIRE(f.segment >= 64 && f.segment % 64 == 0, "segment must be a positive multiple of 64");
+    if (R == 0) {
+        if (f.kept) HIP_TRY(hipMemsetAsync(f.kept, 0, 2 * sizeof(long long), s));
+        return NEO_OK;
+    }
+    REQUIRE(f.rays_o && f.dirs && f.rays_d, "null pointer");
+    const int N0 = f.n_coarse + 1, N1 = N0 + f.n_fine;
+    REQUIRE(static_cast<long>(R) * N1 <= 2147483647L - 1024, "too many points for 32-bit indices");
+    const float* t0 = ctx->get_edges(f.n_coarse, f.near, f.far, s);
+    const float* u = ctx->get_quantiles(f.n_fine, s);
+    if (!t0 || !u) return fail(NEO_ERR_HIP, "constant table upload failed");
+    ORDERED_LANE(ctx, s);      // writes this lane's workspaces only, reads the packed weights and the grid
+    const int win = std::min(window, R);
+    const size_t r = static_cast<size_t>(R);
+    // eps == 0 stops nothing (a transmittance is >= 0 or NaN): no level follows the rule, stop = N
+    const bool follow[2] = {f.coarse != 0 && f.eps > 0.0f, f.eps > 0.0f};
+    const size_t candidates = grid ? static_cast<size_t>(win) * N1 : 0;
+    if (ctx->ws[0].reserve(r * N0 * 16) || ctx->ws[1].reserve(r * N0 * 4) || ctx->ws[2].reserve(r * N1 * 4) ||
+        ctx->ws[3].reserve(r * N1 * 16) || ctx->ws[4].reserve(MarchState::bytes(false, r, win, candidates)))
+        return NEO_ERR_NOMEM;
+    const neo_vanilla_march_samples *s0 = f.samples0, *s1 = f.samples1;
+    MarchState st[2];
+    st[0].carve(ctx->ws[4].p, false, r, win);
+    st[1] = st[0];
+    if (s0 && s0->stop) st[0].stop = s0->stop;
+    if (s1 && s1->stop) st[1].stop = s1->stop;
+    float* out0 = s0 && s0->rows ? s0->rows : ctx->ws[0].as<float>();
+    float* w0 = s0 && s0->w ? s0->w : ctx->ws[1].as<float>();
+    float* t1 = s1 && s1->t ? s1->t : ctx->ws[2].as<float>();
+    float* out1 = s1 && s1->rows ? s1->rows : ctx->ws[3].as<float>();
+    neo::PointSource src{};
+    src.rays_o = f.rays_o, src.dirs = f.dirs, src.viewdirs = f.viewdirs, src.R = R, src.chunk = f.chunk;
+    // one level into `out` (R,N,4) with its stops in the state: the dense launch, or march_level with the point rows in W[5]
+    const auto level = [&](int lv, float* out, long long* kept) -> int {
+        const MarchRule rule{follow[lv], f.eps, f.segment, 0, f.rays_d, nullptr, nullptr, nullptr};
+        if (!rule.follow && !grid) {
+            neo::launch_march_init(nullptr, nullptr, nullptr, R, nullptr, nullptr, nullptr, st[lv].stop, src.N, kept, src.N, s);
+            return dense(lv, src, out);
+        }
+        const size_t cap = march_level_cap(rule, src.N, win);
+        if (ctx->ws[5].reserve(neo::occ_rows_bytes(cap))) return NEO_ERR_NOMEM;
+        neo::OccRows w;
+        w.carve(ctx->ws[5].p, cap);
+        return march_level(src, grid, rule, st[lv], win, w, out, kept, s,
+                           [&](const neo::OccRows& rows, long P) { return compact(lv, rows, P); });
+    };
+    // level 0: one shared row of positions (stride 0)
+    src.pos = t0, src.stride = 0, src.N = N0;
+    if (int rc = level(0, out0, f.kept)) return rc;
+    neo::launch_composite(0, out0, t0, 0, f.rays_d, nullptr, R, N0, f.white_bkgd, f.rgb0, f.acc0, f.depth0, w0, nullptr, s);
+    if (neo::launch_resample(t0, 0, w0, u, 0, R, N0, f.n_fine, 0, t1, s)) return fail(NEO_ERR_INVALID, "unsupported sample counts");
+    src.pos = t1, src.stride = N1, src.N = N1;
+    if (int rc = level(1, out1, f.kept ? f.kept + 1 : nullptr)) return rc;
+    neo::launch_composite(0, out1, t1, N1, f.rays_d, nullptr, R, N1, f.white_bkgd, f.rgb1, f.acc1, f.depth1, s1 ? s1->w : nullptr, nullptr, s);
+    if (s0 && s0->t) HIP_TRY(hipMemcpyAsync(s0->t, t0, static_cast<size_t>(N0) * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // the keep masks of the whole rows, behind the stops as well (no grid: all ones)
+    const neo::OccGrid mask_grid = grid ? *grid : neo::OccGrid{};
+    if (s0 && s0->keep) neo::launch_point_keep(neo::point_source_dense(f.rays_o, f.dirs, t0, 0, R, N0), mask_grid, s0->keep, nullptr, s);
+    if (s1 && s1->keep) neo::launch_point_keep(neo::point_source_dense(f.rays_o, f.dirs, t1, N1, R, N1), mask_grid, s1->keep, nullptr, s);
+    return check_launch();
 }
 
 }  // namespace neo_host

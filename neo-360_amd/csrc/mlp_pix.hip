@@ -61,6 +61,8 @@ __device__ __forceinline__ void gemm_rows(f32x16 (&acc)[2], const f32x4* __restr
     }
 }
 
+// COMPACT: as k_pix_mlp_h's (mlp_pix_h.hip) - min(*sc.cull_count, R) live rows of one point each, N = 1, chunk = R
+template <bool COMPACT>
 __global__ __launch_bounds__(256, 2) void k_pix_mlp(TpMlpDev m, TpScene sc, TpViews views, const float* __restrict__ rays_o,
                                                    const float* __restrict__ rays_d, const float* __restrict__ viewdirs,
                                                    const float* __restrict__ tvals, int t_shared, int R, int N, int chunk,
@@ -77,11 +79,26 @@ __global__ __launch_bounds__(256, 2) void k_pix_mlp(TpMlpDev m, TpScene sc, TpVi
     LaneCtx L;
     L.init();
     const int tid = threadIdx.x;
+    if constexpr (COMPACT) {
+        // the live rows stand in for the launch's R, and what the contract fixes is a literal (registers: the compact twin must not
+        // spill beyond the dense one): one sample per row, one chunk, a position row of its own per row
+        const int n = *sc.cull_count;
+        R = n < R ? n : R;
+        N = 1, chunk = R, t_shared = 0;
+    }
     const long P = (long)R * N;
-    const long tile0 = tp::xcd_tile(blockIdx.x, (P + TM - 1) / TM) * TM;
-    if (tile0 >= P) return;
+    const long tile0 = tp::xcd_tile<COMPACT>(blockIdx.x, (P + TM - 1) / TM) * TM;
+    if (tile0 >= P) return;       // a workgroup at or behind the count leaves as a whole, before the first barrier
     const f32x4* wp = reinterpret_cast<const f32x4*>(m.wpack);
 
+    // COMPACT: the tile and the count, which no launch argument gives back, wait for the closing block in LDS instead of in
+    // registers - in two words of the carve that this decoder leaves alone: column 3 of the feature-lookup points (rows 0 and 1),
+    // which point_setup<3> does not write and view_descriptors does not read.  Both fit 32 bits (the launch holds cap <= 2^29 rows),
+    // and the launch asks for the dense launch's LDS, byte for byte.
+    int* tail = reinterpret_cast<int*>(S.feat_world);
+    constexpr int TAIL_TILE = 3, TAIL_COUNT = 7;
+    if constexpr (COMPACT)
+        if (tid == 0) { tail[TAIL_TILE] = (int)tile0; tail[TAIL_COUNT] = (int)P; }
     tp::point_setup<3>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, nullptr, nullptr, t_shared != 0);
     __syncthreads();
 
@@ -208,8 +225,8 @@ __global__ __launch_bounds__(256, 2) void k_pix_mlp(TpMlpDev m, TpScene sc, TpVi
             g = fmaf(h, wr[128 + k], g);
             b = fmaf(h, wr[256 + k], b);
         }
-        const long gi = tile0 + tid;
-        if (gi < P) out[gi] = make_float4(sigmoid_act(r), sigmoid_act(g), sigmoid_act(b), sigma);
+        const long gi = (COMPACT ? (long)tail[TAIL_TILE] : tile0) + tid;
+        if (gi < (COMPACT ? (long)tail[TAIL_COUNT] : P)) out[gi] = make_float4(sigmoid_act(r), sigmoid_act(g), sigmoid_act(b), sigma);
     }
 }
 
@@ -244,8 +261,20 @@ void launch_pix_mlp(const TpMlpDev& m, const TpScene& sc, const TpViews& views, 
     if (P <= 0) return;
     const size_t lds = tp::LDS_WORDS * sizeof(float);
     const long tiles = tp::xcd_grid((P + TM - 1) / TM);
-    hipLaunchKernelGGL(k_pix_mlp, dim3((unsigned)tiles), dim3(256), lds, s, m, sc, views, rays_o, rays_d, viewdirs, tvals,
+    hipLaunchKernelGGL(k_pix_mlp<false>, dim3((unsigned)tiles), dim3(256), lds, s, m, sc, views, rays_o, rays_d, viewdirs, tvals,
                        t_shared, R, N, chunk, reinterpret_cast<float4*>(out));
+}
+
+void launch_pix_mlp_compact(const TpMlpDev& m, const TpScene& sc, const TpViews& views, const float* rays_o, const float* rays_d,
+                            const float* viewdirs, const float* t, long cap, const int* count, float* out, hipStream_t s) {
+    if (cap <= 0) return;
+    const size_t lds = tp::LDS_WORDS * sizeof(float);
+    const long tiles = tp::xcd_grid((cap + TM - 1) / TM);
+    TpScene scc = sc;
+    scc.cull_count = count;
+    const int R = (int)cap;
+    hipLaunchKernelGGL(k_pix_mlp<true>, dim3((unsigned)tiles), dim3(256), lds, s, m, scc, views, rays_o, rays_d, viewdirs, t, 0, R, 1,
+                       R, reinterpret_cast<float4*>(out));
 }
 
 }  // namespace neo

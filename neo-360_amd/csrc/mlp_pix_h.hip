@@ -99,7 +99,13 @@ __global__ void k_pix_pack_x_h(const float* __restrict__ src, _Float16* __restri
     }
 }
 
-template <bool PROJ>
+// COMPACT (the PixelNeRF march, api_pix.hip; as mlp_vanilla_h.hip's): the launch was sized for R rows, the host's bound, of which
+// min(*sc.cull_count, R) are live - a device word - and every row is ONE point that is its own ray (N = 1, chunk = R: the view
+// column of a row is the row's own, the caller has resolved quirk Q1).  A workgroup whose first row is at or behind the count
+// leaves before the first barrier and as a whole; a row behind the count inside a live tile is the dense launch's tail row: it
+// reads the LAST LIVE row and stores nothing.  Nothing else differs, so a row's value is the dense launch's for the same point and
+// direction, bit for bit; the dense instantiations compile to what they were.
+template <bool PROJ, bool COMPACT = false>
 __global__ __launch_bounds__(256, NEO_GATHER_WAVES_PER_SIMD) void k_pix_mlp_h(TpMlpHDev m, const float* __restrict__ proj,
                                                       TpScene sc, TpViews views,
                                                       const float* __restrict__ rays_o,
@@ -121,11 +127,26 @@ __global__ __launch_bounds__(256, NEO_GATHER_WAVES_PER_SIMD) void k_pix_mlp_h(Tp
     LaneCtx L;
     L.init();
     int tid = threadIdx.x;
+    if constexpr (COMPACT) {
+        // the live rows stand in for the launch's R, and what the contract fixes is a literal (registers: the compact twin must not
+        // spill beyond the dense one): one sample per row, one chunk, a position row of its own per row
+        const int n = *sc.cull_count;
+        R = n < R ? n : R;
+        N = 1, chunk = R, t_shared = 0;
+    }
     const long P = (long)R * N;
-    const long tile0 = tp::xcd_tile(blockIdx.x, (P + TM - 1) / TM) * TM;      // contiguous tile range per XCD (tp_common.h)
+    const long tile0 = tp::xcd_tile<COMPACT>(blockIdx.x, (P + TM - 1) / TM) * TM;      // contiguous tile range per XCD (tp_common.h)
     if (tile0 >= P) return;       // surplus workgroup of the rounded-up grid (uniform exit before any barrier)
     const h8* wp = reinterpret_cast<const h8*>(m.wpack);
 
+    // COMPACT: the tile and the count, which no launch argument gives back, wait for the closing block in LDS instead of in
+    // registers - in two words of the carve that this decoder leaves alone: column 3 of the feature-lookup points (rows 0 and 1),
+    // which point_setup<3> does not write and view_descriptors does not read.  Both fit 32 bits (the launch holds cap <= 2^29 rows),
+    // and the launch asks for the dense launch's LDS, byte for byte.
+    int* tail = reinterpret_cast<int*>(S.feat_world);
+    constexpr int TAIL_TILE = 3, TAIL_COUNT = 7;
+    if constexpr (COMPACT)
+        if (tid == 0) { tail[TAIL_TILE] = (int)tile0; tail[TAIL_COUNT] = (int)P; }
     tp::point_setup<3>(S, tid, tile0, P, N, R, chunk, rays_o, rays_d, viewdirs, tvals, nullptr, nullptr, t_shared != 0);
     float* dens_w = smem + tp::OFF_DENSW;
     if (tid < 128) dens_w[tid] = m.heads[HD_DW + tid];
@@ -456,8 +477,8 @@ __global__ __launch_bounds__(256, NEO_GATHER_WAVES_PER_SIMD) void k_pix_mlp_h(Tp
         g += __shfl_xor(g, 1, 64); g += __shfl_xor(g, 2, 64);
         b += __shfl_xor(b, 1, 64); b += __shfl_xor(b, 2, 64);
         range_commit(L, m.flags);
-        const long gi = tile0 + pt;
-        if (part == 0 && gi < P) {
+        const long gi = (COMPACT ? (long)tail[TAIL_TILE] : tile0) + pt;
+        if (part == 0 && gi < (COMPACT ? (long)tail[TAIL_COUNT] : P)) {
             out[gi] = make_float4(sigmoid_act(r + m.heads[HD_RB]), sigmoid_act(g + m.heads[HD_RB + 1]),
                                   sigmoid_act(b + m.heads[HD_RB + 2]), sigma);
         }
@@ -515,11 +536,29 @@ void launch_pix_mlp_h(const TpMlpHDev& m, const float* proj, const TpScene& sc, 
     const size_t lds = tp::LDS_WORDS * sizeof(float);
     const long tiles = tp::xcd_grid((P + TM - 1) / TM);
     if (proj)
-        hipLaunchKernelGGL(k_pix_mlp_h<true>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
+        hipLaunchKernelGGL((k_pix_mlp_h<true, false>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
                            viewdirs, tvals, t_shared, R, N, chunk, reinterpret_cast<float4*>(out));
     else
-        hipLaunchKernelGGL(k_pix_mlp_h<false>, dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
+        hipLaunchKernelGGL((k_pix_mlp_h<false, false>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, sc, views, rays_o, rays_d,
                            viewdirs, tvals, t_shared, R, N, chunk, reinterpret_cast<float4*>(out));
+}
+
+// row k < min(*count, cap): the point rays_o[k] + t[k] rays_d[k] seen along viewdirs[k] (N = 1 and one chunk: a row is its own ray)
+void launch_pix_mlp_h_compact(const TpMlpHDev& m, const float* proj, const TpScene& sc, const TpViews& views, const float* rays_o,
+                              const float* rays_d, const float* viewdirs, const float* t, long cap, const int* count, float* out,
+                              hipStream_t s) {
+    if (cap <= 0) return;
+    const size_t lds = tp::LDS_WORDS * sizeof(float);
+    const long tiles = tp::xcd_grid((cap + TM - 1) / TM);
+    TpScene scc = sc;
+    scc.cull_count = count;
+    const int R = (int)cap;
+    if (proj)
+        hipLaunchKernelGGL((k_pix_mlp_h<true, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, scc, views, rays_o, rays_d,
+                           viewdirs, t, 0, R, 1, R, reinterpret_cast<float4*>(out));
+    else
+        hipLaunchKernelGGL((k_pix_mlp_h<false, true>), dim3((unsigned)tiles), dim3(256), lds, s, m, proj, scc, views, rays_o, rays_d,
+                           viewdirs, t, 0, R, 1, R, reinterpret_cast<float4*>(out));
 }
 
 }  // namespace neo

@@ -98,6 +98,18 @@ int set_occupancy(neo_ctx* ctx, neo_ctx::OccInstalled& to, const uint32_t* bits,
     return NEO_OK;
 }
 
+// a BOX GRID (include/neo360_hip.h) into the slot `to`: validated, then installed; bits NULL removes the slot's grid
+int set_box_occupancy(neo_ctx* ctx, neo_ctx::OccInstalled& to, const uint32_t* bits, int G, const float* lo, const float* hi, int clip,
+                      void* stream) {
+    neo::OccGrid box{};
+    if (bits) {
+        REQUIRE(occ_resolution_ok(G), OCC_RESOLUTION_MSG);
+        REQUIRE(lo && hi, "null pointer");
+        if (const char* msg = neo::occ_grid_box(G, lo, hi, clip, box)) return fail(NEO_ERR_INVALID, "%s", msg);
+    }
+    return set_occupancy(ctx, to, bits, box, stream);
+}
+
 // the KEEP RULE on caller rows (R,N): touches no context-owned memory, no ordering scope (as neo_tp_edit_rows)
 int occupancy_keep(const neo::OccGrid& grid, const float* rays_o, const float* dirs, const float* t, int R, int N, uint8_t* keep,
                    void* stream) {
@@ -119,13 +131,13 @@ int neo_tp_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, void* stream
 
 int neo_vanilla_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, const float* lo, const float* hi, int clip, void* stream) {
     ENTER(ctx);
-    neo::OccGrid box{};
-    if (bits) {
-        REQUIRE(occ_resolution_ok(G), OCC_RESOLUTION_MSG);
-        REQUIRE(lo && hi, "null pointer");
-        if (const char* msg = neo::occ_grid_box(G, lo, hi, clip, box)) return fail(NEO_ERR_INVALID, "%s", msg);
-    }
-    return set_occupancy(ctx, ctx->vocc, bits, box, stream);
+    return set_box_occupancy(ctx, ctx->vocc, bits, G, lo, hi, clip, stream);
+}
+
+// the same BOX GRID in the PixelNeRF decoder's own slot (neo_pix_render_marching reads it)
+int neo_pix_set_occupancy(neo_ctx* ctx, const uint32_t* bits, int G, const float* lo, const float* hi, int clip, void* stream) {
+    ENTER(ctx);
+    return set_box_occupancy(ctx, ctx->pocc, bits, G, lo, hi, clip, stream);
 }
 
 int neo_tp_set_skip_window(neo_ctx* ctx, int rays) {

@@ -18,6 +18,10 @@ and, for training through the grid (VANILLA MARCHING TRAINING: `MarchingNeRF.ren
     scatter_activate            activations + scatter into the composite's rows, under autograd (neo_vanilla_train_scatter)
     occupancy_probes            one jittered probe point per cell (neo_vanilla_grid_probes)
 
+`MarchingPixelNeRF` is `models.PixelNeRF` with the same grid and frame (PIXELNERF MARCHING FRAME): positions lie along rays_d, a
+sample is seen along the direction the reference's chunk tiling gives it, and `eval_points_pix` is its compact evaluator launch
+(neo_pix_mlp_compact).  The first three rules above are reused as they are (`occupancy_keep_box` with dirs = rays_d).
+
 Every caller tensor goes through `context.dense` / `context.owned_output`; a bad shape, dtype, G, box, eps or segment raises
 ValueError before any device access.
 """
@@ -160,6 +164,39 @@ def eval_points(model, level, rays_o, dirs, t, count, out=None):
     model._sync_weights(ctx)
     _lib.check(ctx.lib.neo_vanilla_mlp_compact(ctx.handle, int(level), ptr(rays_o), ptr(dirs), ptr(t), cap, ptr(count), ptr(out),
                                                ctx.stream()))
+    model._raise_flags(ctx.poll_flags())     # stage-level access: always immediate
+    return out
+
+
+@torch.no_grad()
+def eval_points_pix(model, slot, rays, t, count, out=None):
+    """The compact launch of the PixelNeRF evaluators (neo_pix_mlp_compact): `model.eval_mlp(slot, ...)` on single points whose
+    number lives on the device.  rays["rays_o" | "rays_d" | "viewdirs"] (cap,3) and t (cap,) or (cap,1) on the GPU are allocated for
+    `cap` rows, of which min(count, cap) are live; rays also carries the source cameras (`src_poses`, `src_focal`, `src_c`; `src_imgs`
+    for an attached encoder).  count is an int32 device tensor of one element and is not read by the host.  Row k is the point
+    rays_o[k] + t[k] * rays_d[k] seen along viewdirs[k] - the caller has resolved the reference's direction tiling, every row is
+    its own ray; its (rgb, sigma) row is bitwise `eval_mlp`'s for that point and direction, with and without `preproject` and in
+    both arithmetics.  out: a caller-owned (cap,4) float32 tensor, written in place - rows at or behind the count stay as they
+    are - or None for a fresh one (whose rows behind the count are undefined).  Returns out."""
+    if not isinstance(model, models.PixelNeRF):
+        raise TypeError("eval_points_pix evaluates PixelNeRF modules, got %r" % type(model))
+    if slot not in (0, 1):
+        raise ValueError("eval_points_pix: slot must be 0 or 1, got %r" % (slot,))
+    rays_o, rays_d, viewdirs = ray_rows(rays)
+    cap, dev = rays_o.shape[0], rays_o.device
+    t = dense(t, "t", [(cap,), (cap, 1)], device=dev)
+    count = dense(count, "count", [(), (1,)], dtypes=(torch.int32,), to=torch.int32, device=dev)
+    if out is None:
+        out = torch.empty(cap, 4, device=dev)
+    else:
+        out = owned_output(out, "out", (cap, 4), device=dev)
+        _lib.note_external_write()
+    ctx = model._context(dev)
+    model._ensure_scene(rays)
+    model._sync_weights(ctx)
+    host_poses, NV, focal, cx, cy = model._camera_args(rays)
+    _lib.check(ctx.lib.neo_pix_mlp_compact(ctx.handle, int(slot), ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(t), cap, ptr(count),
+                                           host_poses, NV, focal, cx, cy, ptr(out), ctx.stream()))
     model._raise_flags(ctx.poll_flags())     # stage-level access: always immediate
     return out
 
@@ -349,28 +386,17 @@ def occupancy_probes(box, resolution, seed, step, device="cuda", ctx=None):
     return pts
 
 
-class MarchingNeRF(models.NeRF):
-    """`models.NeRF` with an occupancy grid over a box, the marching frame, and training through the grid
-    (`render_train_marching`, `init_occupancy`, `update_occupancy`).  `forward`, `eval_mlp` and the parent's training path read none
-    of this."""
+class _BoxOccupancy:
+    """The installed box grid of a marching module: the module's copy, its box and clip, and the library context that holds the
+    bits (`_occ_entry`: that renderer's set_occupancy entry point)."""
 
-    # rays per window of render_marching (None: the library's default, 8192): a window bounds the extra workspace at 68 bytes per
-    # (ray, sample) of one window and segment; results do not depend on it
-    march_window = None
+    _occ_entry = None
 
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
+    def _init_box_occupancy(self):
         self._occupancy = self._occ_box = self._occ_ctx = None
         self._occ_clip = False
         self._occ_bits = None
         self.last_march_kept = None
-        self.last_train_kept = None
-        self._run = None            # init_occupancy: dict(box, G, clip, density, updates)
-
-    @property
-    def occupancy_density(self):
-        """The running density of `update_occupancy` as a float (G,G,G) device tensor (a copy), or None before `init_occupancy`."""
-        return None if self._run is None else self._run["density"].clone()
 
     @property
     def occupancy(self):
@@ -392,7 +418,7 @@ class MarchingNeRF(models.NeRF):
         if grid is None:
             if self._occ_ctx is not None and self._occ_ctx.handle:
                 c = self._occ_ctx
-                _lib.check(c.lib.neo_vanilla_set_occupancy(c.handle, None, 0, None, None, 0, c.stream()))
+                _lib.check(getattr(c.lib, self._occ_entry)(c.handle, None, 0, None, None, 0, c.stream()))
             self._occupancy = self._occ_box = self._occ_ctx = self._occ_bits = None
             self._occ_clip = False
             return
@@ -402,9 +428,31 @@ class MarchingNeRF(models.NeRF):
         ctx = self._context(dev)
         occ = grid.detach().to(dev).contiguous().clone()
         bits = ops.pack_occupancy(occ)
-        _lib.check(ctx.lib.neo_vanilla_set_occupancy(ctx.handle, ptr(bits), G, _c3(lo), _c3(hi), int(bool(clip)), ctx.stream()))
+        _lib.check(getattr(ctx.lib, self._occ_entry)(ctx.handle, ptr(bits), G, _c3(lo), _c3(hi), int(bool(clip)), ctx.stream()))
         self._occupancy, self._occ_box, self._occ_clip, self._occ_ctx = occ, (lo, hi), bool(clip), ctx
         self._occ_bits = bits       # the training row builder reads the caller-side bits (render_train_marching)
+
+
+class MarchingNeRF(_BoxOccupancy, models.NeRF):
+    """`models.NeRF` with an occupancy grid over a box, the marching frame, and training through the grid
+    (`render_train_marching`, `init_occupancy`, `update_occupancy`).  `forward`, `eval_mlp` and the parent's training path read none
+    of this."""
+
+    # rays per window of render_marching (None: the library's default, 8192): a window bounds the extra workspace at 68 bytes per
+    # (ray, sample) of one window and segment; results do not depend on it
+    march_window = None
+    _occ_entry = "neo_vanilla_set_occupancy"
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._init_box_occupancy()
+        self.last_train_kept = None
+        self._run = None            # init_occupancy: dict(box, G, clip, density, updates)
+
+    @property
+    def occupancy_density(self):
+        """The running density of `update_occupancy` as a float (G,G,G) device tensor (a copy), or None before `init_occupancy`."""
+        return None if self._run is None else self._run["density"].clone()
 
     @torch.no_grad()
     def init_occupancy(self, box, resolution, clip=False):
@@ -607,32 +655,165 @@ class MarchingNeRF(models.NeRF):
         return out
 
 
+_PIX_SRC_KEYS = ("src_poses", "src_focal", "src_c", "src_imgs")
+
+
+class MarchingPixelNeRF(_BoxOccupancy, models.PixelNeRF):
+    """`models.PixelNeRF` - same constructor, `state_dict` keys, `forward`, `eval_mlp` and training path - with an occupancy grid
+    over a box and the marching frame (include/neo360_hip.h: PIXELNERF MARCHING FRAME).  Given the scene latent, the source cameras
+    and the weights, a PixelNeRF density depends on the position alone, so the grid describes ONE scene: `set_scene` removes it."""
+
+    # rays per window of render_marching (None: the library's default); results do not depend on it
+    march_window = None
+    _occ_entry = "neo_pix_set_occupancy"
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._init_box_occupancy()
+
+    @torch.no_grad()
+    def set_scene(self, latent, image_wh):
+        """`PixelNeRF.set_scene`, after which no grid is installed: a grid describes one scene (as `NeRF_TP.set_scene`).  An
+        attached encoder that runs again on new `src_imgs` therefore falls back to "no grid" - slower, never wrong."""
+        super().set_scene(latent, image_wh)
+        self.set_occupancy(None)
+
+    @torch.no_grad()
+    def _occupancy_sigma(self, rays, box, resolution, probes, points_per_piece=1 << 20):
+        """max(sigma of slot 0, sigma of slot 1) on the lattice of `occupancy_lattice_box`, its columns evaluated as rays by
+        `eval_mlp` in pieces of at most points_per_piece points; the maximum is taken on the device."""
+        dev = next(self.parameters()).device
+        M = resolution * probes
+        c, o, d = occupancy_lattice_box(box, resolution, probes, dev)
+        src = {k: rays[k] for k in _PIX_SRC_KEYS if k in rays}
+        sigma = torch.empty(M * M, M, device=dev)
+        step = max(1, points_per_piece // M)
+        for i in range(0, M * M, step):
+            piece = dict(src, rays_o=o[i:i + step], rays_d=d[i:i + step], viewdirs=d[i:i + step])
+            t = c[None, :].expand(piece["rays_o"].shape[0], M).contiguous()
+            sigma[i:i + step] = torch.maximum(self.eval_mlp(0, piece, t)[..., 3], self.eval_mlp(1, piece, t)[..., 3])
+        return sigma.reshape(M, M, M)
+
+    @torch.no_grad()
+    def build_occupancy(self, rays, box, resolution, sigma_threshold, probes=2, dilate=1, clip=False):
+        """Builds, installs and returns the grid of the current scene over box = (lo, hi).  rays supplies the source cameras
+        (`src_poses`, `src_focal`, `src_c`; `src_imgs` for an attached encoder) - its own rays are not read.  Both MLPs are
+        evaluated with `eval_mlp` on the (resolution * probes)^3 lattice of cell sub-centres, a cell is occupied iff the larger of
+        the two densities at one of its probes is not <= sigma_threshold, and the result is dilated by `dilate` cells over the
+        26-neighbourhood, on the device (`occupancy_from_sigma_box`).  sigma_threshold has no default: nobody has measured one on
+        trained weights.  ValueError, before any device access, for a bad box, resolution, probes, dilate or threshold."""
+        G, probes, dilate = ops._check_build(resolution, sigma_threshold, probes, dilate, "build_occupancy")
+        box = _check_box(box, "build_occupancy")
+        sigma = self._occupancy_sigma(rays, box, G, probes)
+        grid = occupancy_from_sigma_box(sigma, G, sigma_threshold, probes, dilate, ctx=self._context(sigma.device))
+        self.set_occupancy(grid, box, clip)
+        return grid
+
+    @torch.no_grad()
+    def render_marching(self, rays, eps, white_bkgd, near, far, chunk=None, segment=64, coarse=False, grid=True, return_samples=False):
+        """`forward(rays, False, white_bkgd, near, far, chunk)` in which a sample is evaluated iff the installed grid keeps it
+        (`occupancy_keep_box` with dirs = rays_d; grid=False or no grid: every sample is kept) AND it lies in front of its ray's
+        stop (neo_pix_render_marching).  The stop is `termination_stops_vanilla` on the level's rows with the samples that are not
+        kept zeroed: segment 0 is always marched, segment k >= 1 iff the transmittance at every earlier boundary was not below
+        eps.  A sample that is not evaluated has a zero row and weight exactly 0; an evaluated one is bitwise `eval_mlp`'s at the
+        call's `chunk` (all rays of the call form ONE reference chunk unless chunk is given: the direction a sample is seen along
+        is that of ray (b N + j) mod B of its chunk, as in `forward`).
+        Level 1 follows the stop rule; level 0 only with coarse=True, which moves the level-1 positions: NO bound is claimed for
+        that mode.  With coarse=False, against the same call at eps = 0: a ray that never stops is bitwise equal, and a stopped
+        ray's level-1 rgb differs by at most 1.003 * trans per channel and its depth by at most 1.001 * far * trans, trans < eps
+        being its transmittance at the stop.  Without a grid at eps = 0, with grid=False, with an all-ones grid, or with a box that
+        holds no sample and clip=False, the six outputs are bitwise `forward`'s.  Results do not depend on `march_window`, on the
+        stream, or on whether a frame is one call or the caller's loop over its reference chunks.
+        ValueError, before any device access, for eps outside [0, 1) or NaN, a segment that is not a positive multiple of 64, or
+        a chunk that is not a positive integer; NeoError when grid=True and the installed grid belongs to another context.
+
+        Returns [(rgb (B,3), acc (B,), depth (B,))] * 2; with return_samples a third element holds per level
+        (t (B,N), weights (B,N), keep (B,N) bool - the grid's verdict on the whole row, behind the stop as well - stop (B,) int32,
+        rows (B,N,4)): the evaluated set is keep & (j < stop).  `self.last_march_kept` (int64[2]: evaluated samples per level)
+        stays on the device; nothing is read back."""
+        eps, segment = ops._check_termination(eps, segment, "render_marching")
+        if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
+            raise ValueError("render_marching: chunk must be a positive integer or None, got %r" % (chunk,))
+        raw = (rays["rays_o"], rays["rays_d"], rays["viewdirs"])
+        rays_o, rays_d, viewdirs = ray_rows(rays)
+        dev = rays_o.device
+        ctx = self._context(dev)
+        self._ensure_scene(rays)       # an encoder that runs again removes the grid (set_scene)
+        if self._scene_ctx is not ctx:
+            raise _lib.NeoError("the scene latent was uploaded on a different device")
+        if grid and self._occupancy is not None and self._occ_ctx is not ctx:
+            raise _lib.NeoError("the occupancy grid does not belong to this module's context on %s: install it again" % dev)
+        self._sync_weights(ctx)
+        self._before_call(ctx)
+        B = rays_o.shape[0]
+        host_poses, NV, focal, cx, cy = self._camera_args(rays)
+        n = (self.num_coarse_samples + 1, self.num_coarse_samples + 1 + self.num_fine_samples)
+        outs, samples, counts = [], [], []
+
+        def launch():
+            self._set_mode(ctx, "_pix_window", "neo_pix_set_march_window", int(self.march_window or 0))
+            outs.extend((torch.empty(B, 3, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)) for _ in range(2))
+            structs = [None, None]
+            if return_samples:
+                t0 = torch.empty(n[0], device=dev)
+                for lv in range(2):
+                    s = dict(t=t0 if lv == 0 else torch.empty(B, n[1], device=dev), w=torch.empty(B, n[lv], device=dev),
+                             keep=torch.empty(B, n[lv], dtype=torch.bool, device=dev),
+                             stop=torch.empty(B, dtype=torch.int32, device=dev), rows=torch.empty(B, n[lv], 4, device=dev))
+                    samples.append(s)
+                    structs[lv] = ctypes.byref(_lib.VanillaMarchSamples(*(s[k].data_ptr() for k, _ in _lib.VanillaMarchSamples._fields_)))
+            counts.append(torch.empty(2, dtype=torch.int64, device=dev))
+            _lib.check(ctx.lib.neo_pix_render_marching(
+                ctx.handle, ptr(rays_o), ptr(rays_d), ptr(viewdirs), B, int(chunk or max(B, 1)), host_poses, NV, focal, cx, cy,
+                float(near), float(far), self.num_coarse_samples, self.num_fine_samples, int(bool(white_bkgd)), eps, segment,
+                int(bool(coarse)), int(bool(grid)), ptr(outs[0][0]), ptr(outs[0][1]), ptr(outs[0][2]), ptr(outs[1][0]),
+                ptr(outs[1][1]), ptr(outs[1][2]), structs[0], structs[1], counts[0].data_ptr(), ctx.stream()))
+            self._after_call(ctx)
+            return [t for lv in outs for t in lv] + [v for s in samples for v in s.values()] + counts
+        self._launch_overlapped(ctx, dev, raw, (rays_o, rays_d, viewdirs), launch)
+        self.last_march_kept = counts[0]
+        out = list(outs)
+        if return_samples:
+            samples[0]["t"] = samples[0]["t"][None, :].expand(B, n[0])
+            out.append([tuple(s[k] for k in ("t", "w", "keep", "stop", "rows")) for s in samples])
+        return out
+
+
 @torch.no_grad()
 def render_marching_rays(model, batch, eps, chunk=32768, white_bkgd=False, near=0.2, far=3.0, segment=64, coarse=False, grid=True,
                          check=True, on_range="retry_f32"):
-    """Frame of a MarchingNeRF with empty space skipped and early ray termination: the fine level of
-    `model.render_marching(batch, eps, ...)` on every ray of `batch`, `chunk` rays a library call (a vanilla ray does not depend on
-    its chunk: the chunk only bounds the workspace).  Returns dict(rgb (R,3), depth (R,), acc (R,)) plus `kept_fraction`, a (2,)
-    float64 DEVICE tensor - the share of samples evaluated at level 0 and level 1 (reading it synchronises, the call does not) -
-    and `target` / `instance_mask` passed through.  check / on_range: the flag read, range-guard retry and latch of
-    `render.render_rays_test` (the same code path)."""
+    """Frame of a MarchingNeRF or a MarchingPixelNeRF with empty space skipped and early ray termination: the fine level of
+    `model.render_marching(batch, eps, ...)` on every ray of `batch`.  MarchingNeRF: `chunk` rays a library call (a vanilla ray does
+    not depend on its chunk: the chunk only bounds the workspace).  MarchingPixelNeRF: ONE library call per frame with the reference
+    `chunk` passed down, as `render.render_rays_test` does for PixelNeRF - a PixelNeRF ray depends on its chunk - and `batch` carries
+    the source cameras.  Returns dict(rgb (R,3), depth (R,), acc (R,)) plus `kept_fraction`, a (2,) float64 DEVICE tensor - the
+    share of samples evaluated at level 0 and level 1 (reading it synchronises, the call does not) - and `target` /
+    `instance_mask` passed through.  check / on_range: the flag read, range-guard retry and latch of `render.render_rays_test` (the
+    same code path); a retry lands on the compact instantiation of the exact kernel."""
     from . import render
-    if not isinstance(model, MarchingNeRF):
-        raise TypeError("render_marching_rays renders MarchingNeRF modules, got %r" % type(model))
+    if not isinstance(model, (MarchingNeRF, MarchingPixelNeRF)):
+        raise TypeError("render_marching_rays renders MarchingNeRF and MarchingPixelNeRF modules, got %r" % type(model))
     if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
         raise ValueError("render_marching_rays: chunk must be a positive integer, got %r" % (chunk,))
     ops._check_termination(eps, segment, "render_marching_rays")
+    pix = isinstance(model, MarchingPixelNeRF)
     rays_o, viewdirs, rays_d = ray_rows(batch, ("rays_o", "viewdirs", "rays_d"), on_device=False)
     R = rays_o.shape[0]
+    n0 = model.num_coarse_samples + 1
+    per = (float(max(R * n0, 1)), float(max(R * (n0 + model.num_fine_samples), 1)))      # scalar divisors: no host read, no copy
 
     def once():
         parts, kept = [], None
-        for i in range(0, max(R, 1), chunk):
-            part = dict(rays_o=rays_o[i:i + chunk], viewdirs=viewdirs[i:i + chunk], rays_d=rays_d[i:i + chunk])
-            parts.append(model.render_marching(part, eps, white_bkgd, near, far, segment=segment, coarse=coarse, grid=grid)[1])
-            kept = model.last_march_kept if kept is None else kept + model.last_march_kept
-        n0 = model.num_coarse_samples + 1
-        per = (float(max(R * n0, 1)), float(max(R * (n0 + model.num_fine_samples), 1)))      # scalar divisors: no host read, no copy
+        if pix:
+            frame = dict({k: batch[k] for k in _PIX_SRC_KEYS if k in batch}, rays_o=rays_o, viewdirs=viewdirs, rays_d=rays_d)
+            parts.append(model.render_marching(frame, eps, white_bkgd, near, far, chunk=chunk, segment=segment, coarse=coarse,
+                                               grid=grid)[1])
+            kept = model.last_march_kept
+        else:
+            for i in range(0, max(R, 1), chunk):
+                part = dict(rays_o=rays_o[i:i + chunk], viewdirs=viewdirs[i:i + chunk], rays_d=rays_d[i:i + chunk])
+                parts.append(model.render_marching(part, eps, white_bkgd, near, far, segment=segment, coarse=coarse, grid=grid)[1])
+                kept = model.last_march_kept if kept is None else kept + model.last_march_kept
         kept = kept.double()
         return dict(rgb=torch.cat([p[0] for p in parts]), acc=torch.cat([p[1] for p in parts]), depth=torch.cat([p[2] for p in parts]),
                     kept_fraction=torch.stack([kept[0] / per[0], kept[1] / per[1]]))
